@@ -87,6 +87,9 @@ def parse():
     p.add_argument("--fft-whole-blocks", action="store_true",
                    help="fftconv: round --samples up to whole overlap-save hops (12288) so that no ragged last block is transformed")
     p.add_argument("--dump-output", default="", help="rank 0 saves the last step's (gathered) output rows as .npy (tests)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes what the last timed step delivered (its gathered rows with a gather) as DIR/<workload>.npy, "
+                        "float32, at most 64 MB (a fixed, seeded sample of the channels beyond that): two builds compare output for output")
     p.add_argument("--force-dist", action="store_true",
                    help="tests: initialise the process group even with one rank, so that the RCCL gather path (side stream, async_op) runs on a one-GPU box")
     return p.parse_args()
@@ -167,6 +170,33 @@ def synth_cs16(torch, C, N, dev, seed, chan0=0):
         out[c0:c0 + re.shape[0], :, 0] = (re.to(torch.int64) + (h & 0xFFFF) % 129 - 64).to(torch.int16)
         out[c0:c0 + re.shape[0], :, 1] = (im.to(torch.int64) + (h >> 16) % 129 - 64).to(torch.int16)
     return out
+
+
+def randn_cf32(torch, C, N, dev, seed):
+    """Seeded complex<float> noise (0.3 rms per component), generated on the GPU: the same batches run after run."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    return torch.randn((C, N, 2), dtype=torch.float32, device=dev, generator=g) * 0.3
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: data bytes per run at most
+
+
+def dump_outputs(path, name, out, count, rows_axis=0):
+    """--dump-outputs: the first `count` outputs of every row of the output buffer `out` (a device tensor; channel rows on
+    `rows_axis`, outputs on the axis after it) as path/<name>.npy in float32, which holds int16 outputs exactly. Beyond
+    DUMP_BYTES a fixed, seeded sample of the rows is written, in row order."""
+    import numpy as np
+    import torch
+    y = out.narrow(rows_axis + 1, 0, count)
+    rows = y.shape[rows_axis]
+    keep = min(rows, max(1, DUMP_BYTES // (max(1, y.numel() // max(rows, 1)) * 4)))
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(2024).choice(rows, size=keep, replace=False))
+        y = y.index_select(rows_axis, torch.from_numpy(idx).to(y.device))
+        sys.stderr.write("bench.py: --dump-outputs keeps %d of %d rows of %s (numpy default_rng(2024), sorted)\n" % (keep, rows, name))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), y.float().cpu().numpy())
 
 
 def cpu_model():
@@ -455,7 +485,18 @@ class BenchError(RuntimeError):
 
 class Workload:
     """One --workload: the plan, resident inputs, double-buffered outputs, the launch, and the oracle check."""
-    pass
+
+    def restart(self):
+        """Every node of the step back to a fresh stream (the state a new plan starts from)."""
+        for n in self.nodes:
+            n.reset()
+
+    def delivered(self, got):
+        """Outputs per channel row of a step whose launch returned `got`: a count, one per buffer of a multi-buffer step, or
+        None where a call emits one output per input sample."""
+        if got is None:
+            return self.N
+        return sum(got) if isinstance(got, list) else int(got)
 
 
 def multi_verify(verify1, B, N, D, real):
@@ -487,11 +528,12 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
     import numpy as np
     C, N = a.channels, a.samples
     w = Workload()
-    w.name, w.N, w.verify = wl, N, None
+    w.name, w.N, w.verify, w.nodes = wl, N, None, []   # (w.nodes: every node of the step, for restart())
     order, D = a.order, a.decim
     B = max(1, a.buffers)
     NB = N * B   # samples per channel per step (--buffers reference-sized buffers in one launch)
     cs16 = lambda n=N: [synth_cs16(torch, C, n, dev, 1234 + b, chan0=rank * C) for b in range(a.batches)]
+    cf32 = lambda n: [randn_cf32(torch, C, n, dev, 4321 + 1000 * rank + b) for b in range(a.batches)]
     w.bound, w.compute = "hbm", None
     if B > 1 and wl not in ("iqbb_fm", "iqbb_usb", "iqbb_fm_cu8", "bb_real_fm"):
         raise BenchError("--buffers is for the iqbb_* and bb_real_fm workloads")
@@ -550,10 +592,12 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
             def run_chain(b, o):
                 k = node.process_dev(w.ins[b].data_ptr(), N, N, w.mids[o].data_ptr(), n_out)
                 de.process_dev(w.mids[o].data_ptr(), k, n_out, w.outs[o].data_ptr(), n_out)
+                return k
             w.run = run_chain
             w.kernels = w.kernels + de.kernel_names(node.out_count(N))
             w.desc += " -> FMDeemph(alpha %d)" % de_alpha
             w.key += "/deemph"
+            w.nodes.append(de)
             w.verify_needs_chan = True
 
         w.verify_needs_n0 = w.verify_needs_pre = True
@@ -702,7 +746,7 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
         w.in_bytes, w.alg_bytes = 8.0, 9.0
         n_out = N // 8 + 1
         w.outs = [torch.zeros((C, n_out, 2), dtype=torch.float32, device=dev) for _ in range(nbuf_out)]
-        w.ins = [torch.randn((C, N, 2), dtype=torch.float32, device=dev) * 0.3 for b in range(a.batches)]
+        w.ins = cf32(N)
         w.run = lambda b, o: node.process_dev(w.ins[b].data_ptr(), N, N, w.outs[o].data_ptr(), n_out)
         w.dtype, w.kernels = "f32", node.kernel_names(N)
         w.desc = "float baseband: shift 100 kHz -> FIRLowPass<cf32>(127) -> /8"
@@ -723,7 +767,7 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
         node = sa.FFTConv(ctx, sa.FFTCONV_OLA, 2048, Ks, channels=C, max_in=N)
         w.in_bytes, w.alg_bytes = 8.0, 8.0 + 8.0 * len(bands)
         w.outs = [torch.zeros((len(bands), C, N, 2), dtype=torch.float32, device=dev) for _ in range(nbuf_out)]
-        w.ins = [torch.randn((C, N, 2), dtype=torch.float32, device=dev) * 0.3 for b in range(a.batches)]
+        w.ins = cf32(N)
         w.run = lambda b, o: node.process_dev(w.ins[b].data_ptr(), N, N, w.outs[o].data_ptr(), N)
         w.dtype, w.kernels, w.bound = "f32", ["fftconv_fused_kernel"], "lds/issue"
         w.desc = "FFT filter bank: 2048-point overlap-add, 1024-sample blocks, %d bands behind one forward transform" % len(bands)
@@ -750,7 +794,7 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
         node = sa.FFTConv(ctx, sa.FFTCONV_OLA, 2 * Nb, Kk, channels=C, max_in=N)
         w.in_bytes, w.alg_bytes = 8.0, 16.0
         w.outs = [torch.zeros((C, N, 2), dtype=torch.float32, device=dev) for _ in range(nbuf_out)]
-        w.ins = [torch.randn((C, N, 2), dtype=torch.float32, device=dev) * 0.3 for b in range(a.batches)]
+        w.ins = cf32(N)
         w.run = lambda b, o: node.process_dev(w.ins[b].data_ptr(), N, N, w.outs[o].data_ptr(), N)
         w.dtype, w.kernels, w.bound = "f32", ["fftconv_fused_kernel"], "lds/issue"
         w.desc = "FFT filter, reference mode: overlap-add, blocks of 8192, 16384-point transforms, 8192-tap FilterSource kernel 50..150 kHz"
@@ -771,7 +815,7 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
         node = sa.FFTConv(ctx, sa.FFTCONV_OLS, 16384, tapsf, channels=C, max_in=N)
         w.in_bytes, w.alg_bytes = 8.0, 16.0
         w.outs = [torch.zeros((C, N, 2), dtype=torch.float32, device=dev) for _ in range(nbuf_out)]
-        w.ins = [torch.randn((C, N, 2), dtype=torch.float32, device=dev) * 0.3 for b in range(a.batches)]
+        w.ins = cf32(N)
         w.run = lambda b, o: node.process_dev(w.ins[b].data_ptr(), N, N, w.outs[o].data_ptr(), N)
         w.dtype, w.kernels, w.bound = "f32", ["fftconv_fused_kernel"], "lds/issue"
         w.desc = "FFT convolution, overlap-save L=16384, 4097 taps (hop 12288), %d samples per channel per step" % N
@@ -814,6 +858,7 @@ def build_workload(a, wl, sa, torch, shard, ctx, dev, rank, nbuf_out):
     else:
         raise BenchError("unknown workload " + wl)
     w.node = node
+    w.nodes.insert(0, node)
     if B > 1:
         w.N = NB
     w.key += "/C%d/N%d" % (C, w.N)
@@ -825,6 +870,10 @@ def main():
     ends in ONE JSON line on rank 0 — with an `error` key and value null — and a non-zero exit code."""
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
+    if a.steps < 1 or a.warmup < 0:
+        if rank == 0:
+            print(error_line(a, "--steps must be at least 1 and --warmup at least 0"), flush=True)
+        raise SystemExit(2)
     if a.comm == "sdrhip":   # one process whatever --gpus says: the library owns the ranks
         try:
             run_sdrhip(a)
@@ -1090,6 +1139,7 @@ def run(a):
         pending = [None, None]   # the gather that still reads outs[o]
         ev = [torch.cuda.Event(), torch.cuda.Event()]
         it = [0]                 # steps run so far on this plan: step i reads batch i % batches and writes output buffer i & 1
+        got = [None]             # what the last step's launch returned (its output count)
 
         def issue_gather(o):
             if g_ok:   # RCCL: on the side stream, behind this step's kernel; the next step starts meanwhile
@@ -1107,7 +1157,7 @@ def run(a):
                 pending[o].wait()
                 pending[o] = None
             if compute:
-                w.run(i % a.batches, o)
+                got[0] = w.run(i % a.batches, o)
                 it[0] = i + 1
             if with_gather:
                 issue_gather(o)
@@ -1166,6 +1216,11 @@ def run(a):
             pre_s = time.perf_counter() - t1
             last_ms = timer.elapsed_ms() / chunk
             sustained = {"ms_per_launch": tot_ms / launches, "launches": launches, "last_chunk_ms_per_launch": last_ms}
+        # ---- the streams start over: what the warm-up and the timed steps compute depends on the arguments alone, not on how
+        # many launches the time-bound pre-conditioning fitted in ----
+        torch.cuda.synchronize()
+        w.restart()
+        it[0] = 0
         # ---- W warm-up steps, then EXACTLY K timed steps between barrier + synchronize on both sides ----
         for _ in range(W):
             step(gather)
@@ -1177,6 +1232,10 @@ def run(a):
         if a.dump_output and rank == 0:
             torch.cuda.synchronize()
             np.save(a.dump_output, (gathered if gathered is not None else w.outs[(it[0] - 1) & 1]).cpu().numpy())
+        if a.dump_outputs and rank == 0:
+            torch.cuda.synchronize()
+            dump_outputs(a.dump_outputs, wl, gathered if gathered is not None else w.outs[(it[0] - 1) & 1], w.delivered(got[0]),
+                         0 if gathered is not None else getattr(w, "out_rows_axis", 0))
 
         # the same K steps without the gather (the per-GPU kernel alone) and the gather alone (no kernel), reported
         # beside the headline of a gathered run
@@ -1392,7 +1451,7 @@ def run_sdrhip(a):
     gathered = torch.zeros((G * C, row_elems), dtype=w0.outs[0].dtype, device=tdev[0])
     for d in set(devices):
         torch.cuda.synchronize(d)
-    it = [0]
+    it, got = [0], [None]
 
     def step(with_gather, compute=True):
         i = it[0]
@@ -1400,7 +1459,7 @@ def run_sdrhip(a):
         comm.gather_wait(o)   # (enqueued on the ranks' streams: the gather of step i - 2 has read outs[o]; a slot never begun: nothing)
         if compute:
             for r in range(G):
-                ws[r].run(i % a.batches, o)
+                got[0] = ws[r].run(i % a.batches, o)
             it[0] = i + 1
         if with_gather:   # on the comm's own streams, behind this step's kernels: the next step's kernels start meanwhile
             comm.gather_begin(o, [ws[r].outs[o].data_ptr() for r in range(G)], [C * row_bytes] * G, gathered.data_ptr(), 0)
@@ -1429,6 +1488,10 @@ def run_sdrhip(a):
             tot += ms[0]
             n += chunk
         pre_s, sustained = time.perf_counter() - t1, tot / n
+    comm.synchronize()   # (the streams start over, as in run())
+    for w in ws:
+        w.restart()
+    it[0] = 0
     for _ in range(W):
         step(True)
     wall, ms = timed(K, True)
@@ -1449,6 +1512,9 @@ def run_sdrhip(a):
             verified["ok"] = False
     if a.dump_output:
         np.save(a.dump_output, gathered.cpu().numpy())
+    if a.dump_outputs:
+        torch.cuda.set_device(devices[0])
+        dump_outputs(a.dump_outputs, wl, gathered, w0.delivered(got[0]))
     wall_ng, ms_ng = timed(K, False)
     wall_go, _ = timed(K, True, compute=False)
     alg, inb = w0.alg_bytes, w0.in_bytes

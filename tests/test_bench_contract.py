@@ -138,22 +138,29 @@ def test_two_ranks_through_hip_nodes_match_single_process(tmp_path, workload):
     assert np.count_nonzero(a) > a.size // 2   # real demodulated output, not zeros
 
 
+# ranks of the launcher pre-flight, all on device 0: with the test process itself five processes hold the device, within
+# what a shared GPU host lets one job open at once (eight ranks would be nine)
+PREFLIGHT_RANKS = 4
+
+
 @pytest.mark.gpu
-def test_eight_ranks_preflight_through_the_real_launcher(tmp_path):
-    """Multi-GPU pre-flight at the REAL rank count on one device (the driver's scaling run is first contact with 8
-    devices): `bench.py --gpus 8 --global-channels 8192` through the same parent -> torch.distributed.run -> 8 ranks path the
-    driver's command takes (gloo rendezvous, every rank on device 0), BASELINE config 5's chain with the gather — all 8 ranks
-    counted by the all-reduce, per-rank launch times present, and the gathered 8192 rows equal the single-rank run bit for bit."""
+def test_multi_rank_preflight_through_the_real_launcher(tmp_path):
+    """Multi-GPU pre-flight on one device (the driver's scaling run is first contact with 8 devices): `bench.py
+    --gpus 4 --global-channels 8192` through the same parent -> torch.distributed.run -> ranks path the driver's command takes
+    (gloo rendezvous, every rank on device 0), BASELINE config 5's chain with the gather — all ranks counted by the
+    all-reduce, per-rank launch times present, and the gathered 8192 rows equal the single-rank run bit for bit. (The 8-rank
+    count itself runs in one process: test_eight_rank_contexts_through_the_c_abi.)"""
     import numpy as np
+    G = PREFLIGHT_RANKS
     common = ["--samples", "16384", "--steps", "3", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--sustain-seconds", "0", "--verify-channels", "2"]
-    eight, one = str(tmp_path / "eight.npy"), str(tmp_path / "one.npy")
-    d8 = _bench(["--gpus", "8", "--backend", "gloo", "--force-device", "0", "--global-channels", "8192", "--dump-output", eight] + common, timeout=1500)
-    assert d8["n_gpus"] == 8 and d8["scaling"] == "strong" and d8["config"]["global_channels"] == 8192 and d8["config"]["channels_per_gpu"] == 1024
-    rf = d8["roofline"]
-    assert rf["ranks_seen"] == 8 and 0 < rf["avg_launch_ms_min_rank"] <= rf["avg_launch_ms_max_rank"]
-    assert rf["without_gather_msamples_s"] > 0 and d8["verified"] is True
+    many, one = str(tmp_path / "many.npy"), str(tmp_path / "one.npy")
+    dg = _bench(["--gpus", str(G), "--backend", "gloo", "--force-device", "0", "--global-channels", "8192", "--dump-output", many] + common, timeout=1500)
+    assert dg["n_gpus"] == G and dg["scaling"] == "strong" and dg["config"]["global_channels"] == 8192 and dg["config"]["channels_per_gpu"] == 8192 // G
+    rf = dg["roofline"]
+    assert rf["ranks_seen"] == G and 0 < rf["avg_launch_ms_min_rank"] <= rf["avg_launch_ms_max_rank"]
+    assert rf["without_gather_msamples_s"] > 0 and dg["verified"] is True
     d1 = _bench(["--gpus", "1", "--workload", "iqbb_usb", "--channels", "8192", "--dump-output", one] + common)
-    a, b = np.load(eight), np.load(one)
+    a, b = np.load(many), np.load(one)
     assert a.shape == b.shape and a.shape[0] == 8192 and a.shape[1] >= 2048 and np.array_equal(a, b) and np.count_nonzero(a) > a.size // 2
     assert rf["gather_bytes_per_step"] == a.size * 2
 
@@ -350,3 +357,44 @@ def test_multi_buffer_workloads_verify(workload, extra):
         assert ks == ["iqbb_hot_kernel"], ks
     else:
         assert ks[-1] == "iqbb_fm_multi_fixup_kernel", ks
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_its_bytes(tmp_path, monkeypatch):
+    """--dump-outputs writes the delivered outputs of every row as float32; past its byte budget a fixed, seeded sample of the
+    rows (channels), in row order — the same sample every run — on whichever axis holds the channels."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.arange(40 * 7, dtype=torch.int16).reshape(40, 7)
+    bench.dump_outputs(str(tmp_path / "all"), "w", out, 6)
+    y = np.load(tmp_path / "all" / "w.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, out[:, :6].numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 6 * 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "w", out, 6)
+    y, y2 = np.load(tmp_path / "s1" / "w.npy"), np.load(tmp_path / "s2" / "w.npy")
+    rows = (y[:, 0] // 7).astype(int)
+    assert y.shape == (10, 6) and np.array_equal(y, y2) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(y, out[rows, :6].numpy())
+    bank = torch.randn(4, 40, 9, 2)   # (the filter bank's [bands, channels, n, 2])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 10 * 8 * 2 * 4)
+    bench.dump_outputs(str(tmp_path / "b"), "w", bank, 8, rows_axis=1)
+    assert np.load(tmp_path / "b" / "w.npy").shape == (4, 10, 8, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["iqbb_fm", "fbb_f32"])
+def test_dump_outputs_repeat_run_for_run(tmp_path, workload):
+    """--dump-outputs DIR: the last timed step's delivered outputs as DIR/<workload>.npy (float32), the same from run to run
+    with the same arguments, however long the time-bound pre-conditioning ran — and what --dump-output saves of that step."""
+    import numpy as np
+    common = ["--workload", workload, "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+              "--verify-channels", "4"]
+    d1 = _bench(common + ["--sustain-seconds", "0.3", "--dump-outputs", str(tmp_path / "a"), "--dump-output", str(tmp_path / "raw.npy")])
+    d2 = _bench(common + ["--sustain-seconds", "0.1", "--dump-outputs", str(tmp_path / "b")])
+    assert d1["verified"] is True and d2["verified"] is True and d1["steps"] == 3
+    a, b = np.load(tmp_path / "a" / (workload + ".npy")), np.load(tmp_path / "b" / (workload + ".npy"))
+    assert a.dtype == np.float32 and a.shape[:2] == (16, 4096) and np.array_equal(a, b)
+    raw = np.load(tmp_path / "raw.npy")
+    assert np.array_equal(a, raw[:, :4096].astype(np.float32)) and np.count_nonzero(a) > a.size // 2
