@@ -175,7 +175,8 @@ int sdrhip_iqbb_i16_kernel_names(sdrhip_iqbb_i16 *h, char *buf, size_t len);
  * plane, info[4] = waves per workgroup, info[5] = input kind (0 complex<int16>, 1 complex<uint8>, 2 real int16), info[6] =
  * padded filter length, info[7] = history samples kept per channel. n >= 8; with n >= 9 also info[8] = the buffer boundaries the
  * last one-launch sdrhip_iqbb_i16_process_dev_multi call left to its fix-up launch (0: the hot kernel wrote them all itself; -1: no
- * such call yet). */
+ * such call yet); with n >= 11 also info[9], info[10] = first step and number of steps the /8 hot kernel issues at all (the
+ * taps' low byte plane is all zero outside them; [0, S) where every step is issued, 0 and 0 without a hot kernel). */
 int sdrhip_iqbb_i16_plan_info(sdrhip_iqbb_i16 *h, int *info, int n);
 /* outputs the next call of n_in samples will produce (does not advance the state) */
 int sdrhip_iqbb_i16_out_count(sdrhip_iqbb_i16 *h, size_t n_in, size_t *n_out);

@@ -16,8 +16,9 @@
 //     only this wave reads them. While slice i is split, multiplied and finished in buffer i&1, the DMA of slice i+1
 //     lands in the other buffer: it is issued at the top of iteration i and has a whole slice period to arrive
 //     (round 2's single raw area could only be refilled after the split, half a period before it was needed).
-//   * The K-step range that needs the taps' high byte plane is a compile-time parameter [S0, S0 + NH): the K loop is
-//     straight-line code with the operands of step s+1 in flight while step s's MFMAs issue.
+//   * The K-step range that needs the taps' high byte plane is a compile-time parameter [S0, S0 + NH), and so is the range
+//     [L0, L0 + NL) outside which the low plane is all zero too (the window's edge steps of a windowed design): the K loop
+//     is straight-line code over [L0, L0 + NL) with the operands of step s+1 in flight while step s's MFMAs issue.
 //   * Persistent grid of (virtual) 4-wave workgroups, static equal-length work units, rotating wave priority.
 //     A real workgroup is NW waves (4, 8 or 16): NW/4 virtual workgroups sharing one LDS copy of the tap fragments and
 //     the rotation table — long filters' fragments (17-34 KB) would otherwise cap the CU at 2 waves per SIMD.
@@ -101,6 +102,26 @@ constexpr HotRange hot_ranges_17[] = {{6, 5, 8}, {4, 9, 8}, {0, 17, 16}};
 // (33 steps: the taps sit at the END of the 513-tap window — zero-padded at the front — so the steps that need the high plane
 // move with the order: 14 ... 18 at 513 taps, 17 ... 22 at 400, 20 ... 25 at 300, 22 ... 26 at 258)
 constexpr HotRange hot_ranges_33[] = {{12, 9, 8}, {16, 9, 8}, {18, 9, 8}, {8, 17, 8}, {0, 33, 8}};
+// Low-plane ranges [L0, L0 + NL) of the /8 kernel (complex<int16> and complex<uint8>): the K steps whose low-byte tap
+// fragments are not all zero, narrowest first, the last one covering every step. Steps outside it multiply zero taps only and
+// are not issued. A range serves a plan when it covers the plan's low-plane mask AND its high-plane range: the loop runs
+// over [L0, L0 + NL) alone. Only where the designers' plans produce one (design_iqbb_taps, Blackman window: the outer taps
+// fall below one Q14 unit): 9 steps, steps 1 ... 7 — the 127-tap headline plan's taps are non-zero at indices 18 ... 109 of
+// the 129-tap window (at 100 or 129 taps, or 100 kHz wide, an edge step is live). Other classes: the full range only.
+struct HotLoRange { int L0, NL; };
+constexpr HotLoRange hot_lo_ranges_9[] = {{1, 7}, {0, 9}};
+inline const HotLoRange *hot_lo_ranges(int S, int *count) {
+  static const HotLoRange full[] = {{0, 2}, {0, 3}, {0, 5}, {0, 17}, {0, 33}};
+  switch (S) {
+    case 9: *count = 2; return hot_lo_ranges_9;
+    case 2: *count = 1; return full;
+    case 3: *count = 1; return full + 1;
+    case 5: *count = 1; return full + 2;
+    case 17: *count = 1; return full + 3;
+    case 33: *count = 1; return full + 4;
+    default: *count = 0; return nullptr;
+  }
+}
 inline const HotRange *hot_ranges(int S, int *count) {
   switch (S) {
     case 2: *count = 1; return hot_ranges_2;
@@ -118,8 +139,9 @@ struct HotLaunch { unsigned grid; hipStream_t stream; };
 void hot_launch_s2(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 void hot_launch_s3(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 void hot_launch_s5(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s9_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s9_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
+// (9 steps: `lo` indexes hot_lo_ranges(9))
+void hot_launch_s9_cs16(int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
+void hot_launch_s9_cu8(int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 void hot_launch_s17_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 void hot_launch_s17_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 void hot_launch_s33_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);   // (orders 258 ... 513)
@@ -190,7 +212,8 @@ __host__ __device__ __forceinline__ bool slice_is_hot(int halo, int win, int bas
 // GS = 512 / D groups (73 ... 256: more than lanes), so the wave's rotated samples go through a 2 KB LDS array in stream
 // order and lane l sums and FINISHES the groups l, l + 64, l + 128, l + 192 per slice (consecutive lanes, consecutive
 // outputs: coalesced stores), the /8 kernel's per-slice finish instead of the parked one.
-template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW, bool DG = false, bool SD = false>
+// [L0, L0 + NL): the K steps the hot loop issues (the low plane is all zero outside; the high range lies inside)
+template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW, bool DG = false, bool SD = false, int L0 = 0, int NL = S>
 __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &b_kernarg) {
   // `b` serves the cold phase only. Left to itself the compiler loads the whole block at kernel entry and keeps it in
   // scalar registers ACROSS the hot loop — in the any-D forms that pushed the loop's own scalars into spill lanes (27 to
@@ -227,6 +250,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 
   const int DD = DG ? a.D : 8, GS = DG ? a.GS : 64;   // decimation, whole groups per slice
   static_assert(S >= 2 && S0 >= 0 && NH >= 1 && S0 + NH <= S, "high-plane range inside the K loop");
+  static_assert(L0 >= 0 && L0 + NL <= S && S0 >= L0 && S0 + NH <= L0 + NL, "high-plane range inside the low-plane range");
   static_assert(!REAL || NW == 4, "real input: 4-wave workgroups");
   static_assert(NW == 4 || NW == 8 || NW == 16, "4-wave virtual workgroups");
   constexpr int HALO = hot_halo(S, IN), WIN = hot_win(S, IN), PLB = hot_plb(S, IN), HALF = PLB / 2, BUFB = hot_bufb(S, IN);
@@ -441,17 +465,17 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   for (int s = 0; s < NRES; s++) AhRes[s] = taps_s[(S + s) * 64 + l];
   struct KOps { v4i uh, ul, Al, Ah; };
   auto stageK_begin = [&](const char *cb, KOps &o) __attribute__((always_inline)) {
-    const char *pl = cb + coff, *ph = cb + (CU8 ? 0 : PLB) + coff;
+    const char *pl = cb + coff + KSB * L0, *ph = cb + (CU8 ? 0 : PLB) + coff + KSB * L0;   // (the loop's first step: L0)
     o.uh = *reinterpret_cast<const v4i *>(ph); o.ul = o.uh;
     if (!CU8) o.ul = *reinterpret_cast<const v4i *>(pl);
-    if (K1_AREG) { o.Al = AlR[0]; o.Ah = AhR[0]; }
+    if (K1_AREG) { o.Al = AlR[L0]; o.Ah = AhR[0]; }
     else {
-      o.Al = taps_s[l]; o.Ah = o.Al;
-      if (S0 == 0) o.Ah = NRES > 0 ? AhRes[0] : taps_s[S * 64 + l];
+      o.Al = taps_s[L0 * 64 + l]; o.Ah = o.Al;
+      if (S0 == L0) o.Ah = NRES > 0 ? AhRes[0] : taps_s[S * 64 + l];
     }
   };
   auto stageK = [&](const char *cb, KOps &o, v16i &acc_hh, v16i &acc_mid, v16i &acc_ll) __attribute__((always_inline)) {
-    constexpr int SA = 0, SB = S;
+    constexpr int SA = L0, SB = L0 + NL;   // (the steps outside multiply all-zero tap fragments: not issued)
     const char *pl = cb + coff, *ph = cb + (CU8 ? 0 : PLB) + coff;
 #ifdef K1_ABL_NOKLOOP
     if (SA == 0) acc_mid[0] = o.uh.x ^ o.ul.x ^ o.Al.x ^ o.Ah.x;
@@ -464,7 +488,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       if (!REAL && s > SA) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o.uh), "+v"(o.ul) :: "memory");
 #endif
       KOps nx = o;
-      if (s + 1 < S) {
+      if (s + 1 < SB) {
 #ifdef K1_BSHIFT
         // (-DK1_BSHIFT) The sample-plane operand of step s + 1 IS the operand of step s one lane to the left inside each
         // half of the wave (lane (n, h) reads piece n + s of half h): the next operand comes by four DPP moves per plane
@@ -1538,9 +1562,9 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #define K1_MINWAVES 4
 #endif
 // One launch per call: the hot grid, then each virtual workgroup's share of the cold slices.
-template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW>
+template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW, int L0 = 0, int NL = S>
 __global__ __launch_bounds__(64 * NW, K1_MINWAVES) void iqbb_hot_kernel(const HotArgs a, const IqbbArgs b) {
-  iqbb_hot_body<S, S0, NH, ROT, EPI, IN, NW>(a, b);
+  iqbb_hot_body<S, S0, NH, ROT, EPI, IN, NW, false, false, L0, NL>(a, b);
 }
 template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW = 4>
 __global__ __launch_bounds__(64 * NW, K1_MINWAVES) void iqbb_hot_anyd_kernel(const HotArgs a, const IqbbArgs b) {
@@ -1589,21 +1613,21 @@ int hot_launch_sd_one(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha,
   return 0;
 }
 
-template <int S, int S0, int NH, int IN, int NW>
+template <int S, int S0, int NH, int IN, int NW, int L0 = 0, int NL = S>
 void hot_launch_one(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
   constexpr bool PAIR = hot_pair(IN, NW, false);
   const size_t lds = (size_t)hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, 0, PAIR), PAIR);
   if constexpr (IN != HOT_CS8) if (lds > 64 * 1024) {   // (the pair variant's four window buffers per wave; long filters)
     static std::atomic<uint64_t> attr_set{0};
     once_per_device(attr_set, [&] {
-#define SDRHIP_HOT_ATTR(R_, E_) SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+#define SDRHIP_HOT_ATTR(R_, E_) SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW, L0, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
     SDRHIP_HOT_ATTR(true, SDRHIP_EPI_FM); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_AM); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_USB); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_NONE);
     SDRHIP_HOT_ATTR(false, SDRHIP_EPI_FM); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_AM); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_USB); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_NONE);
 #undef SDRHIP_HOT_ATTR
     });
   }
   const dim3 grid(hl.grid, 1), block(64 * NW);
-#define SDRHIP_HOT(R_, E_) hipLaunchKernelGGL((iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW>), grid, block, lds, hl.stream, ha, b)
+#define SDRHIP_HOT(R_, E_) hipLaunchKernelGGL((iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW, L0, NL>), grid, block, lds, hl.stream, ha, b)
 #define SDRHIP_HOT_E(R_) do { switch (epi) { \
     case SDRHIP_EPI_FM: SDRHIP_HOT(R_, SDRHIP_EPI_FM); break; \
     case SDRHIP_EPI_AM: if constexpr (IN != HOT_CS8) SDRHIP_HOT(R_, SDRHIP_EPI_AM); break; \

@@ -3,7 +3,17 @@
 #include "iqbb_hot.hpp"
 
 namespace sdrhip {
-void hot_launch_s9_cs16(int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+// lo = 0: the low-plane range [1, 8) of hot_lo_ranges_9 — every high-plane range but the full one lies inside it (the host
+// never pairs it with that one); lo = 1: all 9 steps
+void hot_launch_s9_cs16(int range, int lo, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+  if (lo == 0 && range <= 2) {
+    switch (range) {
+      case 0: hot_launch_one<9, 3, 3, HOT_CS16, 4, 1, 7>(rot, epi, hl, ha, b); break;
+      case 1: hot_launch_one<9, 2, 5, HOT_CS16, 4, 1, 7>(rot, epi, hl, ha, b); break;
+      default: hot_launch_one<9, 1, 7, HOT_CS16, 4, 1, 7>(rot, epi, hl, ha, b); break;
+    }
+    return;
+  }
   switch (range) {
     case 0: hot_launch_one<9, 3, 3, HOT_CS16, 4>(rot, epi, hl, ha, b); break;
     case 1: hot_launch_one<9, 2, 5, HOT_CS16, 4>(rot, epi, hl, ha, b); break;

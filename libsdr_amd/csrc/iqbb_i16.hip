@@ -786,7 +786,7 @@ __global__ __launch_bounds__(256) void iqbb_bigd_finish_kernel(const BigdArgs a)
 
 namespace {
 // the hot kernels live in one translation unit per filter-length class (iqbb_hot_s*.hip)
-void launch_hot(int S, int in, int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+void launch_hot(int S, int in, int range, int lo, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
   if (in == HOT_REAL) { hot_launch_real(S, range, rot, epi, hl, ha, b); return; }
   if (in == HOT_CS8) { hot_launch_cs8(S, range, rot, epi, hl, ha, b); return; }
   const bool cu8 = in == HOT_CU8;
@@ -794,7 +794,7 @@ void launch_hot(int S, int in, int range, bool rot, int epi, const HotLaunch &hl
     case 2: hot_launch_s2(in, range, rot, epi, hl, ha, b); break;
     case 3: hot_launch_s3(in, range, rot, epi, hl, ha, b); break;
     case 5: hot_launch_s5(in, range, rot, epi, hl, ha, b); break;
-    case 9: if (cu8) hot_launch_s9_cu8(range, rot, epi, hl, ha, b); else hot_launch_s9_cs16(range, rot, epi, hl, ha, b); break;
+    case 9: if (cu8) hot_launch_s9_cu8(range, lo, rot, epi, hl, ha, b); else hot_launch_s9_cs16(range, lo, rot, epi, hl, ha, b); break;
     case 17: if (cu8) hot_launch_s17_cu8(range, rot, epi, hl, ha, b); else hot_launch_s17_cs16(range, rot, epi, hl, ha, b); break;
     default: if (cu8) hot_launch_s33_cu8(range, rot, epi, hl, ha, b); else hot_launch_s33_cs16(range, rot, epi, hl, ha, b); break;
   }
@@ -820,9 +820,12 @@ struct sdrhip_iqbb_i16 {
   int env_tpw = 0, env_wgpcu = 0;   // tuning hooks SDRHIP_IQBB_TPW / SDRHIP_IQBB_WGPCU, read once at create (0: not set)
   int env_fm_resident = -1;         // SDRHIP_IQBB_FM_RESIDENT=0|1: never / always complete the any-D forms' FM outputs inside the hot kernel (-1: by the channel count)
   int hot_range = -1;    // which compile-time high-plane K-step range of the hot kernel covers ah_mask (-1: none)
+  int lo_range = -1;     // ... and which low-plane range of its /8 form covers al_mask and the high range (-1: none; path 1)
+  bool env_trim = true;  // SDRHIP_IQBB_TRIM=0 (A/B, tests): the full low-plane range whatever the taps
   int in_cu8 = 0, real = 0, i8 = 0;   // input kinds: complex<uint8> with AutoCast, real int16 (BaseBand), complex<int8> (IQBaseBand<int8_t>)
   int path = 0, S = 0, cre = 0, cim = 0;   // path 1 = int8-MFMA formulation with S K-steps
   uint64_t ah_mask = 0;   // bit s: the high-byte tap fragments of K step s are not all zero (up to 33 steps)
+  uint64_t al_mask = 0;   // bit s: the low-byte tap fragments of K step s are not all zero
   DevBuf<v4i> tapfrag;
   DevBuf<v4i> tapfrag_hot;   // path 3: the any-D hot forms' fragments (rows permuted as path 1's)
   DevBuf<v4i> tapfrag_rot;   // paths 1 and 3: the hot forms' fragments for complex<uint8> input (bytes rotated inside every dword)
@@ -853,9 +856,9 @@ struct sdrhip_iqbb_i16 {
 
 
   // (re)loads the tap-dependent device data: packed taps (VALU kernel, the slow first-sample evaluation), the
-  // Toeplitz byte-plane fragments, their constant term and high-plane step mask (MFMA paths). create and retap.
+  // Toeplitz byte-plane fragments, their constant term and high- and low-plane step masks (MFMA paths). create and retap.
   void load_taps(const int32_t *taps) {
-    ah_mask = 0; hot_range = -1;
+    ah_mask = 0; al_mask = 0; hot_range = -1; lo_range = -1;
     // taps: zero-padded at the FRONT (older samples) so that the newest sample still meets K[order-1]
     std::vector<uint2> tp(OP, make_uint2(0, 0));
     const int pad = OP - order;
@@ -886,6 +889,7 @@ struct sdrhip_iqbb_i16 {
             const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
             frag[(((size_t)(2 * st) * 64 + l) * 16) + j] = (int8_t)ah;
             if (ah != 0) ah_mask |= (uint64_t)1 << st;
+            if (al != 0) al_mask |= (uint64_t)1 << st;
             frag[(((size_t)(2 * st + 1) * 64 + l) * 16) + j] = (int8_t)al;
           }
       {   // the hot kernel's compile-time high-plane range, as for path 1
@@ -928,6 +932,7 @@ struct sdrhip_iqbb_i16 {
               const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
               frag[(((size_t)(2 * st) * 64 + l) * 16) + j] = (int8_t)ah;
               if (ah != 0) ah_mask |= (uint64_t)1 << st;
+              if (al != 0) al_mask |= (uint64_t)1 << st;
               frag[(((size_t)(2 * st + 1) * 64 + l) * 16) + j] = (int8_t)al;
             }
       };
@@ -953,6 +958,17 @@ struct sdrhip_iqbb_i16 {
         const HotRange *rg = hot_ranges(S, &nr);
         for (int r = 0; r < nr && hot_range < 0; r++)
           if ((ah_mask & ~((((uint64_t)1 << rg[r].NH) - 1u) << rg[r].S0)) == 0) hot_range = r;
+        // (path 1: the /8 form's low-plane range [L0, L0+NL), the narrowest that covers al_mask and the high range; the last
+        // entry is every step. al_mask is read off the packed fragments themselves: the cu8 set only permutes bytes inside a dword)
+        if (path == 1 && hot_range >= 0) {
+          int nl = 0;
+          const HotLoRange *lr = hot_lo_ranges(S, &nl);
+          for (int r = 0; r < nl && lo_range < 0; r++) {
+            const bool covers = (al_mask & ~((((uint64_t)1 << lr[r].NL) - 1u) << lr[r].L0)) == 0;
+            const bool inside = rg[hot_range].S0 >= lr[r].L0 && rg[hot_range].S0 + rg[hot_range].NH <= lr[r].L0 + lr[r].NL;
+            if ((covers && inside && env_trim) || r == nl - 1) lo_range = r;
+          }
+        }
       }
       if (!tapfrag.p) tapfrag.alloc((size_t)S * 2 * 64);
       tapfrag.upload(reinterpret_cast<const v4i *>(frag.data()), (size_t)S * 2 * 64, ctx->stream);
@@ -1033,7 +1049,7 @@ struct sdrhip_iqbb_i16 {
     ha.dq = gx / ha.G; ha.dr = gx % ha.G;
     a.bt_hi = (int)t; a.tpw = 1;
     HotLaunch hl{(unsigned)grid, ctx->stream};
-    launch_hot(S, kind, hot_range, inc != 0, epi, hl, ha, a);
+    launch_hot(S, kind, hot_range, lo_range, inc != 0, epi, hl, ha, a);
     return true;
   }
 
@@ -1397,6 +1413,7 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       { const char *e = getenv("SDRHIP_IQBB_WGPCU"); if (e) h->env_wgpcu = std::max(1, atoi(e)); }
       { const char *e = getenv("SDRHIP_IQBB_FM_RESIDENT"); if (e) h->env_fm_resident = atoi(e) != 0; }
       { const char *e = getenv("SDRHIP_IQBB_FM_HANDSHAKE"); if (e) h->env_fm_handshake = atoi(e) != 0; }
+      { const char *e = getenv("SDRHIP_IQBB_TRIM"); if (e && e[0] == '0') h->env_trim = false; }   // A/B, tests: the full low-plane range
       const char *force = getenv("SDRHIP_IQBB_PATH");   // "valu": test hook (the VALU kernel for every plan)
       if (force && !strcmp(force, "valu")) mfma_ok = false;
       h->path = mfma_ok ? 1 : 0;
@@ -1534,12 +1551,18 @@ int sdrhip_iqbb_i16_path(sdrhip_iqbb_i16 *h, int *path) {
 int sdrhip_iqbb_i16_plan_info(sdrhip_iqbb_i16 *h, int *info, int n) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && info && n >= 8, SDRHIP_E_INVALID, "info must hold 8 ints");
+    int lcnt = 0;
+    const HotLoRange *lr = hot_lo_ranges(h->S, &lcnt);
     int cnt = 0;
     const HotRange *rg = hot_ranges(h->S, &cnt);
     const bool hot = h->hot_range >= 0 && h->hot_range < cnt;
     info[0] = h->path; info[1] = h->S; info[2] = hot ? rg[h->hot_range].S0 : 0; info[3] = hot ? rg[h->hot_range].NH : 0;
     info[4] = hot ? rg[h->hot_range].NW : 4; info[5] = h->hot_kind(); info[6] = h->OP; info[7] = h->HH;
     if (n >= 9) info[8] = h->last_multi_left;
+    if (n >= 11) {   // the /8 hot kernel's low-plane range (path 1; the other forms run every step: [0, S))
+      const bool lo = hot && h->lo_range >= 0 && h->lo_range < lcnt;
+      info[9] = lo ? lr[h->lo_range].L0 : 0; info[10] = lo ? lr[h->lo_range].NL : (hot ? h->S : 0);
+    }
   });
 }
 
