@@ -7,6 +7,8 @@
 //   sdr::gpu::FIRLowPass<complex<int16|float>>  <->  sdr::FIRLowPass<...>            src/firfilter.hh:117-289
 //   sdr::gpu::FMDemod<int16_t>, AMDemod<S>, USBDemod<S>  <->  same names             src/demod.hh:18-264
 //   sdr::gpu::SubSample<complex<...>>       <->  sdr::SubSample<...>                 src/subsample.hh:16-116
+//   sdr::gpu::FilterSink<float|double>      <->  sdr::FilterSink<Scalar>             src/filternode.hh:32-99
+//   sdr::gpu::FilterSource<float|double>    <->  sdr::FilterSource<Scalar>           src/filternode.hh:103-227
 //   sdr::gpu::FilterNode<float|double>      <->  sdr::FilterNode<Scalar>             src/filternode.hh:230-284
 //   sdr::gpu::FFT, FFTPlan<float|double>    <->  sdr::FFT, sdr::FFTPlan<...>        src/fftplan.hh, src/fftplan_fftw3.hh
 //   sdr::gpu::ChannelBank<int16_t>          many IQBaseBand(+demod) channels in ONE batched kernel launch;
@@ -800,6 +802,213 @@ template <> struct FftConvApi<double> {
 };
 }  // namespace detail
 
+// =================================================================================================
+// FilterSink<float|double> / FilterSource<float|double>: the split FFT filter with its spectrum stream in the open
+// =================================================================================================
+template <class Scalar> class FilterSource;
+
+namespace detail {
+template <class Scalar> struct SplitTag;
+template <> struct SplitTag<float> { enum { dtype = SDRHIP_T_CF32 }; };
+template <> struct SplitTag<double> { enum { dtype = SDRHIP_T_CF64 }; };
+/** The direct hand-off of a spectrum between a gpu::FilterSink and its gpu::FilterSources: just before a direct send the
+ * sink records {host buffer data -> device spectrum, device}; the host buffer stays unfilled, and a source that receives
+ * that very buffer reads the device copy. Direct delivery is synchronous, so the sink erases the entry after send. */
+struct SpectrumHandoff { const void *dev; int device; };
+inline std::map<const void *, SpectrumHandoff> &spectrumHandoffs() {
+  static std::map<const void *, SpectrumHandoff> table;
+  return table;
+}
+inline void *deviceAlloc(sdrhip_ctx *c, size_t bytes, const char *what) {
+  void *p = 0;
+  configCheck(sdrhip_malloc(c, bytes, &p), what);
+  return p;
+}
+}  // namespace detail
+
+/** Drop-in for sdr::FilterSink<Scalar>, Scalar = float or double (reference src/filternode.hh:32-99): every buffer of
+ * block_size samples becomes one 2 x block_size-point spectrum (zero-padded block, forward DFT, natural order), sent as
+ * complex<Scalar>. The config it propagates says bufferSize = block_size, as the reference's does (:76-77), although its
+ * buffers hold 2 x block_size points. When every connected sink is connected DIRECT and is a gpu::FilterSource<Scalar> on
+ * the same device, the spectrum stays on the device (no copy per block) and the buffer sent is left unfilled; otherwise it
+ * is copied into the buffer. */
+template <class Scalar>
+class FilterSink : public Sink< std::complex<Scalar> >, public Source {
+public:
+  typedef std::complex<Scalar> CScalar;
+  FilterSink(size_t block_size, int device = 0)
+    : _block(block_size), _device(device), _plan(0), _in(0), _spec(0), _out(2 * block_size), _onDevice(false) {}
+  virtual ~FilterSink() { _release(); _out.unref(); }
+
+  virtual void config(const Config &src_cfg) {
+    if ((Config::Type_UNDEFINED == src_cfg.type()) || (0 == src_cfg.sampleRate()) || (0 == src_cfg.bufferSize())) return;
+    if (Config::typeId<CScalar>() != src_cfg.type()) {
+      ConfigError err;
+      err << "Can not configure filter-sink: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<CScalar>();
+      throw err;
+    }
+    if (_block != src_cfg.bufferSize()) {
+      ConfigError err;
+      err << "Can not configure filter-sink: Invalid buffer size " << src_cfg.bufferSize() << ", expected " << _block;
+      throw err;
+    }
+    if (!_plan) {
+      sdrhip_ctx *c = Device::get(_device);
+      detail::configCheck(sdrhip_fftsink_create(c, detail::SplitTag<Scalar>::dtype, int(_block), 1, 1, &_plan), "gpu::FilterSink");
+      _in = detail::deviceAlloc(c, _block * sizeof(CScalar), "gpu::FilterSink");
+      _spec = detail::deviceAlloc(c, 2 * _block * sizeof(CScalar), "gpu::FilterSink");
+    }
+    setConfig(Config(Config::typeId<CScalar>(), src_cfg.sampleRate(), src_cfg.bufferSize(), src_cfg.numBuffers()));
+  }
+
+  virtual void process(const Buffer<CScalar> &buffer, bool) {
+    if (!_plan || buffer.size() != _block) return;
+    _onDevice = _deviceHandoff();
+    if (!_onDevice) {
+      // the repo's drop rule: a buffer still referenced downstream is not overwritten
+      if (!_out.isUnused()) return;
+      if (!detail::processOk(sdrhip_fftsink_process(_plan, buffer.data(), _block, 0, _out.data(), 0), "gpu::FilterSink")) return;
+      send(_out);
+      return;
+    }
+    sdrhip_ctx *c = Device::get(_device);
+    if (!detail::processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), _block * sizeof(CScalar)), "gpu::FilterSink") ||
+        !detail::processOk(sdrhip_fftsink_process_dev(_plan, _in, _block, 0, _spec, 0), "gpu::FilterSink")) return;
+    const detail::SpectrumHandoff rec = {_spec, _device};
+    detail::spectrumHandoffs()[_out.data()] = rec;
+    send(_out);
+    detail::spectrumHandoffs().erase(_out.data());
+  }
+
+  /** true: the last block's spectrum went to the sources on the device (no host copy). */
+  bool lastBlockOnDevice() const { return _onDevice; }
+  size_t blockSize() const { return _block; }
+  int device() const { return _device; }
+
+protected:
+  bool _deviceHandoff() const;
+  void _release() {
+    if (_plan) { sdrhip_fftsink_destroy(_plan); _plan = 0; }
+    if (_in) { sdrhip_free(Device::get(_device), _in); _in = 0; }
+    if (_spec) { sdrhip_free(Device::get(_device), _spec); _spec = 0; }
+  }
+  size_t _block;
+  int _device;
+  sdrhip_fftsink *_plan;
+  void *_in, *_spec;
+  Buffer<CScalar> _out;
+  bool _onDevice;
+};
+
+/** Drop-in for sdr::FilterSource<Scalar>, Scalar = float or double (reference src/filternode.hh:103-227): a Sink of the
+ * 2 x block_size-point spectra FilterSink sends, a Source of block_size filtered samples. Per block: spectrum x kernel,
+ * inverse DFT, / 2N, and the upper half of the last block's result added (overlap-add, the tail carried on the device).
+ * The kernel is sinc_flt_kernel + _updateFilter's spectrum (:18-28,186-203), made at config and by setFreq, which applies it
+ * from the next block and keeps the tail: the block after it is the OLD kernel's tail plus the NEW kernel's head, exactly
+ * as the reference's. A block whose output buffer is still referenced downstream is dropped; the kernel still runs, so
+ * that the tail stays aligned with the input. */
+template <class Scalar>
+class FilterSource : public Sink< std::complex<Scalar> >, public Source {
+public:
+  typedef std::complex<Scalar> CScalar;
+  FilterSource(size_t block_size, double fmin, double fmax, int device = 0)
+    : _block(block_size), _fmin(fmin), _fmax(fmax), _device(device), _Fs(0), _plan(0), _spec(0), _outDev(0),
+      _onDevice(false), _inert(false) {}
+  virtual ~FilterSource() {
+    if (_plan) sdrhip_fftsource_destroy(_plan);
+    if (_spec) sdrhip_free(Device::get(_device), _spec);
+    if (_outDev) sdrhip_free(Device::get(_device), _outDev);
+    _buffer.unref();
+  }
+
+  /** FilterSource::setFreq (:128-130): the kernel is recomputed (once configured) and applies from the next block. */
+  virtual void setFreq(double fmin, double fmax) {
+    _fmin = fmin; _fmax = fmax;
+    if (_plan) {
+      std::vector<Scalar> K(4 * _block);
+      _kernel(K.data());
+      detail::configCheck(sdrhip_fftsource_set_kernel(_plan, K.data()), "FilterSource");
+    }
+  }
+  virtual double fmin() const { return _fmin; }
+  virtual double fmax() const { return _fmax; }
+  /** true: the last block's spectrum came from a gpu::FilterSink on the device (no upload). */
+  bool lastBlockOnDevice() const { return _onDevice; }
+  int device() const { return _device; }
+
+  virtual void config(const Config &src_cfg) {
+    if (_inert) return;
+    if ((0 == src_cfg.sampleRate()) || (0 == src_cfg.bufferSize())) return;
+    if (_block != src_cfg.bufferSize()) {
+      ConfigError err;
+      err << "Can not configure FilterSource, block-size (=" << _block << ") != buffer-size (=" << src_cfg.bufferSize() << ")!";
+      throw err;
+    }
+    _Fs = src_cfg.sampleRate();
+    std::vector<Scalar> K(4 * _block);
+    _kernel(K.data());
+    if (!_plan) {
+      sdrhip_ctx *c = Device::get(_device);
+      detail::configCheck(sdrhip_fftsource_create(c, detail::SplitTag<Scalar>::dtype, int(_block), K.data(), 1, 1, &_plan),
+                          "FilterSource");
+      _spec = detail::deviceAlloc(c, 2 * _block * sizeof(CScalar), "FilterSource");
+      _outDev = detail::deviceAlloc(c, _block * sizeof(CScalar), "FilterSource");
+      _buffer = Buffer<CScalar>(_block);
+      _scratch.resize(_block);
+    } else {
+      detail::configCheck(sdrhip_fftsource_set_kernel(_plan, K.data()), "FilterSource");
+    }
+    Source::setConfig(Config(Config::typeId<CScalar>(), src_cfg.sampleRate(), _block, src_cfg.numBuffers()));
+  }
+
+  virtual void process(const Buffer<CScalar> &buffer, bool) {
+    if (_inert || !_plan || buffer.size() < 2 * _block) return;
+    sdrhip_ctx *c = Device::get(_device);
+    const bool keep = _buffer.isUnused();
+    const std::map<const void *, detail::SpectrumHandoff> &t = detail::spectrumHandoffs();
+    const std::map<const void *, detail::SpectrumHandoff>::const_iterator it = t.find(buffer.data());
+    _onDevice = it != t.end() && it->second.device == _device;
+    const void *spec = _onDevice ? it->second.dev : _spec;
+    if (!_onDevice && !detail::processOk(sdrhip_memcpy_h2d(c, _spec, buffer.data(), 2 * _block * sizeof(CScalar)), "FilterSource"))
+      return;
+    if (!detail::processOk(sdrhip_fftsource_process_dev(_plan, spec, 1, 0, _outDev, 0), "FilterSource")) return;
+    CScalar *dst = keep ? reinterpret_cast<CScalar *>(_buffer.data()) : _scratch.data();
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, dst, _outDev, _block * sizeof(CScalar)), "FilterSource") || !keep) return;
+    send(_buffer);
+  }
+
+protected:
+  /** Band of gpu::FilterNode: no device state, its sink side does nothing (the bank runs it). */
+  struct Inert {};
+  FilterSource(Inert, size_t block_size, double fmin, double fmax, int device)
+    : _block(block_size), _fmin(fmin), _fmax(fmax), _device(device), _Fs(0), _plan(0), _spec(0), _outDev(0),
+      _onDevice(false), _inert(true) {}
+  void _kernel(Scalar *K) const {   // sinc_flt_kernel + FilterSource::_updateFilter (:18-28,186-203)
+    std::vector<Scalar> h(2 * _block);
+    design::fftFilterKernel(int(_block), _fmin, _fmax, _Fs, h.data());
+    design::fftFilterSpectrum(int(_block), h.data(), K);
+  }
+  size_t _block;
+  double _fmin, _fmax;
+  int _device;
+  double _Fs;
+  sdrhip_fftsource *_plan;
+  void *_spec, *_outDev;
+  bool _onDevice, _inert;
+  Buffer<CScalar> _buffer;
+  std::vector<CScalar> _scratch;
+};
+
+template <class Scalar>
+bool FilterSink<Scalar>::_deviceHandoff() const {
+  if (_sinks.empty()) return false;
+  for (std::map<SinkBase *, bool>::const_iterator it = _sinks.begin(); it != _sinks.end(); ++it) {
+    const gpu::FilterSource<Scalar> *s = dynamic_cast<const gpu::FilterSource<Scalar> *>(it->first);
+    if (!it->second || !s || s->device() != _device) return false;
+  }
+  return true;
+}
+
 /** Drop-in for sdr::FilterNode<Scalar>, Scalar = float or double (reference src/filternode.hh:230-284), ANY block size
  * (:235: `FilterNode(size_t block_size=1024)`; FFTW plans any 2 x block_size): one launch per buffer where the transform
  * fits a workgroup's LDS and is made of the factors 2 ... 13, passes over device memory around a four-step / chirp
@@ -808,26 +1017,23 @@ template <class Scalar>
 class FilterNode {
 public:
   typedef std::complex<Scalar> CScalar;
-  /** One band of the bank: a Source of complex<float> buffers (role of FilterSource, src/filternode.hh:105-227). */
-  class Band : public Source {
+  /** One band of the bank: a gpu::FilterSource<Scalar> (src/filternode.hh:105-227) whose sink side is inert — the bank
+   * runs it — so that `gpu::FilterSource<Scalar> *s = bank.addFilter(a, b)` works as with the reference's FilterNode. */
+  class Band : public gpu::FilterSource<Scalar> {
   public:
-    Band(FilterNode *p, size_t index, double fmin, double fmax) : _p(p), _index(index), _fmin(fmin), _fmax(fmax) {}
-    virtual ~Band() { _buffer.unref(); }
+    Band(FilterNode *p, size_t index, double fmin, double fmax)
+      : gpu::FilterSource<Scalar>(typename gpu::FilterSource<Scalar>::Inert(), p->_block, fmin, fmax, p->_device), _p(p), _index(index) {}
     /** FilterSource::setFreq (:132-139): only this band's kernel is recomputed; the overlap history goes on. */
-    void setFreq(double fmin, double fmax) {
+    virtual void setFreq(double fmin, double fmax) {
       if (fmax < fmin) std::swap(fmin, fmax);
-      _fmin = fmin; _fmax = fmax;
+      this->_fmin = fmin; this->_fmax = fmax;
       _p->_bandChanged(_index);
     }
-    double fmin() const { return _fmin; }
-    double fmax() const { return _fmax; }
 
   protected:
     friend class FilterNode;
     FilterNode *_p;
     size_t _index;
-    double _fmin, _fmax;
-    Buffer<CScalar> _buffer;
   };
 
   explicit FilterNode(size_t block_size = 1024, int device = 0) : _block(block_size), _device(device), _plan(0), _sink(this) {}

@@ -424,6 +424,44 @@ int sdrhip_fft_plan_exec_dev(sdrhip_fft_plan *p, int sign, int batch, const void
 int sdrhip_fft_plan_exec(sdrhip_fft_plan *p, int sign, const void *in_host, void *out_host);
 int sdrhip_fft_plan_destroy(sdrhip_fft_plan *p);
 
+/* ---- FilterSink / FilterSource as separate stages (src/filternode.hh:32-99,103-227) --------- */
+/* The reference's split FFT filter with its spectrum stream in the open. dtype = SDRHIP_T_CF32 or SDRHIP_T_CF64 (FilterSink /
+ * FilterSource<Scalar>, :30-32,102-104); `void *` buffers hold complex<float> resp. complex<double>. Block size N >= 1, any value
+ * (FFTW plans any 2N, src/fftplan_fftw3.hh:34-36). `max_blocks`: blocks per channel and call at most; `channels` rows per call.
+ *
+ * FilterSink (:81-88): every N input samples become one SPECTRUM of 2N points — the block zero-padded to 2N, forward DFT,
+ * unnormalised, FFTW sign (X[k] = sum_n x[n] exp(-2 pi i k n / 2N)), NATURAL frequency order. n_in must be a whole number of
+ * blocks (any other value: SDRHIP_E_INVALID, nothing is launched); channel c's row of `spec` receives n_in / N spectra back to
+ * back. Strides in elements, 0 = packed. */
+typedef struct sdrhip_fftsink sdrhip_fftsink;
+int sdrhip_fftsink_create(sdrhip_ctx *ctx, int dtype, int N, int channels, size_t max_blocks, sdrhip_fftsink **out);
+int sdrhip_fftsink_process(sdrhip_fftsink *h, const void *in_host, size_t n_in, size_t in_stride, void *spec_host,
+                           size_t spec_stride);
+int sdrhip_fftsink_process_dev(sdrhip_fftsink *h, const void *in_dev, size_t n_in, size_t in_stride, void *spec_dev,
+                               size_t spec_stride);
+/* the path the plan took: "fused" (complex<float>, 2N a power of two in [2048, 16384]: one tuned kernel per call) or
+ * "composed" (every other size and complex<double>: gather/pad, the planned transform of sdrhip_fft_plan_*, row copy) */
+int sdrhip_fftsink_form(sdrhip_fftsink *h, const char **name);
+int sdrhip_fftsink_destroy(sdrhip_fftsink *h);
+/* FilterSource (:164-181): a sink of such spectra. Per block: Y = IDFT(spec x K) / 2N, out[0:N] = tail + Y[0:N], tail = Y[N:2N]
+ * — overlap-ADD, the tail (_last_trafo, :117-120) carried from block to block and from call to call, zero at create and after
+ * reset. kernel_spectrum: 2N points, natural order, normalised as _updateFilter leaves _kern (:186-203; the designers
+ * sdrhip_design_fftfilt_spectrum[_f64]). set_kernel (FilterSource::setFreq, :128-130) applies from the next block and keeps the
+ * tail: the block after the swap is the OLD kernel's tail plus the NEW kernel's head, exactly as the reference (the fused bank,
+ * sdrhip_fftconv_set_kernel, has a different one-block transient); it synchronises the context's stream. process: n_blocks
+ * spectra per channel (row stride spec_stride >= 2N n_blocks) to n_blocks x N samples (out_stride >= N n_blocks); 0 = packed. */
+typedef struct sdrhip_fftsource sdrhip_fftsource;
+int sdrhip_fftsource_create(sdrhip_ctx *ctx, int dtype, int N, const void *kernel_spectrum, int channels, size_t max_blocks,
+                            sdrhip_fftsource **out);
+int sdrhip_fftsource_set_kernel(sdrhip_fftsource *h, const void *kernel_spectrum);
+int sdrhip_fftsource_process(sdrhip_fftsource *h, const void *spec_host, size_t n_blocks, size_t spec_stride, void *out_host,
+                             size_t out_stride);
+int sdrhip_fftsource_process_dev(sdrhip_fftsource *h, const void *spec_dev, size_t n_blocks, size_t spec_stride, void *out_dev,
+                                 size_t out_stride);
+int sdrhip_fftsource_form(sdrhip_fftsource *h, const char **name);   /* as sdrhip_fftsink_form */
+int sdrhip_fftsource_reset(sdrhip_fftsource *h);                      /* tails zeroed */
+int sdrhip_fftsource_destroy(sdrhip_fftsource *h);
+
 /* ---- float baseband (BASELINE config 2; build-defined) ---------------------- */
 /* y = SubSample_D( FIR_cf32( x[n] * exp(-2*pi*i*Fc*n/Fs) ) ); the reference has no float
  * baseband (IQBaseBand<float> does not compile, FreqShift<float> is wrong: SURVEY fact 6). */

@@ -154,6 +154,18 @@ def lib():
             "sdrhip_fft_plan_exec_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
             "sdrhip_fft_plan_exec": (C.c_int, [vp, C.c_int, vp, vp]),
             "sdrhip_fft_plan_destroy": (C.c_int, [vp]),
+            "sdrhip_fftsink_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, sz, pvp]),
+            "sdrhip_fftsink_process": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_fftsink_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_fftsink_form": (C.c_int, [vp, C.POINTER(C.c_char_p)]),
+            "sdrhip_fftsink_destroy": (C.c_int, [vp]),
+            "sdrhip_fftsource_create": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, sz, pvp]),
+            "sdrhip_fftsource_set_kernel": (C.c_int, [vp, vp]),
+            "sdrhip_fftsource_process": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_fftsource_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_fftsource_form": (C.c_int, [vp, C.POINTER(C.c_char_p)]),
+            "sdrhip_fftsource_reset": (C.c_int, [vp]),
+            "sdrhip_fftsource_destroy": (C.c_int, [vp]),
             "sdrhip_comm_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, pvp]),
             "sdrhip_comm_size": (C.c_int, [vp, C.POINTER(C.c_int)]),
             "sdrhip_comm_ctx": (C.c_int, [vp, C.c_int, pvp]),

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (EPI_NONE, EPI_FM, EPI_AM, EPI_USB, FIR_CS16_EXACT, FIR_CF32, T_CS16, T_CF32,
+from .abi import (EPI_NONE, EPI_FM, EPI_AM, EPI_USB, FIR_CS16_EXACT, FIR_CF32, T_CS16, T_CF32, T_CF64,
                   FFTCONV_OLA, FFTCONV_OLS, check)
 
 
@@ -595,6 +595,80 @@ class FFTConv(_Node):
     def reset(self):
         check(abi.lib().sdrhip_fftconv_reset(self._h))
 
+
+
+def _split_dtype(dtype):
+    dt = np.dtype(dtype)
+    assert dt in (np.float32, np.float64), dt
+    return dt, (T_CF64 if dt == np.float64 else T_CF32)
+
+
+class FFTSink(_Node):
+    """FilterSink<Scalar> (sdrhip_fftsink_*): every N samples -> one 2N-point spectrum (zero-padded block, forward DFT,
+    natural order). process(x[channels, n_in, 2]) -> [channels, n_in / N, 2N, 2]; n_in must be a multiple of N."""
+    _destroy = "sdrhip_fftsink_destroy"
+
+    def __init__(self, ctx, N, channels=1, max_blocks=64, dtype=np.float32):
+        super().__init__()
+        self.dtype, dt = _split_dtype(dtype)
+        self.ctx, self.N, self.channels = ctx, N, channels
+        check(abi.lib().sdrhip_fftsink_create(ctx.handle, dt, N, channels, max_blocks, C.byref(self._h)))
+
+    @property
+    def form(self):
+        s = C.c_char_p()
+        check(abi.lib().sdrhip_fftsink_form(self._h, C.byref(s)))
+        return s.value.decode()
+
+    def process(self, x):
+        x = _as3(x, self.dtype)
+        n = x.shape[1]
+        out = np.zeros((x.shape[0], n // self.N, 2 * self.N, 2), self.dtype)
+        check(abi.lib().sdrhip_fftsink_process(self._h, _ptr(x), n, n, _ptr(out), out.shape[1] * 2 * self.N))
+        return out
+
+    def process_dev(self, in_ptr, n_in, in_stride, spec_ptr, spec_stride):
+        check(abi.lib().sdrhip_fftsink_process_dev(self._h, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(spec_ptr), spec_stride))
+
+
+class FFTSource(_Node):
+    """FilterSource<Scalar> (sdrhip_fftsource_*): spectra [channels, blocks, 2N, 2] -> overlap-added output
+    [channels, blocks * N, 2]; the tail is carried across calls. `spectrum`: the 2N-point kernel spectrum (natural order,
+    normalised: design_fftfilt_spectrum)."""
+    _destroy = "sdrhip_fftsource_destroy"
+
+    def __init__(self, ctx, N, spectrum, channels=1, max_blocks=64, dtype=np.float32):
+        super().__init__()
+        self.dtype, dt = _split_dtype(dtype)
+        self.ctx, self.N, self.channels = ctx, N, channels
+        k = np.ascontiguousarray(spectrum, self.dtype)
+        check(abi.lib().sdrhip_fftsource_create(ctx.handle, dt, N, _ptr(k), channels, max_blocks, C.byref(self._h)))
+
+    @property
+    def form(self):
+        s = C.c_char_p()
+        check(abi.lib().sdrhip_fftsource_form(self._h, C.byref(s)))
+        return s.value.decode()
+
+    def process(self, spec):
+        spec = np.ascontiguousarray(spec, self.dtype)
+        if spec.ndim == 3:
+            spec = spec[None]
+        c, nb = spec.shape[0], spec.shape[1]
+        out = np.zeros((c, nb * self.N, 2), self.dtype)
+        check(abi.lib().sdrhip_fftsource_process(self._h, _ptr(spec), nb, nb * 2 * self.N, _ptr(out), nb * self.N))
+        return out
+
+    def process_dev(self, spec_ptr, n_blocks, spec_stride, out_ptr, out_stride):
+        check(abi.lib().sdrhip_fftsource_process_dev(self._h, C.c_void_p(spec_ptr), n_blocks, spec_stride, C.c_void_p(out_ptr),
+                                                     out_stride))
+
+    def set_kernel(self, spectrum):
+        k = np.ascontiguousarray(spectrum, self.dtype)
+        check(abi.lib().sdrhip_fftsource_set_kernel(self._h, _ptr(k)))
+
+    def reset(self):
+        check(abi.lib().sdrhip_fftsource_reset(self._h))
 
 class FloatBaseBand(_Node):
     """Build-defined float baseband (BASELINE config 2): shift -> FIR(cf32) -> /D."""
