@@ -35,11 +35,18 @@
 //   D = 2 ... 7       iqbb_hot_sd_kernel    SD: 73 ... 256 groups per slice out of an LDS array, finished per slice
 //   D = 257 ... 32768 iqbb_hot_anyd_kernel  PART: slices of 512 samples whatever the groups; a slice leaves the sums of its
 //                                           stretches between group boundaries, one lane per group finishes (same choice)
+//
+// Host side: the tables below are the one source of the compiled classes — (form, S, input kind) in hot_class, the K-step
+// ranges of each S in hot_ranges_* / hot_lo_ranges_9. HotClass<form, S, in>::launch turns a run-time range into template
+// arguments by walking them, hot_launch_form launches one form, each iqbb_hot_*.hip unit explicitly instantiates its
+// classes, and hot_launch (iqbb_i16.hip) picks a class at run time. hot_sd_waves answers the small-D form's workgroup size.
 #pragma once
 #include <atomic>
 #include "iqbb_common.hpp"
 
+#include <iterator>
 #include <type_traits>
+#include <utility>
 
 namespace sdrhip {
 
@@ -110,61 +117,80 @@ constexpr HotRange hot_ranges_33[] = {{12, 9, 8}, {16, 9, 8}, {18, 9, 8}, {8, 17
 // the 129-tap window (at 100 or 129 taps, or 100 kHz wide, an edge step is live). Other classes: the full range only.
 struct HotLoRange { int L0, NL; };
 constexpr HotLoRange hot_lo_ranges_9[] = {{1, 7}, {0, 9}};
-inline const HotLoRange *hot_lo_ranges(int S, int *count) {
-  static const HotLoRange full[] = {{0, 2}, {0, 3}, {0, 5}, {0, 17}, {0, 33}};
-  switch (S) {
-    case 9: *count = 2; return hot_lo_ranges_9;
-    case 2: *count = 1; return full;
-    case 3: *count = 1; return full + 1;
-    case 5: *count = 1; return full + 2;
-    case 17: *count = 1; return full + 3;
-    case 33: *count = 1; return full + 4;
-    default: *count = 0; return nullptr;
-  }
+template <int S> constexpr HotLoRange hot_lo_full[] = {{0, S}};
+
+// The tables by S, at compile time (the kernels' template arguments) and at run time (the host's picks, plan_info).
+// Adding a range or a class is an edit here and, for a new class, one explicit instantiation (iqbb_hot_*.hip).
+constexpr int hot_steps[] = {2, 3, 5, 9, 17, 33};
+template <int S> constexpr auto &hot_ranges_of() {
+  if constexpr (S == 2) return hot_ranges_2;
+  else if constexpr (S == 3) return hot_ranges_3;
+  else if constexpr (S == 5) return hot_ranges_5;
+  else if constexpr (S == 9) return hot_ranges_9;
+  else if constexpr (S == 17) return hot_ranges_17;
+  else return hot_ranges_33;
+}
+template <int S> constexpr auto &hot_lo_ranges_of() {
+  if constexpr (S == 9) return hot_lo_ranges_9;
+  else return hot_lo_full<S>;
+}
+// calls f(std::integral_constant<int, i>) for a run-time index i in [0, N); any other value picks the last one
+template <int N, class F, int... I>
+void hot_pick(int i, F &&f, std::integer_sequence<int, I...>) {
+  if (i < 0 || i >= N) i = N - 1;
+  ((i == I ? f(std::integral_constant<int, I>{}) : void()), ...);
+}
+template <int N, class F> void hot_pick(int i, F &&f) { hot_pick<N>(i, f, std::make_integer_sequence<int, N>{}); }
+// calls f(std::integral_constant<int, S>) if S is one of hot_steps; false: it is not
+template <class F> bool hot_with_steps(int S, F &&f) {
+  constexpr int N = (int)std::size(hot_steps);
+  for (int i = 0; i < N; i++)
+    if (hot_steps[i] == S) { hot_pick<N>(i, [&](auto k) { f(std::integral_constant<int, hot_steps[decltype(k)::value]>{}); }); return true; }
+  return false;
 }
 inline const HotRange *hot_ranges(int S, int *count) {
-  switch (S) {
-    case 2: *count = 1; return hot_ranges_2;
-    case 3: *count = 2; return hot_ranges_3;
-    case 5: *count = 2; return hot_ranges_5;
-    case 9: *count = 4; return hot_ranges_9;
-    case 17: *count = 3; return hot_ranges_17;
-    case 33: *count = 5; return hot_ranges_33;
-    default: *count = 0; return nullptr;
-  }
+  const HotRange *r = nullptr;
+  *count = 0;
+  hot_with_steps(S, [&](auto s) { r = hot_ranges_of<s>(); *count = (int)std::size(hot_ranges_of<s>()); });
+  return r;
+}
+inline const HotLoRange *hot_lo_ranges(int S, int *count) {
+  const HotLoRange *r = nullptr;
+  *count = 0;
+  hot_with_steps(S, [&](auto s) { r = hot_lo_ranges_of<s>(); *count = (int)std::size(hot_lo_ranges_of<s>()); });
+  return r;
+}
+
+// Forms of the hot kernel, and the classes (form, S, input kind) that are compiled: one explicit instantiation of HotClass
+// each, in the iqbb_hot_*.hip units. /8 and any-D: every S for complex<int16> and complex<uint8>, S = 2, 3, 5, 9 for
+// complex<int8>; small-D: S up to 17, none for complex<int8>; real input: S = 3, 5, 9 in every form.
+enum { HOT_D8 = 0, HOT_ANYD = 1, HOT_SD = 2 };   // iqbb_hot_kernel, iqbb_hot_anyd_kernel, iqbb_hot_sd_kernel
+constexpr bool hot_class(int form, int S, int in) {
+  if (in == HOT_REAL) return S == 3 || S == 5 || S == 9;
+  if (in == HOT_CS8) return form != HOT_SD && (S == 2 || S == 3 || S == 5 || S == 9);
+  return S == 2 || S == 3 || S == 5 || S == 9 || S == 17 || (S == 33 && form != HOT_SD);
+}
+// the small-D form's workgroup for a class's range (hot_sd_nw from the table's NW; real input: 4-wave workgroups only —
+// a plan whose arrays need a larger one runs the VALU kernel); 0: none fits (the general kernel runs the plan)
+constexpr int hot_sd_range_waves(int S, const HotRange &r, int in, bool rot) {
+  const int nw = hot_sd_nw(S, r.NH, in, rot, r.NW);
+  return in != HOT_REAL || nw == 4 ? nw : 0;
+}
+inline int hot_sd_waves(int S, int in, int range, bool rot) {
+  int n = 0;
+  const HotRange *rg = hot_ranges(S, &n);
+  if (!hot_class(HOT_SD, S, in)) return 0;
+  return hot_sd_range_waves(S, rg[range >= 0 && range < n ? range : n - 1], in, rot);
 }
 
 struct HotLaunch { unsigned grid; hipStream_t stream; };
-// one function per translation unit (iqbb_hot_s*.hip): `range` indexes hot_ranges(S)
-void hot_launch_s2(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s3(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s5(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-// (9 steps: `lo` indexes hot_lo_ranges(9))
-void hot_launch_s9_cs16(int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s9_cu8(int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s17_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s17_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_s33_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);   // (orders 258 ... 513)
-void hot_launch_s33_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_anyd33_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_anyd33_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_cs8(int S, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);        // complex<int8>: S = 2, 3, 5 or 9; no demodulator or FM
-void hot_launch_anyd_cs8(int S, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_real(int S, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);   // S = 3, 5 or 9
-// real input at any other decimation: the any-D form (9 ... 512) and the small-decimation form (1 ... 7; 0: its LDS does not fit)
-void hot_launch_real_anyd(int S, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_real_anyd9(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-int hot_launch_real_sd(int S, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);
-int hot_launch_real_sd9(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);
-void hot_launch_anyd(int S, int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);   // S = 2, 3, 5, 9 or 17, cs16 / cu8
-void hot_launch_anyd9(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-void hot_launch_anyd17_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);   // (orders 130 ... 257: 8- and 16-wave workgroups, as the /8 kernel's)
-void hot_launch_anyd17_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
-// decimations 2 ... 7 (S = 2, 3, 5, 9 or 17, cs16 / cu8): returns the waves per workgroup the plan runs in — 0: its LDS fits none (the general kernel runs it)
-int hot_launch_sd(int S, int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);   // (returns the waves per workgroup, 0: no form fits)
-int hot_launch_sd9(int in, int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);
-int hot_launch_sd17_cs16(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);
-int hot_launch_sd17_cu8(int range, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &, bool dry_run);
+// one launch of a class's kernel: `range` indexes hot_ranges_of<S>, `lo` (the /8 form, complex<int16> / complex<uint8>)
+// hot_lo_ranges_of<S> — a pair whose high-plane range is not inside the low-plane one runs over every step
+template <int FORM, int S, int IN> struct HotClass {
+  static void launch(int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
+};
+// the run-time entry point (iqbb_i16.hip): the class of (form, S, in); an error where none is compiled
+void hot_launch(int form, int S, int in, int range, int lo, bool rot, int epi, const HotLaunch &, const HotArgs &, const IqbbArgs &);
 
 }  // namespace sdrhip
 
@@ -1589,81 +1615,88 @@ inline void once_per_device(std::atomic<uint64_t> &mask, F &&set_attributes) {
   mask.fetch_or(bit, std::memory_order_release);
 }
 
-// returns the waves per workgroup the plan runs in (hot_sd_nw; the host sizes the grid by it) — 0: its LDS fits none (nothing
-// launched); dry_run: only answer
-template <int S, int S0, int NH, int IN, int NW0 = 4>
-int hot_launch_sd_one(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b, bool dry_run) {
-  const dim3 grid(hl.grid, 1);
-#define SDRHIP_SD(R_, E_) hipLaunchKernelGGL((iqbb_hot_sd_kernel<S, S0, NH, R_, E_, IN, NWX>), grid, dim3(64 * NWX), lds, hl.stream, ha, b)
-#define SDRHIP_SD_ATTR(R_, E_) SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&iqbb_hot_sd_kernel<S, S0, NH, R_, E_, IN, NWX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-#define SDRHIP_SD_E(R_) do { if (dry_run) return NWX; \
-    const size_t lds = (size_t)hot_lds_bytes(S, NH, IN, NWX, false) + hot_sd_extra(S, IN, R_, NWX); \
-    if (lds > 64 * 1024) { static std::atomic<uint64_t> attr_set{0}; once_per_device(attr_set, [&] { SDRHIP_SD_ATTR(R_, SDRHIP_EPI_FM); SDRHIP_SD_ATTR(R_, SDRHIP_EPI_AM); SDRHIP_SD_ATTR(R_, SDRHIP_EPI_USB); SDRHIP_SD_ATTR(R_, SDRHIP_EPI_NONE); }); } \
-    switch (epi) { \
-    case SDRHIP_EPI_FM: SDRHIP_SD(R_, SDRHIP_EPI_FM); break; \
-    case SDRHIP_EPI_AM: SDRHIP_SD(R_, SDRHIP_EPI_AM); break; \
-    case SDRHIP_EPI_USB: SDRHIP_SD(R_, SDRHIP_EPI_USB); break; \
-    default: SDRHIP_SD(R_, SDRHIP_EPI_NONE); break; } return NWX; } while (0)
-  // (real input: 4-wave workgroups only — a plan whose arrays need a larger one runs the VALU kernel)
-  if (rot) { constexpr int NWX = hot_sd_nw(S, NH, IN, true, NW0); if constexpr (NWX > 0 && (IN != HOT_REAL || NWX == 4)) SDRHIP_SD_E(true); }
-  else { constexpr int NWX = hot_sd_nw(S, NH, IN, false, NW0); if constexpr (NWX > 0 && (IN != HOT_REAL || NWX == 4)) SDRHIP_SD_E(false); }
-#undef SDRHIP_SD_E
-#undef SDRHIP_SD_ATTR
-#undef SDRHIP_SD
-  return 0;
+// The kernel of a form for one rotation flag and epilogue, and the epilogues each form launches: HOT_EPI_PARTIAL in the
+// any-D form only (not for real or complex<int8> input), no AM or USB for complex<int8>.
+template <int FORM, int S, int S0, int NH, bool ROT, int EPI, int IN, int NW, int L0, int NL>
+constexpr auto hot_kernel() {
+  if constexpr (FORM == HOT_D8) return &iqbb_hot_kernel<S, S0, NH, ROT, EPI, IN, NW, L0, NL>;
+  else if constexpr (FORM == HOT_ANYD) return &iqbb_hot_anyd_kernel<S, S0, NH, ROT, EPI, IN, NW>;
+  else return &iqbb_hot_sd_kernel<S, S0, NH, ROT, EPI, IN, NW>;
+}
+constexpr bool hot_has_epi(int form, int in, int epi) {
+  if (epi == HOT_EPI_PARTIAL) return form == HOT_ANYD && in != HOT_REAL && in != HOT_CS8;
+  return in != HOT_CS8 || epi == SDRHIP_EPI_FM || epi == SDRHIP_EPI_NONE;
 }
 
-template <int S, int S0, int NH, int IN, int NW, int L0 = 0, int NL = S>
-void hot_launch_one(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  constexpr bool PAIR = hot_pair(IN, NW, false);
-  const size_t lds = (size_t)hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, 0, PAIR), PAIR);
-  if constexpr (IN != HOT_CS8) if (lds > 64 * 1024) {   // (the pair variant's four window buffers per wave; long filters)
-    static std::atomic<uint64_t> attr_set{0};
-    once_per_device(attr_set, [&] {
-#define SDRHIP_HOT_ATTR(R_, E_) SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW, L0, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-    SDRHIP_HOT_ATTR(true, SDRHIP_EPI_FM); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_AM); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_USB); SDRHIP_HOT_ATTR(true, SDRHIP_EPI_NONE);
-    SDRHIP_HOT_ATTR(false, SDRHIP_EPI_FM); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_AM); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_USB); SDRHIP_HOT_ATTR(false, SDRHIP_EPI_NONE);
-#undef SDRHIP_HOT_ATTR
-    });
-  }
-  const dim3 grid(hl.grid, 1), block(64 * NW);
-#define SDRHIP_HOT(R_, E_) hipLaunchKernelGGL((iqbb_hot_kernel<S, S0, NH, R_, E_, IN, NW, L0, NL>), grid, block, lds, hl.stream, ha, b)
-#define SDRHIP_HOT_E(R_) do { switch (epi) { \
-    case SDRHIP_EPI_FM: SDRHIP_HOT(R_, SDRHIP_EPI_FM); break; \
-    case SDRHIP_EPI_AM: if constexpr (IN != HOT_CS8) SDRHIP_HOT(R_, SDRHIP_EPI_AM); break; \
-    case SDRHIP_EPI_USB: if constexpr (IN != HOT_CS8) SDRHIP_HOT(R_, SDRHIP_EPI_USB); break; \
-    default: SDRHIP_HOT(R_, SDRHIP_EPI_NONE); break; } } while (0)
-  if (rot) SDRHIP_HOT_E(true); else SDRHIP_HOT_E(false);
-#undef SDRHIP_HOT_E
-#undef SDRHIP_HOT
-}
-
-template <int S, int S0, int NH, int IN, int NW = 4>
-void hot_launch_anyd_one(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  const int extra = hot_anyd_extra(S, IN, rot, NW);
-  const size_t lds = (size_t)hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, extra)) + extra;
-  static_assert(hot_lds_bytes(S, NH, IN, NW, false) + hot_anyd_extra(S, IN, false, NW) <= 163840, "any-D form: a workgroup's LDS");
-  if constexpr (IN != HOT_CS8) if (NW > 4) {   // (beyond 64 KB of dynamic LDS: once per DEVICE and kernel)
-    static std::atomic<uint64_t> attr_set{0};
-    once_per_device(attr_set, [] {
-#define SDRHIP_ANYD_ATTR(R_, E_) SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&iqbb_hot_anyd_kernel<S, S0, NH, R_, E_, IN, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, hot_lds_cap(NW, false, S) + hot_anyd_extra(S, IN, false, NW) > 163840 ? 163840 : hot_lds_cap(NW, false, S) + hot_anyd_extra(S, IN, false, NW)))
-      SDRHIP_ANYD_ATTR(true, SDRHIP_EPI_NONE); SDRHIP_ANYD_ATTR(true, SDRHIP_EPI_FM); SDRHIP_ANYD_ATTR(true, SDRHIP_EPI_AM); SDRHIP_ANYD_ATTR(true, SDRHIP_EPI_USB);
-      SDRHIP_ANYD_ATTR(false, SDRHIP_EPI_NONE); SDRHIP_ANYD_ATTR(false, SDRHIP_EPI_FM); SDRHIP_ANYD_ATTR(false, SDRHIP_EPI_AM); SDRHIP_ANYD_ATTR(false, SDRHIP_EPI_USB);
-      SDRHIP_ANYD_ATTR(true, HOT_EPI_PARTIAL); SDRHIP_ANYD_ATTR(false, HOT_EPI_PARTIAL);
-#undef SDRHIP_ANYD_ATTR
-    });
-  }
-  const dim3 grid(hl.grid, 1), block(64 * NW);
-#define SDRHIP_ANYD(R_, E_) hipLaunchKernelGGL((iqbb_hot_anyd_kernel<S, S0, NH, R_, E_, IN, NW>), grid, block, lds, hl.stream, ha, b)
-#define SDRHIP_ANYD_E(R_) do { switch (epi) { \
-    case SDRHIP_EPI_FM: SDRHIP_ANYD(R_, SDRHIP_EPI_FM); break; \
-    case SDRHIP_EPI_AM: if constexpr (IN != HOT_CS8) SDRHIP_ANYD(R_, SDRHIP_EPI_AM); break; \
-    case SDRHIP_EPI_USB: if constexpr (IN != HOT_CS8) SDRHIP_ANYD(R_, SDRHIP_EPI_USB); break; \
-    case HOT_EPI_PARTIAL: if constexpr (IN != HOT_REAL && IN != HOT_CS8) SDRHIP_ANYD(R_, HOT_EPI_PARTIAL); break; \
-    default: SDRHIP_ANYD(R_, SDRHIP_EPI_NONE); break; } } while (0)
-  if (rot) SDRHIP_ANYD_E(true); else SDRHIP_ANYD_E(false);
-#undef SDRHIP_ANYD_E
-#undef SDRHIP_ANYD
+// One launch of a form over the high-plane range [S0, S0 + NH) and the low-plane range [L0, L0 + NL), in workgroups of NW
+// waves (the small-D form: hot_sd_range_waves of that NW — nothing is launched where it is 0, the host has checked).
+// Beyond 64 KB of dynamic LDS the kernels' limit is raised once per device: /8 and small-D forms to their launch's LDS,
+// any-D (workgroups of 8 or 16 waves) to its cap. (The any-D list holds HOT_EPI_PARTIAL for real input too: those kernels
+// are compiled, never launched.)
+template <int FORM, int S, int S0, int NH, int IN, int NW, int L0, int NL>
+void hot_launch_form(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+  auto run = [&](auto rot_c) {
+    constexpr bool ROT = decltype(rot_c)::value;
+    constexpr int NWL = FORM == HOT_SD ? hot_sd_range_waves(S, HotRange{S0, NH, NW}, IN, ROT) : NW;
+    if constexpr (NWL > 0) {
+      constexpr bool PAIR = FORM == HOT_D8 && hot_pair(IN, NW, false);
+      constexpr int extra = FORM == HOT_ANYD ? hot_anyd_extra(S, IN, ROT, NW) : FORM == HOT_SD ? hot_sd_extra(S, IN, ROT, NWL) : 0;
+      constexpr size_t lds = FORM == HOT_D8 ? hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, 0, PAIR), PAIR)
+                           : FORM == HOT_ANYD ? hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, extra)) + extra
+                                              : hot_lds_bytes(S, NH, IN, NWL, false) + extra;
+      static_assert(FORM != HOT_ANYD || hot_lds_bytes(S, NH, IN, NW, false) + hot_anyd_extra(S, IN, false, NW) <= 163840, "any-D form: a workgroup's LDS");
+      constexpr int anyd_cap = hot_lds_cap(NW, false, S) + hot_anyd_extra(S, IN, false, NW);
+      constexpr int attr = FORM == HOT_ANYD ? (anyd_cap > 163840 ? 163840 : anyd_cap) : (int)lds;
+      if constexpr (IN != HOT_CS8) if (FORM == HOT_ANYD ? NW > 4 : lds > 64 * 1024) {
+        static std::atomic<uint64_t> attr_set{0};
+        once_per_device(attr_set, [] {
+          auto set = [](auto e) {
+            constexpr int E = decltype(e)::value;
+            if constexpr (E != HOT_EPI_PARTIAL || FORM == HOT_ANYD)
+              SDRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(hot_kernel<FORM, S, S0, NH, ROT, E, IN, NWL, L0, NL>()),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, attr));
+          };
+          set(std::integral_constant<int, SDRHIP_EPI_FM>{}); set(std::integral_constant<int, SDRHIP_EPI_AM>{});
+          set(std::integral_constant<int, SDRHIP_EPI_USB>{}); set(std::integral_constant<int, SDRHIP_EPI_NONE>{});
+          set(std::integral_constant<int, HOT_EPI_PARTIAL>{});
+        });
+      }
+      auto go = [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (hot_has_epi(FORM, IN, E))
+          hipLaunchKernelGGL((hot_kernel<FORM, S, S0, NH, ROT, E, IN, NWL, L0, NL>()), dim3(hl.grid, 1), dim3(64 * NWL), lds, hl.stream, ha, b);
+      };
+      switch (epi) {
+        case SDRHIP_EPI_FM: go(std::integral_constant<int, SDRHIP_EPI_FM>{}); break;
+        case SDRHIP_EPI_AM: go(std::integral_constant<int, SDRHIP_EPI_AM>{}); break;
+        case SDRHIP_EPI_USB: go(std::integral_constant<int, SDRHIP_EPI_USB>{}); break;
+        case HOT_EPI_PARTIAL: go(std::integral_constant<int, HOT_EPI_PARTIAL>{}); break;
+        default: go(std::integral_constant<int, SDRHIP_EPI_NONE>{}); break;
+      }
+    }
+  };
+  if (rot) run(std::true_type{}); else run(std::false_type{});
 }
 
 }  // namespace
+
+#ifdef SDRHIP_HOT_INSTANTIATE   // (the iqbb_hot_*.hip units only: every other file sees HotClass's declaration alone)
+namespace sdrhip {
+// range (and low-plane range) -> template arguments, walking the class's tables
+template <int FORM, int S, int IN>
+void HotClass<FORM, S, IN>::launch(int range, int lo, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+  hot_pick<(int)std::size(hot_ranges_of<S>())>(range, [&](auto r) {
+    constexpr HotRange R = hot_ranges_of<S>()[decltype(r)::value];
+    if constexpr (FORM == HOT_D8 && (IN == HOT_CS16 || IN == HOT_CU8)) {
+      hot_pick<(int)std::size(hot_lo_ranges_of<S>())>(lo, [&](auto l) {
+        constexpr HotLoRange L = hot_lo_ranges_of<S>()[decltype(l)::value];
+        constexpr bool inside = R.S0 >= L.L0 && R.S0 + R.NH <= L.L0 + L.NL;
+        hot_launch_form<FORM, S, R.S0, R.NH, IN, R.NW, inside ? L.L0 : 0, inside ? L.NL : S>(rot, epi, hl, ha, b);
+      });
+    } else {
+      hot_launch_form<FORM, S, R.S0, R.NH, IN, R.NW, 0, S>(rot, epi, hl, ha, b);
+    }
+  });
+}
+}  // namespace sdrhip
+#endif

@@ -1,13 +1,4 @@
-// iqbb_hot_anyd17_cs16.hip — the hot kernel's any-decimation form (iqbb_hot.hpp, DG) for S = 17 K steps (orders 130 ... 257),
-// complex<int16> input: 8- and 16-wave workgroups sharing one LDS copy of the tap fragments, as the /8 kernel of this class.
+// iqbb_hot_anyd17_cs16.hip — the hot kernel (iqbb_hot.hpp): the any-D form, 17 K steps, complex<int16> (one unit per class group: they compile in parallel)
+#define SDRHIP_HOT_INSTANTIATE
 #include "iqbb_hot.hpp"
-
-namespace sdrhip {
-void hot_launch_anyd17_cs16(int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  switch (range) {
-    case 0: hot_launch_anyd_one<17, 6, 5, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    case 1: hot_launch_anyd_one<17, 4, 9, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    default: hot_launch_anyd_one<17, 0, 17, HOT_CS16, 16>(rot, epi, hl, ha, b); break;
-  }
-}
-}  // namespace sdrhip
+template struct sdrhip::HotClass<HOT_ANYD, 17, HOT_CS16>;

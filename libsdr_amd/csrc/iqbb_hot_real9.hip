@@ -1,14 +1,4 @@
-// iqbb_hot_real9.hip — explicit instantiations of the hot kernel (iqbb_hot.hpp) for the real-input BaseBand<int16_t>,
-// S = 9 K steps of 32 real samples (orders up to 273).
+// iqbb_hot_real9.hip — the hot kernel (iqbb_hot.hpp): the /8 form, real input, 9 K steps (one unit per class group: they compile in parallel)
+#define SDRHIP_HOT_INSTANTIATE
 #include "iqbb_hot.hpp"
-
-namespace sdrhip {
-void hot_launch_real9(int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  switch (range) {
-    case 0: hot_launch_one<9, 3, 3, HOT_REAL, 4>(rot, epi, hl, ha, b); break;
-    case 1: hot_launch_one<9, 2, 5, HOT_REAL, 4>(rot, epi, hl, ha, b); break;
-    case 2: hot_launch_one<9, 1, 7, HOT_REAL, 4>(rot, epi, hl, ha, b); break;
-    default: hot_launch_one<9, 0, 9, HOT_REAL, 4>(rot, epi, hl, ha, b); break;
-  }
-}
-}  // namespace sdrhip
+template struct sdrhip::HotClass<HOT_D8, 9, HOT_REAL>;

@@ -1,15 +1,4 @@
-// iqbb_hot_s33_cs16.hip — explicit instantiations of the hot kernel (iqbb_hot.hpp) for S = 33 K steps (orders 258 ... 513),
-// complex<int16> input: one 8-wave workgroup per CU (33 ... 66 KB of tap fragments, 1024-sample windows).
+// iqbb_hot_s33_cs16.hip — the hot kernel (iqbb_hot.hpp): the /8 form, 33 K steps (orders up to 513), complex<int16> (one unit per class group: they compile in parallel)
+#define SDRHIP_HOT_INSTANTIATE
 #include "iqbb_hot.hpp"
-
-namespace sdrhip {
-void hot_launch_s33_cs16(int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  switch (range) {
-    case 0: hot_launch_one<33, 12, 9, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    case 1: hot_launch_one<33, 16, 9, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    case 2: hot_launch_one<33, 18, 9, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    case 3: hot_launch_one<33, 8, 17, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-    default: hot_launch_one<33, 0, 33, HOT_CS16, 8>(rot, epi, hl, ha, b); break;
-  }
-}
-}  // namespace sdrhip
+template struct sdrhip::HotClass<HOT_D8, 33, HOT_CS16>;

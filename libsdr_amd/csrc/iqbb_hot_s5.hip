@@ -1,13 +1,4 @@
-// iqbb_hot_s5.hip — explicit instantiations of the hot kernel (iqbb_hot.hpp) for S = 5 K steps (orders up to 65), complex<int16> and complex<uint8> input; one translation unit per filter-length
-// class so that the build compiles them in parallel.
+// iqbb_hot_s5.hip — the hot kernel (iqbb_hot.hpp): the /8 form, 5 K steps (orders up to 65) (one unit per class group: they compile in parallel)
+#define SDRHIP_HOT_INSTANTIATE
 #include "iqbb_hot.hpp"
-
-namespace sdrhip {
-void hot_launch_s5(int in, int range, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  const bool cu8 = in == HOT_CU8;
-  switch (range) {
-    case 0: if (cu8) hot_launch_one<5, 1, 3, HOT_CU8, 4>(rot, epi, hl, ha, b); else hot_launch_one<5, 1, 3, HOT_CS16, 4>(rot, epi, hl, ha, b); break;
-    default: if (cu8) hot_launch_one<5, 0, 5, HOT_CU8, 4>(rot, epi, hl, ha, b); else hot_launch_one<5, 0, 5, HOT_CS16, 4>(rot, epi, hl, ha, b); break;
-  }
-}
-}  // namespace sdrhip
+template struct sdrhip::HotClass<HOT_D8, 5, HOT_CS16>; template struct sdrhip::HotClass<HOT_D8, 5, HOT_CU8>;

@@ -784,20 +784,36 @@ __global__ __launch_bounds__(256) void iqbb_bigd_finish_kernel(const BigdArgs a)
 
 }  // namespace
 
+// The hot kernel's classes are compiled in the iqbb_hot_*.hip units; this picks one and instantiates none.
+void sdrhip::hot_launch(int form, int S, int in, int range, int lo, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
+  bool done = false;
+  hot_with_steps(S, [&](auto s) {
+    hot_pick<3>(form, [&](auto f) {
+      hot_pick<4>(in, [&](auto k) {
+        constexpr int SC = decltype(s)::value, F = decltype(f)::value, IN = decltype(k)::value;
+        if constexpr (hot_class(F, SC, IN))
+          if (form == F && in == IN) { HotClass<F, SC, IN>::launch(range, lo, rot, epi, hl, ha, b); done = true; }
+      });
+    });
+  });
+  SDRHIP_REQUIRE(done, SDRHIP_E_UNSUPPORTED, "no hot kernel class for form %d, %d K steps, input kind %d", form, S, in);
+}
+
 namespace {
-// the hot kernels live in one translation unit per filter-length class (iqbb_hot_s*.hip)
-void launch_hot(int S, int in, int range, int lo, bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, const IqbbArgs &b) {
-  if (in == HOT_REAL) { hot_launch_real(S, range, rot, epi, hl, ha, b); return; }
-  if (in == HOT_CS8) { hot_launch_cs8(S, range, rot, epi, hl, ha, b); return; }
-  const bool cu8 = in == HOT_CU8;
-  switch (S) {
-    case 2: hot_launch_s2(in, range, rot, epi, hl, ha, b); break;
-    case 3: hot_launch_s3(in, range, rot, epi, hl, ha, b); break;
-    case 5: hot_launch_s5(in, range, rot, epi, hl, ha, b); break;
-    case 9: if (cu8) hot_launch_s9_cu8(range, lo, rot, epi, hl, ha, b); else hot_launch_s9_cs16(range, lo, rot, epi, hl, ha, b); break;
-    case 17: if (cu8) hot_launch_s17_cu8(range, rot, epi, hl, ha, b); else hot_launch_s17_cs16(range, rot, epi, hl, ha, b); break;
-    default: if (cu8) hot_launch_s33_cu8(range, rot, epi, hl, ha, b); else hot_launch_s33_cs16(range, rot, epi, hl, ha, b); break;
+// A tap set's values must fit the plan's sample type (complex input: int16, real input: 24 bits). Returns whether the high
+// bytes of every value and of its negation fit int8 (the matrix formulations' byte planes); need_planes: an error where not.
+bool check_taps(const int32_t *taps, int order, bool real, bool need_planes) {
+  auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
+  bool planes = true;
+  for (int i = 0; i < 2 * order; i++) {   // (both v and -v are packed: Kr, -Ki / Ki, Kr)
+    if (real) SDRHIP_REQUIRE(taps[i] > -(1 << 23) && taps[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "tap %d = %d exceeds 24 bits", i / 2, taps[i]);
+    else SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
+    const bool fits = high_byte(taps[i]) <= 127 && high_byte(-taps[i]) <= 127;
+    if (need_planes)
+      SDRHIP_REQUIRE(fits, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the plan's int8 byte planes: create a new plan", i / 2, taps[i]);
+    planes = planes && fits;
   }
+  return planes;
 }
 }  // namespace
 
@@ -892,12 +908,6 @@ struct sdrhip_iqbb_i16 {
             if (al != 0) al_mask |= (uint64_t)1 << st;
             frag[(((size_t)(2 * st + 1) * 64 + l) * 16) + j] = (int8_t)al;
           }
-      {   // the hot kernel's compile-time high-plane range, as for path 1
-        int nr = 0;
-        const HotRange *rg = hot_ranges(S, &nr);
-        for (int r = 0; r < nr && hot_range < 0; r++)
-          if ((ah_mask & ~((((uint64_t)1 << rg[r].NH) - 1u) << rg[r].S0)) == 0) hot_range = r;
-      }
       if (!tapfrag.p) tapfrag.alloc((size_t)S * 2 * 64);
       tapfrag.upload(reinterpret_cast<const v4i *>(frag.data()), (size_t)S * 2 * 64, ctx->stream);
     } else if (path >= 1) {   // (a path 3 plan that fell back to the VALU kernel above has path 0 by now)
@@ -953,29 +963,32 @@ struct sdrhip_iqbb_i16 {
       }
       build(path == 1);
       if (path == 1) upload_rot();
-      if (path == 1 || path == 3) {   // smallest centred range [S0, S0+NH) of the hot kernel that covers the mask (path 3: its any-D form)
-        int nr = 0;
-        const HotRange *rg = hot_ranges(S, &nr);
-        for (int r = 0; r < nr && hot_range < 0; r++)
-          if ((ah_mask & ~((((uint64_t)1 << rg[r].NH) - 1u) << rg[r].S0)) == 0) hot_range = r;
-        // (path 1: the /8 form's low-plane range [L0, L0+NL), the narrowest that covers al_mask and the high range; the last
-        // entry is every step. al_mask is read off the packed fragments themselves: the cu8 set only permutes bytes inside a dword)
-        if (path == 1 && hot_range >= 0) {
-          int nl = 0;
-          const HotLoRange *lr = hot_lo_ranges(S, &nl);
-          for (int r = 0; r < nl && lo_range < 0; r++) {
-            const bool covers = (al_mask & ~((((uint64_t)1 << lr[r].NL) - 1u) << lr[r].L0)) == 0;
-            const bool inside = rg[hot_range].S0 >= lr[r].L0 && rg[hot_range].S0 + rg[hot_range].NH <= lr[r].L0 + lr[r].NL;
-            if ((covers && inside && env_trim) || r == nl - 1) lo_range = r;
-          }
-        }
-      }
       if (!tapfrag.p) tapfrag.alloc((size_t)S * 2 * 64);
       tapfrag.upload(reinterpret_cast<const v4i *>(frag.data()), (size_t)S * 2 * 64, ctx->stream);
     }
+    if (path != 0) pick_hot_ranges();
     if (!this->taps.p) this->taps.alloc(OP);
     this->taps.upload(tp.data(), OP, ctx->stream);
   }
+  // The hot kernel's compile-time ranges for the masks: the narrowest high-plane range [S0, S0 + NH) that covers ah_mask and
+  // (path 1: the /8 form) the narrowest low-plane range [L0, L0 + NL) that covers al_mask and holds the high one — the last
+  // entry is every step. (al_mask is read off the packed fragments themselves: the cu8 set only permutes bytes inside a dword)
+  void pick_hot_ranges() {
+    auto covers = [](uint64_t mask, int first, int n) { return (mask & ~((((uint64_t)1 << n) - 1u) << first)) == 0; };
+    int nr = 0, nl = 0;
+    const HotRange *rg = hot_ranges(S, &nr);
+    for (int r = 0; r < nr && hot_range < 0; r++)
+      if (covers(ah_mask, rg[r].S0, rg[r].NH)) hot_range = r;
+    if (path != 1 || hot_range < 0) return;
+    const HotLoRange *lr = hot_lo_ranges(S, &nl);
+    for (int r = 0; r < nl && lo_range < 0; r++) {
+      const bool inside = rg[hot_range].S0 >= lr[r].L0 && rg[hot_range].S0 + rg[hot_range].NH <= lr[r].L0 + lr[r].NL;
+      if ((covers(al_mask, lr[r].L0, lr[r].NL) && inside && env_trim) || r == nl - 1) lo_range = r;
+    }
+  }
+  // the VALU kernel's LDS: sample window, rotation table, group sums (other decimations than 8: a staging row)
+  size_t valu_lds() const { return (TI + (size_t)OP + 8 + 256 + 2 * (((size_t)CG + 3) & ~(size_t)3)) * 4 + (fast8 ? 0 : (size_t)TI * 8); }
+  int hot_nw() const { int n = 0; const HotRange *rg = hot_ranges(S, &n); return rg[std::min(hot_range, n - 1)].NW; }
 
   struct Geometry { uint64_t g_first; int n_groups, n_out, base0_rel, extra0; };
   Geometry geometry(size_t N) const {
@@ -995,6 +1008,31 @@ struct sdrhip_iqbb_i16 {
   size_t out_elem_bytes() const { return epi == SDRHIP_EPI_NONE ? (i8 ? 2 : 4) : 2; }
   size_t in_elem_bytes() const { return (in_cu8 || real || i8) ? 2 : 4; }
 
+  // The fields every hot launch shares; the caller adds its form's geometry.
+  HotArgs hot_args(const uint32_t *in_dev, size_t N, size_t in_stride, void *out_dev, size_t out_stride, const v4i *tapfrag_) const {
+    HotArgs ha{};
+    ha.in = in_dev; ha.in_stride = (long)in_stride; ha.out = out_dev; ha.out_stride = (long)out_stride;
+    ha.tapfrag = tapfrag_; ha.lut = lut.p; ha.inc = inc; ha.n0_lo = (uint32_t)(n0 - phase0); ha.negative = negative;
+    ha.cre = cre; ha.cim = cim; ha.N = (int)N; ha.C = C; ha.stamps = nullptr;
+    return ha;
+  }
+  // The persistent grid of a hot launch over `tiles` tiles per channel, in workgroups of NW waves = NW / 4 virtual (4-wave)
+  // ones: units of tpw tiles (at most 4, fewer while the grid would get under 4 units per virtual workgroup; resident: a whole
+  // channel), units dealt over the virtual workgroups. Returns the workgroups.
+  unsigned hot_grid(HotArgs &ha, int tiles, int NW, bool resident) const {
+    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;   // virtual workgroups = waves per SIMD (SDRHIP_IQBB_WGPCU: tuning hook, builds with -DK1_MINWAVES=5)
+    int htpw = 4; while (htpw > 1 && (size_t)ceil_div((size_t)tiles, (size_t)htpw) * C < 4 * (size_t)nvwg) htpw >>= 1;
+    if (resident) htpw = tiles;
+    else if (env_tpw) htpw = env_tpw;   // tuning hook
+    ha.tpw = htpw;
+    ha.G = (int)ceil_div((size_t)tiles, (size_t)htpw); ha.U = ha.G * C;
+    const int vper = NW / 4;
+    const int grid = (int)ceil_div((size_t)std::max(1, std::min(nvwg, std::max(ha.U, C))), (size_t)vper);   // (every channel's cold slices need a taker too)
+    const int gx = grid * vper;
+    ha.dq = gx / ha.G; ha.dr = gx % ha.G;
+    return (unsigned)grid;
+  }
+
   // Path 1's hot kernel (iqbb_hot.hpp): one launch for the whole call — a persistent grid over the wave slices that
   // touch no border of the call, then the same workgroups' share of the cold slices (tile 0 and the tiles from t_hi on).
   // false: the call is too short to have a tile of hot slices; the general kernel runs it.
@@ -1005,19 +1043,13 @@ struct sdrhip_iqbb_i16 {
     long t = tiles - 1;   // the last tile always holds cold slices (history roll, state)
     while (t >= 2 && !(host_hot((int)t - 1, 0) && host_hot((int)t - 1, 1) && host_hot((int)t - 1, 2) && host_hot((int)t - 1, 3))) t--;
     if (t < 2) return false;
-    int nr = 0;
-    const HotRange *rg = hot_ranges(S, &nr);
-    const int NW = rg[hot_range].NW;
-    HotArgs ha{};
-    ha.in = in_dev; ha.in_stride = (long)in_stride; ha.out = out_dev; ha.out_stride = (long)out_stride;
-    ha.tapfrag = in_cu8 ? tapfrag_rot.p : tapfrag.p; ha.lut = lut.p; ha.inc = inc; ha.n0_lo = (uint32_t)(n0 - phase0); ha.negative = negative;
-    ha.base0_rel = g.base0_rel; ha.OG = OG; ha.ovl = ovl; ha.t_lo = 0; ha.t_hi = tiles; ha.cre = cre; ha.cim = cim;
-    ha.N = (int)N; ha.n_out = g.n_out; ha.C = C; ha.stamps = nullptr;
+    HotArgs ha = hot_args(in_dev, N, in_stride, out_dev, out_stride, in_cu8 ? tapfrag_rot.p : tapfrag.p);
+    ha.base0_rel = g.base0_rel; ha.OG = OG; ha.ovl = ovl; ha.t_lo = 0; ha.t_hi = tiles; ha.n_out = g.n_out;
     ha.D = 8; ha.GS = 64; ha.lpg_sh = 0; ha.inv_d = 0.125f; ha.philast = nullptr; ha.philast_stride = 0; ha.part = nullptr; ha.fin_groups = 0;   // (the any-D form's fields)
     // multi-buffer call with FM (launch_multi): the hot slices write the buffers' first two outputs themselves where the boundary
     // group and the one behind it are stored lanes of ONE hot slice; the others stay on the list for the fix-up launch
     ha.mb_p = 0; ha.mb_q1 = 0; ha.mb_qlast = 0; ha.mb_magic = 0;
-    if (!mb_q.empty() && epi == SDRHIP_EPI_FM && !i8 && !hot_pair(kind, rg[hot_range].NW, false)) {
+    if (!mb_q.empty() && epi == SDRHIP_EPI_FM && !i8 && !hot_pair(kind, hot_nw(), false)) {
       const int per = 64 - ovl;   // stored groups per slice
       long P = mb_q.size() >= 2 ? (long)mb_q[1] - mb_q[0] : (long)1 << 30;
       bool uniform = P >= 128;
@@ -1036,20 +1068,9 @@ struct sdrhip_iqbb_i16 {
     if (!k1_stamps.p) { k1_stamps.alloc(32768 * 16); k1_stamps.zero(ctx->stream); }
     ha.stamps = k1_stamps.p;
 #endif
-    // persistent grid of 4 virtual (4-wave) workgroups per CU = 4 waves per SIMD; a real workgroup is NW / 4 of them.
-    // Units of at most 4 tiles so that the static split leaves a short tail.
-    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;   // virtual (4-wave) workgroups = waves per SIMD (SDRHIP_IQBB_WGPCU: tuning hook, builds with -DK1_MINWAVES=5)
-    int htpw = 4; while (htpw > 1 && (size_t)ceil_div((size_t)tiles, (size_t)htpw) * C < 4 * (size_t)nvwg) htpw >>= 1;
-    if (env_tpw) htpw = env_tpw;   // tuning hook
-    ha.tpw = htpw;
-    ha.G = (int)ceil_div((size_t)tiles, (size_t)htpw); ha.U = ha.G * C;
-    const int vper = NW / 4;
-    const int grid = (int)ceil_div((size_t)std::min(nvwg, std::max(ha.U, C)), (size_t)vper);   // (every channel's cold slices need a taker too)
-    const int gx = grid * vper;   // virtual workgroups
-    ha.dq = gx / ha.G; ha.dr = gx % ha.G;
+    const HotLaunch hl{hot_grid(ha, tiles, hot_nw(), false), ctx->stream};
     a.bt_hi = (int)t; a.tpw = 1;
-    HotLaunch hl{(unsigned)grid, ctx->stream};
-    launch_hot(S, kind, hot_range, lo_range, inc != 0, epi, hl, ha, a);
+    hot_launch(HOT_D8, S, kind, hot_range, lo_range, inc != 0, epi, hl, ha, a);
     return true;
   }
 
@@ -1062,7 +1083,7 @@ struct sdrhip_iqbb_i16 {
     return path == 3 && use_hot && hot_range >= 0 && S <= 33 && !i8 && !real && D >= bigd_min && D >= 257 && !(D >= bigd_skip_lo && D <= 512) && part.p != nullptr;
   }
   bool launch_bigd_call(const IqbbArgs &a0, const Geometry &g, const uint32_t *in_dev, size_t N, size_t in_stride, void *out_dev, size_t out_stride) {
-    const int kind = in_cu8 ? HOT_CU8 : HOT_CS16, halo = hot_halo(S, kind), win = hot_win(S, kind);
+    const int kind = hot_kind(), halo = hot_halo(S, kind), win = hot_win(S, kind);
     // the kernel's geometry: slices of 512 samples from the call's first sample on = "decimation 512", one pseudo-group per slice
     const int nsl = (int)ceil_div(N, (size_t)512), tiles_h = (int)ceil_div((size_t)nsl, (size_t)4);
     auto slice_hot = [&](int sl) { return slice_is_hot(halo, win, 0, 4, 0, (int)N, nsl, sl >> 2, sl & 3, 512, 1); };
@@ -1073,32 +1094,17 @@ struct sdrhip_iqbb_i16 {
     SDRHIP_REQUIRE(part.n >= (size_t)C * 12 * tiles_h, SDRHIP_E_SIZE, "part holds %zu entries, the call needs %zu", part.n, (size_t)C * 12 * tiles_h);
     IqbbArgs a = a0;   // (the cold phase walks the PSEUDO groups; the real geometry goes to the finishing kernel)
     a.base0_rel = 0; a.n_groups = nsl; a.n_out = nsl; a.extra0 = 0; a.D = 512; a.fix_lo = a.fix_hi = 0;
-    HotArgs ha{};
-    ha.in = in_dev; ha.in_stride = (long)in_stride; ha.out = out_dev; ha.out_stride = (long)out_stride;
-    ha.tapfrag = in_cu8 ? tapfrag_rot.p : tapfrag_hot.p; ha.lut = lut.p; ha.inc = inc; ha.n0_lo = (uint32_t)(n0 - phase0); ha.negative = negative;
-    ha.base0_rel = 0; ha.OG = 4; ha.ovl = 0; ha.t_lo = s_lo >> 2; ha.t_hi = (s_hi + 3) >> 2; ha.cre = cre; ha.cim = cim;
-    ha.N = (int)N; ha.n_out = nsl; ha.C = C; ha.stamps = nullptr;
+    HotArgs ha = hot_args(in_dev, N, in_stride, out_dev, out_stride, in_cu8 ? tapfrag_rot.p : tapfrag_hot.p);
+    ha.base0_rel = 0; ha.OG = 4; ha.ovl = 0; ha.t_lo = s_lo >> 2; ha.t_hi = (s_hi + 3) >> 2; ha.n_out = nsl;
     ha.D = 512; ha.GS = 1; ha.tiles_h = tiles_h; ha.lpg_sh = 6; ha.inv_d = 0.f;
     ha.philast = nullptr; ha.philast_stride = 0;
     ha.part = part.p; ha.part_stride = 12 * tiles_h; ha.Dreal = D; ha.base_real = g.base0_rel;
-    int cnt = 0;
-    const HotRange *ranges = hot_ranges(S, &cnt);
-    const int NW = ranges[std::min(hot_range, cnt - 1)].NW, vper = NW / 4;
-    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;
-    int htpw = 4; while (htpw > 1 && (size_t)ceil_div((size_t)tiles_h, (size_t)htpw) * C < 4 * (size_t)nvwg) htpw >>= 1;
     // whole channels as units where they deal evenly over the grid (as the FM fix-up of the any-D form): a workgroup then
     // finishes the groups of its channels itself and the second launch is not needed
     const bool resident = channel_units();
-    if (resident) htpw = tiles_h;
-    else if (env_tpw) htpw = env_tpw;   // tuning hook
     ha.fin_groups = resident ? g.n_groups : 0; ha.fin_out = g.n_out; ha.fin_epi = epi;
-    ha.tpw = htpw;
-    ha.G = (int)ceil_div((size_t)tiles_h, (size_t)htpw); ha.U = ha.G * C;
-    const int grid = (int)ceil_div((size_t)std::max(1, std::min(nvwg, std::max(ha.U, C))), (size_t)vper);
-    const int gx = grid * vper;
-    ha.dq = gx / ha.G; ha.dr = gx % ha.G;
-    HotLaunch hl{(unsigned)grid, ctx->stream};
-    hot_launch_anyd(S, kind, hot_range, inc != 0, HOT_EPI_PARTIAL, hl, ha, a);
+    const HotLaunch hl{hot_grid(ha, tiles_h, hot_nw(), resident), ctx->stream};
+    hot_launch(HOT_ANYD, S, kind, hot_range, -1, inc != 0, HOT_EPI_PARTIAL, hl, ha, a);
     if (resident) return true;
     BigdArgs f;
     f.part = part.p; f.part_stride = 12 * tiles_h;
@@ -1126,7 +1132,7 @@ struct sdrhip_iqbb_i16 {
     if (D >= 9 && D <= 512) return true;
     if (i8) return false;   // (the int8 chain: decimation 8 and 9 ... 512 on the matrix cores)
     // decimations 1 ... 7: the small-decimation form, where its sample arrays fit a workgroup's LDS (iqbb_hot.hpp, SD, hot_sd_nw)
-    return D >= 1 && D <= 7 && hot_launch_sd(S, hot_kind(), hot_range, inc != 0, epi, HotLaunch{0, nullptr}, HotArgs{}, IqbbArgs{}, true) != 0;
+    return D >= 1 && D <= 7 && hot_sd_waves(S, hot_kind(), hot_range, inc != 0) != 0;
   }
   bool launch_anyd_call(IqbbArgs &a, const Geometry &g, const uint32_t *in_dev, size_t N, size_t in_stride, void *out_dev,
                         size_t out_stride) {
@@ -1141,12 +1147,8 @@ struct sdrhip_iqbb_i16 {
     while (s_hi > s_lo && !slice_hot(s_hi - 1)) s_hi--;
     if (s_hi - s_lo < 16) return false;
     const int t_lo = s_lo >> 2, t_hi = (s_hi + 3) >> 2;
-    HotArgs ha{};
-    ha.in = in_dev; ha.in_stride = (long)in_stride; ha.out = out_dev; ha.out_stride = (long)out_stride;
-    ha.tapfrag = real ? tapfrag.p : in_cu8 ? tapfrag_rot.p : tapfrag_hot.p;   // (path 4's only set is the permuted one)
-    ha.lut = lut.p; ha.inc = inc; ha.n0_lo = (uint32_t)(n0 - phase0); ha.negative = negative;
-    ha.base0_rel = g.base0_rel; ha.OG = OGh; ha.ovl = 0; ha.t_lo = t_lo; ha.t_hi = t_hi; ha.cre = cre; ha.cim = cim;
-    ha.N = (int)N; ha.n_out = g.n_out; ha.C = C; ha.stamps = nullptr;
+    HotArgs ha = hot_args(in_dev, N, in_stride, out_dev, out_stride, real ? tapfrag.p : in_cu8 ? tapfrag_rot.p : tapfrag_hot.p);   // (path 4's only set is the permuted one)
+    ha.base0_rel = g.base0_rel; ha.OG = OGh; ha.ovl = 0; ha.t_lo = t_lo; ha.t_hi = t_hi; ha.n_out = g.n_out;
     ha.D = D; ha.GS = GS; ha.tiles_h = tiles_h;
     { int lpg = 1; while (2 * lpg <= 64 && 2 * lpg * GS <= 64) lpg *= 2; int sh = 0; while ((1 << sh) < lpg) sh++; ha.lpg_sh = sh; }
     ha.inv_d = (float)((1.0 / D) * (1.0 - 1.0 / 1048576.0));
@@ -1159,22 +1161,12 @@ struct sdrhip_iqbb_i16 {
     if (!k1_stamps.p) { k1_stamps.alloc(32768 * 16); k1_stamps.zero(ctx->stream); }
     ha.stamps = k1_stamps.p;
 #endif
-    // (17 K steps: 8- or 16-wave workgroups = 2 or 4 virtual ones sharing the tap fragments, as the /8 kernel of that class)
-    int cnt = 0;
-    const HotRange *ranges = hot_ranges(S, &cnt);
-    int NW = ranges[std::min(hot_range, cnt - 1)].NW;
-    if (D < 8) NW = hot_launch_sd(S, kind, hot_range, inc != 0, epi, HotLaunch{0, nullptr}, HotArgs{}, IqbbArgs{}, true);   // (the small-decimation form picks its own: hot_sd_nw)
-    const int vper = NW / 4;
-    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;   // (SDRHIP_IQBB_WGPCU: tuning hook — waves per SIMD)
-    int htpw = 4; while (htpw > 1 && (size_t)ceil_div((size_t)tiles_h, (size_t)htpw) * C < 4 * (size_t)nvwg) htpw >>= 1;
     // FM: the slices whose first output is neither out[0] nor out[1] (their own rules) and is emitted lack the angle of the
     // slice before them. Where whole channels deal evenly over the persistent grid (within 3 %: 1024 or 8192 channels on 1024
     // workgroups) a unit is a channel — one workgroup then finishes every slice of a channel and completes those outputs
     // itself, behind a barrier at its end; otherwise (few channels: units of 4 tiles keep the grid full) a second launch does.
     const int fix_lo = GS == 1 ? 2 : 1, fix_hi = epi == SDRHIP_EPI_FM ? (int)ceil_div((size_t)g.n_out, (size_t)GS) : 0;
     const bool resident = fix_hi > fix_lo && channel_units();
-    if (resident) htpw = tiles_h;
-    else if (env_tpw) htpw = env_tpw;   // tuning hook
     a.fix_lo = resident ? fix_lo : 0; a.fix_hi = resident ? fix_hi : 0;
     // ... and where they do not (few channels, or a count that leaves the grid uneven): the owners of neighbouring slices
     // can complete the first output between them by a handshake through device memory (iqbb_hot.hpp, hs_exchange) — ONE
@@ -1191,14 +1183,11 @@ struct sdrhip_iqbb_i16 {
       if (++hs_seq <= 0) hs_seq = 1;
       ha.hs = hs.p; ha.hs_stride = hs_stride; ha.hs_seq = hs_seq;
     }
-    ha.tpw = htpw;
-    ha.G = (int)ceil_div((size_t)tiles_h, (size_t)htpw); ha.U = ha.G * C;
-    const int grid = (int)ceil_div((size_t)std::max(1, std::min(nvwg, std::max(ha.U, C))), (size_t)vper);   // (every channel's cold slices need a taker too)
-    const int gx = grid * vper;   // virtual workgroups
-    ha.dq = gx / ha.G; ha.dr = gx % ha.G;
-    HotLaunch hl{(unsigned)grid, ctx->stream};
-    if (D < 8) (void)hot_launch_sd(S, kind, hot_range, inc != 0, epi, hl, ha, a, false);
-    else hot_launch_anyd(S, kind, hot_range, inc != 0, epi, hl, ha, a);
+    // (17 K steps: 8- or 16-wave workgroups = 2 or 4 virtual ones sharing the tap fragments, as the /8 kernel of that class;
+    // the small-decimation form picks its own: hot_sd_nw)
+    const int NW = D < 8 ? hot_sd_waves(S, kind, hot_range, inc != 0) : hot_nw();
+    const HotLaunch hl{hot_grid(ha, tiles_h, NW, resident), ctx->stream};
+    hot_launch(D < 8 ? HOT_SD : HOT_ANYD, S, kind, hot_range, -1, inc != 0, epi, hl, ha, a);
     if (!resident && !handshake && fix_hi > fix_lo)
       hipLaunchKernelGGL(iqbb_fm_fixup_kernel, dim3((unsigned)ceil_div((size_t)(fix_hi - fix_lo), (size_t)256), (unsigned)C), dim3(256), 0, ctx->stream,
                          reinterpret_cast<short *>(out_dev), (long)out_stride, philast.p, 4 * tiles_h, fix_lo, fix_hi, GS, C);
@@ -1234,90 +1223,14 @@ struct sdrhip_iqbb_i16 {
     if (env_tpw && mf8) tpw = env_tpw;   // tuning hook
     a.tiles = tiles; a.tpw = tpw; a.bt_hi = 0; a.fix_lo = a.fix_hi = 0;
     a.lpg = 1; while (a.lpg < 64 && a.lpg * 8 < D) a.lpg <<= 1;
-    dim3 grid((unsigned)ceil_div((size_t)tiles, (size_t)tpw), C), block(TPB);
-    if (path == 4 && D == R && use_hot && hot_range >= 0 && tiles >= 3 && launch_hot_call(a, g, in_dev, N, in_stride, out_dev, out_stride, tiles)) {
-      // (real int16 input: the hot kernel took the whole call)
-    } else if (real_anyd() && anyd_plan() && launch_anyd_call(a, g, in_dev, N, in_stride, out_dev, out_stride)) {
-      // (real int16 input at any other decimation: the hot kernel's any-D / small-decimation form took the whole call)
-    } else if (real_anyd()) {   // ... its short calls: the VALU kernel
-      hipLaunchKernelGGL((iqbb_i16_kernel<false, true>), grid, block, lds_bytes, ctx->stream, a);
-    } else if (path == 4) {
-#define SDRHIP_MFR(S_) do { if (inc != 0) hipLaunchKernelGGL((bb_real_mfma_kernel<S_, true>), grid, block, lds_bytes, ctx->stream, a); \
-                             else hipLaunchKernelGGL((bb_real_mfma_kernel<S_, false>), grid, block, lds_bytes, ctx->stream, a); } while (0)
-      switch (S) {
-        case 3: SDRHIP_MFR(3); break;
-        case 5: SDRHIP_MFR(5); break;
-        default: SDRHIP_MFR(9); break;
-      }
-#undef SDRHIP_MFR
-    } else if (long_filter() && path == 1 && use_hot && hot_range >= 0 && tiles >= 3 && launch_hot_call(a, g, in_dev, N, in_stride, out_dev, out_stride, tiles)) {
-      // (orders 258 ... 513 at decimation 8: the hot kernel's 33-step class took the whole call)
-    } else if (long_filter() && path == 3 && bigd_plan() && launch_bigd_call(a, g, in_dev, N, in_stride, out_dev, out_stride)) {
-    } else if (long_filter() && path == 3 && anyd_plan() && launch_anyd_call(a, g, in_dev, N, in_stride, out_dev, out_stride)) {
-    } else if (long_filter()) {   // ... their short calls: the VALU kernel (the class has no general matrix kernel)
-      if (fast8) hipLaunchKernelGGL((iqbb_i16_kernel<true, false>), grid, block, lds_bytes, ctx->stream, a);
-      else hipLaunchKernelGGL((iqbb_i16_kernel<false, false>), grid, block, lds_bytes, ctx->stream, a);
-    } else if (path == 3 && bigd_plan() && launch_bigd_call(a, g, in_dev, N, in_stride, out_dev, out_stride)) {
-      // (decimations above 256: partial sums by the hot kernel, groups finished in its last step or by a second, small launch)
-    } else if (path == 3 && anyd_plan() && launch_anyd_call(a, g, in_dev, N, in_stride, out_dev, out_stride)) {
-      // (the hot kernel's any-D form took the whole call)
-    } else if (path == 3) {
-      int tpw3 = 8; while (tpw3 > 1 && (size_t)ceil_div((size_t)tiles, (size_t)tpw3) * C < 2048) tpw3 >>= 1;
-      if (env_tpw) tpw3 = env_tpw;   // tuning hook
-      a.tpw = tpw3;
-      dim3 grid3((unsigned)ceil_div((size_t)tiles, (size_t)tpw3), C);
-#define SDRHIP_MFG(S_) do { if (in_cu8 && inc != 0) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, true, true>), grid3, block, lds_bytes, ctx->stream, a); \
-                             else if (in_cu8) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, false, true>), grid3, block, lds_bytes, ctx->stream, a); \
-                             else if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, true, false>), grid3, block, lds_bytes, ctx->stream, a); \
-                             else hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, false, false>), grid3, block, lds_bytes, ctx->stream, a); } while (0)
-      if (lds_bytes > 64 * 1024) {   // (17 K steps, small decimations; once per kernel and device: allow_lds_max)
-        allow_lds_max(&iqbb_i16_mfmag_kernel<17, true, true>, lds_bytes); allow_lds_max(&iqbb_i16_mfmag_kernel<17, false, true>, lds_bytes);
-        allow_lds_max(&iqbb_i16_mfmag_kernel<17, true, false>, lds_bytes); allow_lds_max(&iqbb_i16_mfmag_kernel<17, false, false>, lds_bytes);
-      }
-      switch (S) {
-        case 2: SDRHIP_MFG(2); break;
-        case 3: SDRHIP_MFG(3); break;
-        case 5: SDRHIP_MFG(5); break;
-        case 9: SDRHIP_MFG(9); break;
-        default: SDRHIP_MFG(17); break;
-      }
-#undef SDRHIP_MFG
-    } else if (path == 1 && use_hot && hot_range >= 0 && tiles >= 3 && launch_hot_call(a, g, in_dev, N, in_stride, out_dev, out_stride, tiles)) {
-      // (complex<int16> or complex<uint8> input, any filter length of path 1: the hot kernel took the whole call)
-    } else if (path == 1 && !in_cu8) {
-      // complex<int16> input, calls too short for the hot kernel (or SDRHIP_IQBB_HOT=0): the general kernel, raw tiles
-      // by LDS-DMA (LDS: table | one plane pair | raw tile | tap fragments)
-      const size_t PLWd = (2 * (size_t)(TI + OP) + 64 + 31) / 32 * 8, quads = (TI + OP + 4) / 4;
-      const size_t ldsd = (256 + 2 * PLWd + 4 * ((quads + 63) / 64 * 64)) * 4 + (size_t)S * 2 * 64 * 16;
-#define SDRHIP_MFD(S_) do { if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfma_dma_kernel<S_, true>), grid, block, ldsd, ctx->stream, a); \
-                             else hipLaunchKernelGGL((iqbb_i16_mfma_dma_kernel<S_, false>), grid, block, ldsd, ctx->stream, a); } while (0)
-      switch (S) {
-        case 2: SDRHIP_MFD(2); break;
-        case 3: SDRHIP_MFD(3); break;
-        case 5: SDRHIP_MFD(5); break;
-        case 9: SDRHIP_MFD(9); break;
-        default: SDRHIP_MFD(17); break;
-      }
-#undef SDRHIP_MFD
-    } else if (path == 1) {
-      // complex<uint8> input, calls too short for the hot kernel: the one-plane general kernel (its LDS: two single planes
-      // instead of two pairs)
-      const size_t lds1 = lds_bytes - 2 * (((2 * (size_t)(TI + OP) + 64 + 31) / 32 * 8) * 4);
-#define SDRHIP_MF(S_) do { if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfma_kernel<S_, true, true>), grid, block, lds1, ctx->stream, a); \
-                            else hipLaunchKernelGGL((iqbb_i16_mfma_kernel<S_, false, true>), grid, block, lds1, ctx->stream, a); } while (0)
-      switch (S) {
-        case 2: SDRHIP_MF(2); break;
-        case 3: SDRHIP_MF(3); break;
-        case 5: SDRHIP_MF(5); break;
-        case 9: SDRHIP_MF(9); break;
-        default: SDRHIP_MF(17); break;
-      }
-#undef SDRHIP_MF
-    } else if (real) {
-      if (fast8) hipLaunchKernelGGL((iqbb_i16_kernel<true, true>), grid, block, lds_bytes, ctx->stream, a);
-      else hipLaunchKernelGGL((iqbb_i16_kernel<false, true>), grid, block, lds_bytes, ctx->stream, a);
-    } else if (fast8) hipLaunchKernelGGL((iqbb_i16_kernel<true, false>), grid, block, lds_bytes, ctx->stream, a);
-    else hipLaunchKernelGGL((iqbb_i16_kernel<false, false>), grid, block, lds_bytes, ctx->stream, a);
+    bool done = false;   // (a long-call form that refuses the call leaves `a` as it was)
+    const CallForms cf = call_forms();
+    for (int i = 0; i < cf.n_long && !done; i++) {
+      if (cf.long_form[i] == LONG_HOT8) done = tiles >= 3 && launch_hot_call(a, g, in_dev, N, in_stride, out_dev, out_stride, tiles);
+      else if (cf.long_form[i] == LONG_BIGD) done = launch_bigd_call(a, g, in_dev, N, in_stride, out_dev, out_stride);
+      else done = launch_anyd_call(a, g, in_dev, N, in_stride, out_dev, out_stride);
+    }
+    if (!done) launch_short(cf.short_form, a, tiles);
     SDRHIP_CHECK_HIP(hipGetLastError());
     par ^= 1;
     if (fm_flip) par_fm ^= 1;
@@ -1325,6 +1238,110 @@ struct sdrhip_iqbb_i16 {
     if (n_out) *n_out = (size_t)g.n_out;
     last_args = a;
   }
+  // The kernels of a call, one decision for launch and kernel_names. Long calls: the hot forms in the order they are tried
+  // (each refuses a call too short for it) — the /8 form (paths 1 and 4 at decimation 8; calls of >= 3 tiles), the
+  // large-decimation form, the any-D / small-D form. Every other call: the plan's general kernel — the real-input
+  // lane-owned-group kernel (path 4 at decimation 8), the general MFMA kernels (path 3; path 1: complex<uint8> with one byte
+  // plane, complex<int16> by LDS-DMA), else the VALU kernel (path 0; real input at other decimations; orders 258 ... 513
+  // and the int8 chain, whose classes have no general matrix kernel).
+  enum { LONG_HOT8, LONG_BIGD, LONG_ANYD };
+  enum { SHORT_REAL_MFMA, SHORT_VALU, SHORT_MFMAG, SHORT_MFMA_CU8, SHORT_MFMA_DMA };
+  struct CallForms { int n_long = 0, long_form[2] = {}, short_form = SHORT_VALU; };
+  CallForms call_forms() const {
+    CallForms f;
+    if ((path == 1 || (path == 4 && D == R)) && use_hot && hot_range >= 0) f.long_form[f.n_long++] = LONG_HOT8;
+    if (bigd_plan()) f.long_form[f.n_long++] = LONG_BIGD;
+    if (anyd_plan()) f.long_form[f.n_long++] = LONG_ANYD;
+    f.short_form = path == 4 && D == R ? SHORT_REAL_MFMA
+                 : path == 0 || path == 4 || long_filter() ? SHORT_VALU
+                 : path == 3 ? SHORT_MFMAG
+                 : in_cu8 ? SHORT_MFMA_CU8 : SHORT_MFMA_DMA;
+    return f;
+  }
+  // what kernel_names reports: the kernels a long call runs, with the finishing or fix-up launch where one follows
+  std::string call_kernel_names() const {
+    const CallForms f = call_forms();
+    static const char *const general[] = {"bb_real_mfma_kernel", "iqbb_i16_kernel", "iqbb_i16_mfmag_kernel", "iqbb_i16_mfma_kernel", "iqbb_i16_mfma_dma_kernel"};
+    if (f.n_long == 0) return general[f.short_form];
+    if (f.long_form[0] == LONG_HOT8) return "iqbb_hot_kernel";
+    if (f.long_form[0] == LONG_BIGD) return channel_units() ? "iqbb_hot_anyd_kernel" : "iqbb_hot_anyd_kernel,iqbb_bigd_finish_kernel";
+    const bool fixup = epi == SDRHIP_EPI_FM && !channel_units() && (env_fm_handshake != 1 || !hs.p);   // (launch_anyd_call)
+    return std::string(D < 8 ? "iqbb_hot_sd_kernel" : "iqbb_hot_anyd_kernel") + (fixup ? ",iqbb_fm_fixup_kernel" : "");
+  }
+  void launch_short(int form, IqbbArgs &a, int tiles) {
+    const dim3 grid((unsigned)ceil_div((size_t)tiles, (size_t)a.tpw), C), block(TPB);
+    switch (form) {
+      case SHORT_REAL_MFMA:
+#define SDRHIP_MFR(S_) do { if (inc != 0) hipLaunchKernelGGL((bb_real_mfma_kernel<S_, true>), grid, block, lds_bytes, ctx->stream, a); \
+                             else hipLaunchKernelGGL((bb_real_mfma_kernel<S_, false>), grid, block, lds_bytes, ctx->stream, a); } while (0)
+        switch (S) {
+          case 3: SDRHIP_MFR(3); break;
+          case 5: SDRHIP_MFR(5); break;
+          default: SDRHIP_MFR(9); break;
+        }
+#undef SDRHIP_MFR
+        break;
+      case SHORT_MFMAG: {
+        int tpw3 = 8; while (tpw3 > 1 && (size_t)ceil_div((size_t)tiles, (size_t)tpw3) * C < 2048) tpw3 >>= 1;
+        if (env_tpw) tpw3 = env_tpw;   // tuning hook
+        a.tpw = tpw3;
+        const dim3 grid3((unsigned)ceil_div((size_t)tiles, (size_t)tpw3), C);
+#define SDRHIP_MFG(S_) do { if (in_cu8 && inc != 0) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, true, true>), grid3, block, lds_bytes, ctx->stream, a); \
+                             else if (in_cu8) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, false, true>), grid3, block, lds_bytes, ctx->stream, a); \
+                             else if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, true, false>), grid3, block, lds_bytes, ctx->stream, a); \
+                             else hipLaunchKernelGGL((iqbb_i16_mfmag_kernel<S_, false, false>), grid3, block, lds_bytes, ctx->stream, a); } while (0)
+        switch (S) {   // (17 K steps beyond 64 KB of LDS: the limit is raised at create)
+          case 2: SDRHIP_MFG(2); break;
+          case 3: SDRHIP_MFG(3); break;
+          case 5: SDRHIP_MFG(5); break;
+          case 9: SDRHIP_MFG(9); break;
+          default: SDRHIP_MFG(17); break;
+        }
+#undef SDRHIP_MFG
+        break;
+      }
+      case SHORT_MFMA_DMA: {
+        // complex<int16> input, calls too short for the hot kernel (or SDRHIP_IQBB_HOT=0): the general kernel, raw tiles
+        // by LDS-DMA (LDS: table | one plane pair | raw tile | tap fragments)
+        const size_t PLWd = (2 * (size_t)(TI + OP) + 64 + 31) / 32 * 8, quads = (TI + OP + 4) / 4;
+        const size_t ldsd = (256 + 2 * PLWd + 4 * ((quads + 63) / 64 * 64)) * 4 + (size_t)S * 2 * 64 * 16;
+#define SDRHIP_MFD(S_) do { if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfma_dma_kernel<S_, true>), grid, block, ldsd, ctx->stream, a); \
+                             else hipLaunchKernelGGL((iqbb_i16_mfma_dma_kernel<S_, false>), grid, block, ldsd, ctx->stream, a); } while (0)
+        switch (S) {
+          case 2: SDRHIP_MFD(2); break;
+          case 3: SDRHIP_MFD(3); break;
+          case 5: SDRHIP_MFD(5); break;
+          case 9: SDRHIP_MFD(9); break;
+          default: SDRHIP_MFD(17); break;
+        }
+#undef SDRHIP_MFD
+        break;
+      }
+      case SHORT_MFMA_CU8: {
+        // complex<uint8> input, calls too short for the hot kernel: the one-plane general kernel (its LDS: two single planes
+        // instead of two pairs)
+        const size_t lds1 = lds_bytes - 2 * (((2 * (size_t)(TI + OP) + 64 + 31) / 32 * 8) * 4);
+#define SDRHIP_MF(S_) do { if (inc != 0) hipLaunchKernelGGL((iqbb_i16_mfma_kernel<S_, true, true>), grid, block, lds1, ctx->stream, a); \
+                            else hipLaunchKernelGGL((iqbb_i16_mfma_kernel<S_, false, true>), grid, block, lds1, ctx->stream, a); } while (0)
+        switch (S) {
+          case 2: SDRHIP_MF(2); break;
+          case 3: SDRHIP_MF(3); break;
+          case 5: SDRHIP_MF(5); break;
+          case 9: SDRHIP_MF(9); break;
+          default: SDRHIP_MF(17); break;
+        }
+#undef SDRHIP_MF
+        break;
+      }
+      default:   // the VALU kernel
+        if (fast8 && real) hipLaunchKernelGGL((iqbb_i16_kernel<true, true>), grid, block, lds_bytes, ctx->stream, a);
+        else if (fast8) hipLaunchKernelGGL((iqbb_i16_kernel<true, false>), grid, block, lds_bytes, ctx->stream, a);
+        else if (real) hipLaunchKernelGGL((iqbb_i16_kernel<false, true>), grid, block, lds_bytes, ctx->stream, a);
+        else hipLaunchKernelGGL((iqbb_i16_kernel<false, false>), grid, block, lds_bytes, ctx->stream, a);
+        break;
+    }
+  }
+
   IqbbArgs last_args{};   // the argument block of the last launch (launch_multi's fix-up reads the same call)
   int last_multi_left = -1;   // buffer boundaries the last one-launch multi call left to iqbb_fm_multi_fixup_kernel (-1: none made yet)
   std::vector<int> mb_q;  // launch_multi -> launch: the long call's output indices of the buffers' first elements; on return: those no
@@ -1384,12 +1401,7 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
     const int CG = beyond ? 1 + ovl : TI / decim;   // (beyond: a placeholder — no general kernel ever runs such a plan)
     SDRHIP_REQUIRE(!beyond || (!real && !i8 && order <= 257 && decim <= 32768), SDRHIP_E_UNSUPPORTED,
                    "decim %d too large (max %d; complex<int16> / complex<uint8> plans of up to 257 taps: 32768)", decim, TI / (1 + ovl));
-    for (int i = 0; i < 2 * order; i++) {
-      if (real) SDRHIP_REQUIRE(taps[i] > -(1 << 23) && taps[i] < (1 << 23), SDRHIP_E_UNSUPPORTED,
-                               "tap %d = %d exceeds 24 bits", i / 2, taps[i]);
-      else SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED,
-                          "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
-    }
+    const bool planes = check_taps(taps, order, real, false);   // (the tap high bytes fit int8: the matrix formulations)
     for (int i = 0; i < 256; i++)
       SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
     ctx->use();
@@ -1405,10 +1417,7 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       const int mfma_max_order = h->use_hot ? 513 : 257;
       // (IQBaseBand<int8_t>: hot forms only, up to 129 taps, decimation 8 and 9 ... 512)
       const bool i8_hot = i8 && h->use_hot && order <= 129;
-      bool mfma_ok = !real && (!i8 || i8_hot) && (decim == R) && (order <= mfma_max_order);
-      auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
-      for (int i = 0; i < 2 * order && mfma_ok; i++)   // both v and -v are packed (Kr, -Ki / Ki, Kr)
-        if (high_byte(taps[i]) > 127 || high_byte(-taps[i]) > 127) mfma_ok = false;
+      bool mfma_ok = !real && (!i8 || i8_hot) && (decim == R) && (order <= mfma_max_order) && planes;
       { const char *e = getenv("SDRHIP_IQBB_TPW"); if (e) h->env_tpw = std::max(1, atoi(e)); }
       { const char *e = getenv("SDRHIP_IQBB_WGPCU"); if (e) h->env_wgpcu = std::max(1, atoi(e)); }
       { const char *e = getenv("SDRHIP_IQBB_FM_RESIDENT"); if (e) h->env_fm_resident = atoi(e) != 0; }
@@ -1418,9 +1427,7 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       if (force && !strcmp(force, "valu")) mfma_ok = false;
       h->path = mfma_ok ? 1 : 0;
       // path 3: the same matrix part for any decimation (measured ahead of the VALU kernel at every order tried, 9 ... 257 taps)
-      bool mfmag_ok = !real && (!i8 || (i8_hot && decim >= 9 && decim <= 512)) && decim != R && order <= mfma_max_order && (order <= 257 || decim >= 9);   // (the 33-step class has no small-decimation form)
-      for (int i = 0; i < 2 * order && mfmag_ok; i++)
-        if (high_byte(taps[i]) > 127 || high_byte(-taps[i]) > 127) mfmag_ok = false;
+      bool mfmag_ok = !real && (!i8 || (i8_hot && decim >= 9 && decim <= 512)) && decim != R && order <= mfma_max_order && (order <= 257 || decim >= 9) && planes;   // (the 33-step class has no small-decimation form)
       if (force && !strcmp(force, "valu")) mfmag_ok = false;
       if (h->path == 0 && mfmag_ok) h->path = 3;
       SDRHIP_REQUIRE(!beyond || (h->path == 3 && h->use_hot), SDRHIP_E_UNSUPPORTED,
@@ -1430,11 +1437,8 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       // path 4: real input on the matrix cores — D == 8, at most 9 K steps, taps that fit two byte planes
       // ... at decimation 8 the lane-owned-group kernel; at any other up to 512 the hot kernel's any-D forms for the long calls
       // and the VALU kernel for the short ones (src/baseband.hh:305-529: any sub_sample)
-      if (real && !i8 && (decim == R || (decim <= 512 && h->use_hot)) && order <= 273 && !(force && !strcmp(force, "valu"))) {
-        bool fits = true;
-        for (int i = 0; i < 2 * order && fits; i++) if (high_byte(taps[i]) > 127 || high_byte(-taps[i]) > 127) fits = false;   // (the rule set_taps applies)
-        if (fits) h->path = 4;
-      }
+      if (real && !i8 && (decim == R || (decim <= 512 && h->use_hot)) && order <= 273 && !(force && !strcmp(force, "valu")) && planes)
+        h->path = 4;   // (planes: the rule set_taps applies)
       if (h->path == 4) {
         h->S = order <= 81 ? 3 : order <= 145 ? 5 : 9;   // the hot kernel's filter-length classes (K steps of 32 real samples)
         h->OP = decim == R ? 32 * h->S - 15 : (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;   // (other decimations: the VALU kernel's tap chunks)
@@ -1451,8 +1455,7 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       if (h->path == 1 || (h->path == 4 && decim == R)) { h->OG = 4 * (64 - ovl); h->CG = h->OG + ovl; }   // every wave recomputes its own FM overlap group
       h->fast8 = (decim == R);
       if ((h->path == 4 && decim != R) || h->long_filter()) {   // (the VALU kernel's: it runs this plan's short calls)
-        const size_t XS = TI + h->OP + 8;
-        h->lds_bytes = (XS + 256 + 2 * (((size_t)h->CG + 3) & ~(size_t)3)) * 4 + (h->fast8 ? 0 : (size_t)TI * 8);
+        h->lds_bytes = h->valu_lds();
       } else if (h->path == 4) {
         h->lds_bytes = 1024 + (size_t)h->S * 2 * 64 * 16 + 4 * 2 * (size_t)(512 + 32 * h->S);
       } else if (h->path == 3) {
@@ -1462,17 +1465,19 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
         // kernel's dynamic-LDS limit; beyond that: back to the VALU kernel)
         if (h->lds_bytes > 80 * 1024) {
           h->path = 0; h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC; h->HH = h->OP;
-          const size_t XS = TI + h->OP + 8;
-          h->lds_bytes = (XS + 256 + 2 * ((CG + 3) & ~3)) * 4 + (h->fast8 ? 0 : (size_t)TI * 8);
+          h->lds_bytes = h->valu_lds();
         }
       } else if (h->path == 1) {
         const size_t PLW = (2 * (size_t)(TI + h->OP) + 64 + 31) / 32 * 8;
         h->lds_bytes = (4 * PLW + 256) * 4 + (size_t)h->S * 2 * 64 * 16;
       } else {
-        const size_t XS = TI + h->OP + 8;
-        h->lds_bytes = (XS + 256 + 2 * ((CG + 3) & ~3)) * 4 + (h->fast8 ? 0 : (size_t)TI * 8);
+        h->lds_bytes = h->valu_lds();
       }
       SDRHIP_REQUIRE(h->lds_bytes <= (h->path == 3 ? 80 : 64) * 1024, SDRHIP_E_UNSUPPORTED, "LDS budget exceeded (%zu B)", h->lds_bytes);
+      if (h->path == 3 && h->lds_bytes > 64 * 1024) {   // (17 K steps, small decimations: the general kernel's limit, once per kernel and device)
+        allow_lds_max(&iqbb_i16_mfmag_kernel<17, true, true>, h->lds_bytes); allow_lds_max(&iqbb_i16_mfmag_kernel<17, false, true>, h->lds_bytes);
+        allow_lds_max(&iqbb_i16_mfmag_kernel<17, true, false>, h->lds_bytes); allow_lds_max(&iqbb_i16_mfmag_kernel<17, false, false>, h->lds_bytes);
+      }
       h->load_taps(taps);
       h->lut.alloc(128); h->lut.upload(reinterpret_cast<const int2 *>(lut), 128, ctx->stream);
       for (int p = 0; p < 2; p++) {
@@ -1569,25 +1574,7 @@ int sdrhip_iqbb_i16_plan_info(sdrhip_iqbb_i16 *h, int *info, int n) {
 int sdrhip_iqbb_i16_kernel_names(sdrhip_iqbb_i16 *h, char *buf, size_t len) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    const char *nm = "iqbb_i16_kernel";
-    if (h->real_anyd() && !h->anyd_plan()) nm = "iqbb_i16_kernel";
-    else if (h->real_anyd()) {   // (calls of a few tiles: the VALU kernel)
-      nm = h->D < 8 ? "iqbb_hot_sd_kernel" : "iqbb_hot_anyd_kernel";
-      if (h->epi == SDRHIP_EPI_FM && !h->channel_units()) nm = h->D < 8 ? "iqbb_hot_sd_kernel,iqbb_fm_fixup_kernel" : "iqbb_hot_anyd_kernel,iqbb_fm_fixup_kernel";
-    }
-    else if (h->path == 4 && h->use_hot && h->hot_range >= 0) nm = "iqbb_hot_kernel";   // (calls of < 3 tiles: the general kernel)
-    else if (h->path == 4) nm = "bb_real_mfma_kernel";
-    else if (h->path == 3 && h->bigd_plan()) nm = h->channel_units() ? "iqbb_hot_anyd_kernel" : "iqbb_hot_anyd_kernel,iqbb_bigd_finish_kernel";   // (calls of a few tiles: the general kernel)
-    else if (h->path == 3 && h->anyd_plan()) {   // (calls of a few tiles: the general kernel "iqbb_i16_mfmag_kernel")
-      nm = h->D < 8 ? "iqbb_hot_sd_kernel" : "iqbb_hot_anyd_kernel";
-      if (h->epi == SDRHIP_EPI_FM && !h->channel_units() && (h->env_fm_handshake != 1 || !h->hs.p))
-        nm = h->D < 8 ? "iqbb_hot_sd_kernel,iqbb_fm_fixup_kernel" : "iqbb_hot_anyd_kernel,iqbb_fm_fixup_kernel";
-    }
-    else if (h->path == 3) nm = "iqbb_i16_mfmag_kernel";
-    else if (h->path == 1 && h->use_hot && h->hot_range >= 0) nm = "iqbb_hot_kernel";   // (calls of < 3 tiles: the general kernel)
-    else if (h->path == 1 && h->in_cu8) nm = "iqbb_i16_mfma_kernel";
-    else if (h->path == 1) nm = "iqbb_i16_mfma_dma_kernel";
-    snprintf(buf, len, "%s", nm);
+    snprintf(buf, len, "%s", h->call_kernel_names().c_str());
   });
 }
 
@@ -1741,14 +1728,7 @@ int sdrhip_iqbb_i16_adopt_state(sdrhip_iqbb_i16 *h, sdrhip_iqbb_i16 *from, int w
 int sdrhip_iqbb_i16_set_taps(sdrhip_iqbb_i16 *h, const int32_t *taps) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
-    auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
-    for (int i = 0; i < 2 * h->order; i++) {
-      if (h->real) SDRHIP_REQUIRE(taps[i] > -(1 << 23) && taps[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "tap %d = %d exceeds 24 bits", i / 2, taps[i]);
-      else SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
-      if (h->path >= 1)
-        SDRHIP_REQUIRE(high_byte(taps[i]) <= 127 && high_byte(-taps[i]) <= 127, SDRHIP_E_UNSUPPORTED,
-                       "tap %d = %d does not fit the plan's int8 byte planes: create a new plan", i / 2, taps[i]);
-    }
+    check_taps(taps, h->order, h->real, h->path >= 1);
     h->ctx->use();
     h->load_taps(taps);   // stream-ordered after the launches already enqueued
   });
