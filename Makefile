@@ -7,7 +7,7 @@ test-cpu: build   ## oracle vs golden vectors, C++ core, ABI, 2-rank gloo — no
 test-gpu: build   ## parity through the C ABI on an MI355X
 	python -m pytest tests -q -m gpu
 bench: build      ## one JSON line: Msamples/s, roofline, cpu_baseline
-	python bench.py
+	python bench.py --full
 golden:           ## re-cut tests/golden/ from the compiled reference (build container only)
 	$(MAKE) -C oracle ref golden
 clean:

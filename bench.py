@@ -14,16 +14,21 @@ on rank 0 inside the timed region — from a double-buffered output, on a side s
 preallocated [N * channels, n_out] tensor (`roofline.without_gather_*` = the same steps without the gather).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload iqbb_fm|iqbb_usb|iqbb_fm_cu8|bb_real_fm|fir255_fm|
-                     fir127_fm|fbb_f32|fftconv|fftbank|fm_demod|subsample8|iqbb_fm_cs8] [--order 127] [--no-verify]
+                     fir127_fm|fbb_f32|fftconv|fftbank|fm_demod|subsample8|iqbb_fm_cs8] [--order 127] [--full [--no-verify]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement). A plain run does what that line's headline needs and no
+more: set-up, pre-conditioning, W warm-up steps, the K timed steps, --dump-output(s), and the line, whose
   "roofline":     achieved algorithmic HBM bytes/s of the dominant kernel vs 8 TB/s, from HIP events
                   recorded on the stream the kernel runs on; `traffic` = PMC bytes of THIS workload's committed profile;
+is priced from those same steps. `--full` adds whatever takes runs or checks of its own:
+  "verified":     the LAST timed step's output of 32 randomly chosen channels compared with the CPU oracle (outside the
+                  timed region): bit-exact for the int16 paths, max|y - ref| / max|ref| <= 1e-5 for float / FFT;
   "cpu_baseline": the reference CPU path (oracle/_ref/ref_driver, the unmodified reference compiled
                   here) or the oracle port, timed on this box's host cores on a bounded sample;
-  "verified":     the LAST timed step's output of 32 randomly chosen channels compared with the CPU oracle (outside the
-                  timed region): bit-exact for the int16 paths, max|y - ref| / max|ref| <= 1e-5 for float / FFT.
+  "configs":      the other BASELINE configs (default one-GPU run), each timed, checked and priced to the same recipe;
+  and in "roofline" the HBM stream-read figure, the clock and power held over the steps, and with a gather the same
+  steps without it and the gather alone.
 """
 import argparse
 import json
@@ -65,6 +70,9 @@ def parse():
                    help="iqbb_* / bb_real_fm workloads: this many reference-sized buffers of --samples per channel in ONE launch "
                         "(sdrhip_iqbb_i16_process_dev_multi: the buffer boundaries kept); a step is then --buffers buffers per channel")
     p.add_argument("--batches", type=int, default=3, help="distinct input batches rotated through (defeats the 256 MiB L3)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need (oracle check, CPU baselines, the other BASELINE "
+                        "configs, stream-read, telemetry, the gather alone / without the gather); the --no-* options below trim it")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for single-GPU dry runs)")
     p.add_argument("--force-device", type=int, default=-1, help="dry runs only: put every rank on this device")
@@ -75,7 +83,7 @@ def parse():
                    help="BEFORE the warm-up and the timed steps: this many seconds of back-to-back launches, so that the timed region "
                         "starts at the clock the chip holds under this load; also the sustained figure (0 = skip)")
     p.add_argument("--no-configs", action="store_true",
-                   help="default one-GPU run: do not append the other BASELINE configs (2, 3, 4 i/ii, 5 at G=1, the sdr_fm plan) as \"configs\"")
+                   help="default one-GPU --full run: do not append the other BASELINE configs (2, 3, 4 i/ii, 5 at G=1, the sdr_fm plan) as \"configs\"")
     p.add_argument("--configs-max-channels", type=int, default=0, help="tests: cap the channel count of every entry of \"configs\"")
     p.add_argument("--config-sustain-seconds", type=float, default=0.4, help="pre-conditioning per entry of \"configs\"")
     p.add_argument("--config-cpu-seconds", type=float, default=2.5, help="CPU-baseline sample per entry of \"configs\"")
@@ -1195,7 +1203,7 @@ def run(a):
             step(False)
         if a.sustain_seconds > 0:
             chunk = max(K, 20)
-            if rank == 0:
+            if rank == 0 and a.full:
                 try:   # the device's sysfs directory by its PCI address (domain:bus:device.function)
                     pr = torch.cuda.get_device_properties(local)
                     tele = Telemetry("%04x:%02x:%02x.0" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id))
@@ -1228,7 +1236,7 @@ def run(a):
         if tele is not None:
             telemetry = tele.stop()   # (stopped only now: nothing but launches between the pre-conditioning and the timed region)
         # ---- verification (outside the timed region): the LAST timed step's output of a few channels vs the CPU oracle ----
-        verified = verify_last(a, w, it[0], rank, np, torch) if K + W >= 2 else None
+        verified = verify_last(a, w, it[0], rank, np, torch) if a.full and K + W >= 2 else None
         if a.dump_output and rank == 0:
             torch.cuda.synchronize()
             np.save(a.dump_output, (gathered if gathered is not None else w.outs[(it[0] - 1) & 1]).cpu().numpy())
@@ -1238,17 +1246,17 @@ def run(a):
                          0 if gathered is not None else getattr(w, "out_rows_axis", 0))
 
         # the same K steps without the gather (the per-GPU kernel alone) and the gather alone (no kernel), reported
-        # beside the headline of a gathered run
+        # beside the headline of a gathered --full run
         no_gather, gather_only = None, None
-        if gather:
+        if gather and a.full:
             wl_, dm_ = timed(K, False)
             no_gather = {"wall": wl_, "dev_ms": dm_}
             wl_, dm_ = timed(K, True, compute=False)
             gather_only = {"wall": wl_}
 
-        # ---- the other BASELINE configs, each to the same recipe (one GPU, default run only) ----
+        # ---- the other BASELINE configs, each to the same recipe (one GPU, default --full run only) ----
         configs, details = None, None
-        if world == 1 and not use_dist and not a.workload and not a.no_configs and not a.global_channels and a.buffers == 1:
+        if a.full and world == 1 and not use_dist and not a.workload and not a.no_configs and not a.global_channels and a.buffers == 1:
             w.node.close()
             w.ins = w.outs = None
             torch.cuda.empty_cache()
@@ -1327,18 +1335,19 @@ def run(a):
             if wall * 1e3 < 20.0:   # a timed region this short: the same metric over the pre-conditioning launches beside it
                 res["value_sustained"] = round(C * N * world / (sustained["ms_per_launch"] / 1e3) / 1e6, 2)
                 res["value_sustained_note"] = "timed region %.1f ms < 20 ms: the same metric over the %.0f s of pre-conditioning launches" % (wall * 1e3, a.sustain_seconds)
-        try:   # what this box's HBM delivers to a pure read of the same buffers, beside the nominal peak
-            import ctypes
-            gbs = ctypes.c_double(0.0)
-            buf = torch.ones(1 << 28, dtype=torch.int32, device=dev)   # 1 GiB: four times the 256 MiB Infinity Cache
-            rc = sa.abi.lib().sdrhip_bench_stream_read(ctx.handle, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
-                                                       5, ctypes.byref(gbs))
-            del buf
-            if rc == 0 and gbs.value > 0:
-                res["roofline"]["stream_read_gbs"] = round(gbs.value, 1)
-                res["roofline"]["frac_of_stream_read"] = round(achieved / gbs.value, 5)
-        except Exception as e:   # measurement aid only
-            res["roofline"]["stream_read_error"] = str(e)[:80]
+        if a.full:
+            try:   # what this box's HBM delivers to a pure read of the same buffers, beside the nominal peak
+                import ctypes
+                gbs = ctypes.c_double(0.0)
+                buf = torch.ones(1 << 28, dtype=torch.int32, device=dev)   # 1 GiB: four times the 256 MiB Infinity Cache
+                rc = sa.abi.lib().sdrhip_bench_stream_read(ctx.handle, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
+                                                           5, ctypes.byref(gbs))
+                del buf
+                if rc == 0 and gbs.value > 0:
+                    res["roofline"]["stream_read_gbs"] = round(gbs.value, 1)
+                    res["roofline"]["frac_of_stream_read"] = round(achieved / gbs.value, 5)
+            except Exception as e:   # measurement aid only
+                res["roofline"]["stream_read_error"] = str(e)[:80]
         if wl == "fbb_f32" and C == 1:   # BASELINE config 2: one channel — what a buffer costs, and against real time
             res["roofline"]["per_buffer_us"] = round(per_launch_s * 1e6, 2)
             res["roofline"]["real_time_factor"] = round((N / FS) / per_launch_s, 1)
@@ -1356,7 +1365,7 @@ def run(a):
     if rank == 0:
         # the CPU baselines run once the GPU work is over and the process group is gone (the other ranks have left: the
         # host cores are idle), on rank 0, for every N
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             cb = cpu_baseline(wl, a.cpu_seconds)
             if cb:
                 res["cpu_baseline"] = cb
@@ -1496,7 +1505,7 @@ def run_sdrhip(a):
         step(True)
     wall, ms = timed(K, True)
     verified = None
-    if K + W >= 2 and not a.no_verify:
+    if a.full and K + W >= 2 and not a.no_verify:
         oks = []
         for r in range(G):
             torch.cuda.set_device(devices[r])
@@ -1515,8 +1524,9 @@ def run_sdrhip(a):
     if a.dump_outputs:
         torch.cuda.set_device(devices[0])
         dump_outputs(a.dump_outputs, wl, gathered, w0.delivered(got[0]))
-    wall_ng, ms_ng = timed(K, False)
-    wall_go, _ = timed(K, True, compute=False)
+    if a.full:   # the same steps without the gather (the kernels alone), and the gather alone (no kernel)
+        wall_ng, ms_ng = timed(K, False)
+        wall_go, _ = timed(K, True, compute=False)
     alg, inb = w0.alg_bytes, w0.in_bytes
     per_launch_s = ms[0] / 1e3 / K
     total = float(C) * N * K * G
@@ -1534,12 +1544,14 @@ def run_sdrhip(a):
                         "kernels_per_step": w0.kernels, "algorithmic_bytes_per_sample": alg,
                         "avg_launch_ms": round(ms[0] / K, 4), "avg_launch_ms_min_rank": round(min(ms) / K, 4), "avg_launch_ms_max_rank": round(max(ms) / K, 4),
                         "avg_launch_note": "HIP events on each rank's stream around the K steps; the gather runs on the comm's own streams (sdrhip_comm_gather_begin / _wait), double-buffered",
-                        "ranks_seen": G,
-                        "with_gather_msamples_s": round(total / wall / 1e6, 2), "without_gather_msamples_s": round(total / wall_ng / 1e6, 2),
-                        "without_gather_ms_per_step": round(wall_ng / K * 1e3, 4), "without_gather_avg_launch_ms": round(ms_ng[0] / K, 4),
-                        "gather_bytes_per_step": gb, "gather_remote_bytes_per_step": gb_remote,
-                        "gather_only_ms_per_step": round(wall_go / K * 1e3, 4), "gather_gbs": round(gb / (wall_go / K) / 1e9, 2),
-                        "gather_remote_gbs": round(gb_remote / (wall_go / K) / 1e9, 2), "gather_gbs_in_step": round(gb / (wall / K) / 1e9, 2)}}
+                        "ranks_seen": G}}
+    if a.full:
+        res["roofline"].update({
+            "with_gather_msamples_s": round(total / wall / 1e6, 2), "without_gather_msamples_s": round(total / wall_ng / 1e6, 2),
+            "without_gather_ms_per_step": round(wall_ng / K * 1e3, 4), "without_gather_avg_launch_ms": round(ms_ng[0] / K, 4),
+            "gather_bytes_per_step": gb, "gather_remote_bytes_per_step": gb_remote,
+            "gather_only_ms_per_step": round(wall_go / K * 1e3, 4), "gather_gbs": round(gb / (wall_go / K) / 1e9, 2),
+            "gather_remote_gbs": round(gb_remote / (wall_go / K) / 1e9, 2), "gather_gbs_in_step": round(gb / (wall / K) / 1e9, 2)})
     if sustained:
         res["roofline"]["sustained_ms_per_launch"] = round(sustained, 4)
     if verified is not None:
@@ -1548,7 +1560,7 @@ def run_sdrhip(a):
         w.node.close()
     del timers
     comm.close()
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         cb = cpu_baseline(wl, a.cpu_seconds)
         if cb:
             res["cpu_baseline"] = cb

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -31,6 +31,21 @@ def test_bench_json_contract():
     assert rf["compute"]["unit"] == "TOPS int8 MFMA" and 0 < rf["compute"]["frac"] < 1 and rf["compute"]["mfma_per_slice"] == 28
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] == 1 and cb["value"] > 0 and "sample" in cb
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone():
+    """Without --full a run sets up, warms up, times its steps and prints the headline line: no oracle check, CPU baseline,
+    other BASELINE configs, stream-read figure or telemetry (--full adds each of them)."""
+    d = _bench(["--steps", "3", "--warmup", "1", "--sustain-seconds", "0.2"])
+    assert d["value"] > 0 and d["unit"] == "Msamples/s" and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "i16"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["metric"].startswith("Msamples/s")
+    rf = d["roofline"]
+    assert rf["kernel"] == "iqbb_hot_kernel" and 0 < rf["frac"] < 1 and rf["sustained_ms_per_launch"] > 0
+    for k in ("verified", "verify", "cpu_baseline", "configs"):
+        assert k not in d, k
+    for k in ("stream_read_gbs", "stream_read_error", "telemetry", "sclk_mhz", "without_gather_msamples_s"):
+        assert k not in rf, k
 
 
 def _error_line(r):
@@ -87,7 +102,7 @@ def test_bench_gpus_flag_spawns_ranks_without_gpu():
 def test_bench_strong_scaling_line():
     """--global-channels G: the job is fixed (BASELINE config 5's 8192 channels), a rank takes G / N of them, the line
     says `"scaling": "strong"` and counts G channels."""
-    d = _bench(["--global-channels", "64", "--samples", "16384", "--steps", "3", "--warmup", "1", "--sustain-seconds", "0", "--no-cpu-baseline"])
+    d = _bench(["--full", "--global-channels", "64", "--samples", "16384", "--steps", "3", "--warmup", "1", "--sustain-seconds", "0", "--no-cpu-baseline"])
     assert d["scaling"] == "strong" and d["config"]["global_channels"] == 64 and d["config"]["channels_per_gpu"] == 64
     assert d["verified"] is True
 
@@ -96,7 +111,7 @@ def test_bench_strong_scaling_line():
 def test_bench_line_carries_clock_and_power_when_the_box_exposes_them():
     """roofline.sclk_mhz / power_w: averaged over the sustained phase from amdgpu's sysfs files by a side thread (keys
     present whenever telemetry was readable; values plausible)."""
-    d = _bench(["--steps", "20", "--warmup", "5", "--sustain-seconds", "1", "--no-cpu-baseline", "--no-verify"])
+    d = _bench(["--full", "--steps", "20", "--warmup", "5", "--sustain-seconds", "1", "--no-cpu-baseline", "--no-verify"])
     rf = d["roofline"]
     if "telemetry" not in rf:
         pytest.skip("no readable amdgpu hwmon files on this box")
@@ -152,7 +167,8 @@ def test_multi_rank_preflight_through_the_real_launcher(tmp_path):
     count itself runs in one process: test_eight_rank_contexts_through_the_c_abi.)"""
     import numpy as np
     G = PREFLIGHT_RANKS
-    common = ["--samples", "16384", "--steps", "3", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--sustain-seconds", "0", "--verify-channels", "2"]
+    common = ["--full", "--samples", "16384", "--steps", "3", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--sustain-seconds", "0",
+              "--verify-channels", "2"]
     many, one = str(tmp_path / "many.npy"), str(tmp_path / "one.npy")
     dg = _bench(["--gpus", str(G), "--backend", "gloo", "--force-device", "0", "--global-channels", "8192", "--dump-output", many] + common, timeout=1500)
     assert dg["n_gpus"] == G and dg["scaling"] == "strong" and dg["config"]["global_channels"] == 8192 and dg["config"]["channels_per_gpu"] == 8192 // G
@@ -170,7 +186,8 @@ def test_eight_rank_contexts_through_the_c_abi(tmp_path):
     """The same job through `--comm sdrhip`: ONE process, 8 rank contexts from sdrhip_comm_create (all on device 0: the
     library's same-device transport), design broadcast, the overlapped sdrhip_comm_gather_begin / _wait every step."""
     import numpy as np
-    common = ["--samples", "16384", "--steps", "3", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--sustain-seconds", "0", "--verify-channels", "2"]
+    common = ["--full", "--samples", "16384", "--steps", "3", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--sustain-seconds", "0",
+              "--verify-channels", "2"]
     eight, one = str(tmp_path / "eight.npy"), str(tmp_path / "one.npy")
     d8 = _bench(["--comm", "sdrhip", "--gpus", "8", "--force-device", "0", "--global-channels", "8192", "--dump-output", eight] + common, timeout=1500)
     assert d8["ranks"] == 8 and d8["roofline"]["ranks_seen"] == 8 and d8["verified"] is True and d8["verify"]["gathered_equals_rank_rows"] is True
@@ -201,7 +218,7 @@ def test_every_workload_emits_its_line_and_verifies(workload):
     """Every `--workload` (the BASELINE configurations and the stand-alone kernels) runs on a small batch, prints one JSON
     line whose roofline names the kernel it timed, and the LAST timed step's output of the sampled channels equals the
     CPU oracle's (bit-exact for int16, <= 1e-5 for float / FFT): `verified` ties the number to the work."""
-    d = _bench(["--workload", workload, "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2",
+    d = _bench(["--full", "--workload", workload, "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2",
                 "--no-cpu-baseline", "--sustain-seconds", "0", "--verify-channels", "4"])
     assert d["value"] > 0 and d["config"]["workload"] and d["roofline"]["kernel"] and 0 < d["roofline"]["frac"] < 1
     assert d["verified"] is True, d.get("verify")
@@ -211,14 +228,14 @@ def test_every_workload_emits_its_line_and_verifies(workload):
 
 @pytest.mark.gpu
 def test_short_timed_region_reports_the_sustained_value():
-    d = _bench(["--channels", "64", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--sustain-seconds", "0.3", "--verify-channels", "2"])
+    d = _bench(["--full", "--channels", "64", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--sustain-seconds", "0.3", "--verify-channels", "2"])
     assert d["verified"] is True and d["value_sustained"] > 0 and d["roofline"]["sustained_frac"] > 0
 
 
 @pytest.mark.gpu
 def test_config2_single_channel_latency_line():
     """BASELINE config 2 as SURVEY §8d states it: one complex<float> channel, per-buffer latency beside Msamples/s."""
-    d = _bench(["--workload", "fbb_f32", "--channels", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--sustain-seconds", "0"])
+    d = _bench(["--full", "--workload", "fbb_f32", "--channels", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--sustain-seconds", "0"])
     assert d["verified"] is True and d["roofline"]["per_buffer_us"] > 0 and d["roofline"]["real_time_factor"] > 1
 
 
@@ -242,7 +259,7 @@ def test_rccl_gather_path_runs_on_one_rank(tmp_path):
     int16 rows landing in one preallocated tensor — on a ONE-rank RCCL group (a one-GPU box cannot hold two RCCL ranks): the
     gathered rows must equal the plain single-process run, and the line must carry both rates."""
     import numpy as np
-    common = ["--workload", "iqbb_usb", "--channels", "16", "--samples", "32768", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    common = ["--full", "--workload", "iqbb_usb", "--channels", "16", "--samples", "32768", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
               "--sustain-seconds", "0", "--verify-channels", "4"]
     one, two = str(tmp_path / "plain.npy"), str(tmp_path / "rccl.npy")
     d1 = _bench(common + ["--dump-output", one])
@@ -256,10 +273,10 @@ def test_rccl_gather_path_runs_on_one_rank(tmp_path):
 
 @pytest.mark.gpu
 def test_default_line_carries_every_baseline_config():
-    """The default one-GPU line (what the driver runs) appends BASELINE configs 2, 3, 4 (i)/(ii), 5 at G = 1 and the
+    """The default one-GPU --full line appends BASELINE configs 2, 3, 4 (i)/(ii), 5 at G = 1 and the
     reference's own sdr_fm plan as "configs": each entry timed to the same recipe, checked against the oracle on its last
     step, with its roofline and the reference CPU chain beside it. (Channel counts capped here; the driver's run is full size.)"""
-    d = _bench(["--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2", "--sustain-seconds", "0.2",
+    d = _bench(["--full", "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2", "--sustain-seconds", "0.2",
                 "--config-sustain-seconds", "0.05", "--cpu-seconds", "0.5", "--config-cpu-seconds", "0.3", "--configs-max-channels", "16",
                 "--verify-channels", "4"])
     assert d["verified"] is True and d["preconditioned_s"] >= 0.2 and d["roofline"]["sustained_ms_per_launch"] > 0
@@ -296,7 +313,7 @@ def test_comm_sdrhip_ranks_on_one_device_match_single_rank(tmp_path, workload):
     sdrhip_comm_broadcast, sdrhip_comm_gather every step. The gathered rows equal the single-rank run over the same
     global channels bit for bit."""
     import numpy as np
-    common = ["--workload", workload, "--samples", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0"]
+    common = ["--full", "--workload", workload, "--samples", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0"]
     one = str(tmp_path / "one.npy")
     d1 = _bench(["--gpus", "1", "--channels", "16", "--dump-output", one] + common)
     b = np.load(one)
@@ -317,7 +334,7 @@ def test_comm_sdrhip_ranks_on_one_device_match_single_rank(tmp_path, workload):
 def test_dist_line_reports_the_gather_and_the_ranks_it_counted():
     """The N > 1 line's extra keys, visible on a one-rank RCCL group: bytes and GB/s of the gather (alone and inside the
     steps), per-rank launch time min / max, and `ranks_seen` counted by an all-reduce."""
-    d = _bench(["--workload", "iqbb_usb", "--channels", "16", "--samples", "32768", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    d = _bench(["--full", "--workload", "iqbb_usb", "--channels", "16", "--samples", "32768", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
                 "--sustain-seconds", "0", "--verify-channels", "4", "--force-dist", "--gather"])
     rf = d["roofline"]
     assert rf["ranks_seen"] == 1 and rf["gather_bytes_per_step"] > 0 and rf["gather_bytes_per_step"] % 32 == 0
@@ -347,7 +364,7 @@ def test_host_side_helpers_touch_no_gpu(tmp_path, monkeypatch):
 def test_multi_buffer_workloads_verify(workload, extra):
     """`--buffers 4`: four reference-sized buffers per channel in ONE launch (sdrhip_iqbb_i16_process_dev_multi); the LAST buffer of
     the last step against the oracle primed with the buffer before it — bit-exact, boundaries included."""
-    d = _bench(["--workload", workload, "--buffers", "4", "--batches", "2", "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2",
+    d = _bench(["--full", "--workload", workload, "--buffers", "4", "--batches", "2", "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2",
                 "--no-cpu-baseline", "--sustain-seconds", "0", "--verify-channels", "4"] + extra)
     assert d["verified"] is True, d.get("verify")
     assert "/B4/" in d["config"]["workload_key"] and d["config"]["samples_per_channel_per_step"] == 4 * 32768
@@ -389,7 +406,7 @@ def test_dump_outputs_repeat_run_for_run(tmp_path, workload):
     """--dump-outputs DIR: the last timed step's delivered outputs as DIR/<workload>.npy (float32), the same from run to run
     with the same arguments, however long the time-bound pre-conditioning ran — and what --dump-output saves of that step."""
     import numpy as np
-    common = ["--workload", workload, "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+    common = ["--full", "--workload", workload, "--channels", "16", "--samples", "32768", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
               "--verify-channels", "4"]
     d1 = _bench(common + ["--sustain-seconds", "0.3", "--dump-outputs", str(tmp_path / "a"), "--dump-output", str(tmp_path / "raw.npy")])
     d2 = _bench(common + ["--sustain-seconds", "0.1", "--dump-outputs", str(tmp_path / "b")])

@@ -3,7 +3,7 @@
 # costs whatever its size (dispatch gap, ramp, tail), the slope the steady rate.   usage: k1_scan_channels.sh [extra bench args]
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 for c in 256 512 1024 2048 4096 8192 1024; do
-  python bench.py --channels $c --steps 200 --warmup 50 --no-verify --no-cpu-baseline --sustain-seconds 1.5 "$@" 2>/dev/null | python -c "
+  python bench.py --full --channels $c --steps 200 --warmup 50 --no-verify --no-cpu-baseline --sustain-seconds 1.5 "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ for wl in iqbb_fm_cu8 iqbb_fm iqbb_usb; do
  for d in 2 3 4 5 6 7 8 9; do
   for hot in 1 0; do
   [ $hot = 0 ] && [ $d -ge 8 ] && continue
-  SDRHIP_IQBB_HOT=$hot python bench.py --workload $wl --order 21 --decim $d --steps 100 --warmup 20 --no-cpu-baseline --sustain-seconds 1 2>/dev/null | python -c "
+  SDRHIP_IQBB_HOT=$hot python bench.py --full --workload $wl --order 21 --decim $d --steps 100 --warmup 20 --no-cpu-baseline --sustain-seconds 1 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,9 +1,11 @@
 #!/bin/bash
 # One profiling round over every bench workload (run on the GPU box through gpurun): per workload tools/prof.sh
-# (kernel trace + the PMC passes of the same bench.py command line) under gpurun_out/prof_<round>_<name>/, and the
-# un-profiled bench.py lines in gpurun_out/<round>_bench.json (headline) and <round>_bench_other_workloads.jsonl.
-# usage: tools/prof_all.sh r09 [name ...]      then, here:  cp gpurun_out/summ/* gpurun_out/r09_bench* profiles/
+# (kernel trace + the PMC passes of the same bench.py command line) under $PROF_OUT/prof_<round>_<name>/, and the
+# un-profiled bench.py --full lines in $PROF_OUT/<round>_bench.json (headline) and <round>_bench_other_workloads.jsonl.
+# (PROF_OUT: a directory under the repository root, default prof_out)
+# usage: tools/prof_all.sh r09 [name ...]      then, here:  cp $PROF_OUT/summ/* $PROF_OUT/r09_bench* profiles/
 R=${1:-r09}; shift
+O=${PROF_OUT:-prof_out}
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 declare -A W=( [fm127]="" [fm16]="--order 16" [fm21]="--order 21" [fm64]="--order 64" [fm255]="--order 255" [usb127]="--workload iqbb_usb"
                [cu8]="--workload iqbb_fm_cu8" [real]="--workload bb_real_fm" [fir255]="--workload fir255_fm" [fbb]="--workload fbb_f32"
@@ -22,17 +24,17 @@ declare -A W=( [fm127]="" [fm16]="--order 16" [fm21]="--order 21" [fm64]="--orde
 #    # the plans of examples/sdr_fm.cc:40 and examples/sdr_rec.cc:42-68 (narrow FM: no shift, 1 MS/s to 12 kS/s)
 # (sdrfm, cfg5g1, cfg2c1, cfg1, multi4, real20: the command lines of bench.py's "configs" entries — their workload keys must match for `traffic`)
 NAMES=${@:-fm127 fm16 fm21 fm64 fm255 usb127 cu8 real fir255 fbb fftconv fftola fftbank fmdemod sub8 sdrfm cfg5g1 cfg2c1 cfg1 multi4 real5 real20 real125 o300 o513d20 sdrrec sdrfmchain wfmchain pocsag ssb sd4 sd7usb d300 d1000 o255d125}
-mkdir -p gpurun_out
-: > gpurun_out/${R}_bench_other_workloads.jsonl
+mkdir -p $O
+: > $O/${R}_bench_other_workloads.jsonl
 for n in $NAMES; do
-  if [ "$n" = fm127 ]; then python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${R}_bench.json 2> gpurun_out/${R}_bench.err   # (the driver's own command line: headline + "configs")
-  else python bench.py ${W[$n]} --cpu-seconds 3 2>/dev/null | grep '^{' >> gpurun_out/${R}_bench_other_workloads.jsonl; fi
+  if [ "$n" = fm127 ]; then python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/${R}_bench.err   # (the headline + "configs")
+  else python bench.py --full ${W[$n]} --cpu-seconds 3 2>/dev/null | grep '^{' >> $O/${R}_bench_other_workloads.jsonl; fi
 done
-python bench.py --workload fbb_f32 --channels 1 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{' >> gpurun_out/${R}_bench_other_workloads.jsonl
+python bench.py --full --workload fbb_f32 --channels 1 --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{' >> $O/${R}_bench_other_workloads.jsonl
 for n in $NAMES; do
-  tools/prof.sh ${R}_$n ${W[$n]} > gpurun_out/prof_${R}_$n.log 2>&1
-  # (the raw rocprofv3 trees are hundreds of MB: condense here, keep the summaries — they come back under gpurun_out/summ/)
-  python tools/summarize_prof.py ${R}_$n gpurun_out/summ > gpurun_out/summ_${R}_$n.log 2>&1
-  rm -rf gpurun_out/prof_${R}_$n
+  PROF_OUT=$O tools/prof.sh ${R}_$n ${W[$n]} > $O/prof_${R}_$n.log 2>&1
+  # (the raw rocprofv3 trees are hundreds of MB: condense here, keep the summaries under $O/summ/)
+  PROF_OUT=$O python tools/summarize_prof.py ${R}_$n $O/summ > $O/summ_${R}_$n.log 2>&1
+  rm -rf $O/prof_${R}_$n
 done
-du -sh gpurun_out | tail -1
+du -sh $O | tail -1

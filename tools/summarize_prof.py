@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condenses a tools/prof.sh output directory (gpurun_out/prof_<tag>) into small, committable files under
+"""Condenses a tools/prof.sh output directory ($PROF_OUT/prof_<tag>, default prof_out/) into small, committable files under
 profiles/: <tag>_kernel_stats.csv (our kernels only), <tag>_pmc.json (per-launch means per counter and
 kernel) and a derived per-launch HBM traffic figure following MI355X_MICROARCH.md §HBM
 (FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half of a streaming read -> doubled)."""
@@ -12,8 +12,8 @@ import os
 import sys
 
 tag = sys.argv[1]
-dst = sys.argv[2] if len(sys.argv) > 2 else "profiles"   # (on the GPU box: a directory under gpurun_out/, copied into profiles/ afterwards)
-src = os.path.join("gpurun_out", "prof_" + tag)
+dst = sys.argv[2] if len(sys.argv) > 2 else "profiles"   # (on the GPU box: a directory under $PROF_OUT, copied into profiles/ afterwards)
+src = os.path.join(os.environ.get("PROF_OUT", "prof_out"), "prof_" + tag)
 os.makedirs(dst, exist_ok=True)
 ours = ("iqbb", "bb_real", "fir_", "fftconv", "demod_", "deemph_", "subsample", "freqshift", "hist_roll", "fft_c2c")
 
