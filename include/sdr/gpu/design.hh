@@ -127,6 +127,21 @@ inline int fmDeemphAlpha(double sampleRate) {
   return int(round(1.0 / ((1.0 - exp(-1.0 / (sampleRate * 75e-6))))));
 }
 
+/** Correlation length of FSKDetector / BitStream: int(Fs / baud), baud a float member (reference src/fsk.cc:32,122). */
+inline int fskCorrLen(double sampleRate, float baud) { return int(sampleRate / baud); }
+
+/** One tone's LUT of FSKDetector::config (reference src/fsk.cc:39-44): corrLen x (re, im) floats, exp(complex<float>(0, phi))
+ * with phi accumulated in double from 0 and narrowed to float at the call; freq is a float member. */
+inline void fskLut(double sampleRate, float freq, int corrLen, float *lut) {
+  double phi = 0;
+  for (int i = 0; i < corrLen; i++) {
+    const std::complex<float> v = std::exp(std::complex<float>(0.0, phi));
+    lut[2 * i] = v.real();
+    lut[2 * i + 1] = v.imag();
+    phi += (2. * M_PI * freq) / sampleRate;
+  }
+}
+
 /** Time-domain kernel of the FFT filter, N complex Scalars: sinc_flt_kernel<Scalar> + FilterSource::_updateFilter's band
  * clamp (reference src/filternode.hh:18-28,186-196). The value is a complex<Scalar> from the first assignment on, so for
  * float the modulation phase is rounded to float before the exponential (a double phase is 3e-5 off). */

@@ -7,6 +7,7 @@
 //   sdr::gpu::FIRLowPass<complex<int16|float>>  <->  sdr::FIRLowPass<...>            src/firfilter.hh:117-289
 //   sdr::gpu::FMDemod<int16_t>, AMDemod<S>, USBDemod<S>  <->  same names             src/demod.hh:18-264
 //   sdr::gpu::SubSample<complex<...>>       <->  sdr::SubSample<...>                 src/subsample.hh:16-116
+//   sdr::gpu::FSKDetector, ASKDetector<int16_t>, BitStream  <->  same names          src/fsk.hh:18-171
 //   sdr::gpu::FilterSink<float|double>      <->  sdr::FilterSink<Scalar>             src/filternode.hh:32-99
 //   sdr::gpu::FilterSource<float|double>    <->  sdr::FilterSource<Scalar>           src/filternode.hh:103-227
 //   sdr::gpu::FilterNode<float|double>      <->  sdr::FilterNode<Scalar>             src/filternode.hh:230-284
@@ -732,6 +733,223 @@ protected:
   int _device;
   sdrhip_deemph *_plan;
   Buffer<int16_t> _buffer;
+};
+
+// =================================================================================================
+// audio to bits: FSKDetector, ASKDetector<int16_t>, BitStream (reference src/fsk.hh, src/fsk.cc)
+// =================================================================================================
+namespace detail {
+/** The direct hand-off of symbols between a gpu detector and a gpu::BitStream, as SpectrumHandoff below: just before a
+ * direct send the detector records {host buffer data -> device symbols}; the host buffer stays unfilled and a BitStream
+ * that receives that very buffer reads the device copy. */
+struct SymbolHandoff { const uint8_t *dev; int device; };
+inline std::map<const void *, SymbolHandoff> &symbolHandoffs() {
+  static std::map<const void *, SymbolHandoff> table;
+  return table;
+}
+inline void *symAlloc(sdrhip_ctx *c, size_t bytes, const char *what) {
+  void *p = 0;
+  configCheck(sdrhip_malloc(c, bytes, &p), what);
+  return p;
+}
+}  // namespace detail
+
+/** Drop-in for sdr::BitStream (reference src/fsk.hh:124-171, src/fsk.cc:102-202): symbols in, bits out, sent only when a
+ * buffer produced at least one (:201). The output buffer holds ceil(bufferSize * omegaMax) + 1 bits (the reference's
+ * 1 + bufferSize / corrLen can be exceeded by its own PLL); the Config forwarded says so. */
+class BitStream : public Sink<uint8_t>, public Source {
+public:
+  typedef enum { NORMAL, TRANSITION } Mode;
+  explicit BitStream(float baud, Mode mode = TRANSITION, int device = 0)
+    : _baud(baud), _mode(mode), _device(device), _plan(0), _in(0), _out(0), _counts(0), _cap(0), _onDevice(false) {}
+  virtual ~BitStream() { _release(); _buffer.unref(); }
+  virtual void config(const Config &src_cfg) {
+    if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
+    if (Config::typeId<uint8_t>() != src_cfg.type()) {
+      ConfigError err;
+      err << "Can not configure BitStream: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
+      throw err;
+    }
+    _release();   // a fresh plan: ring, PLL and bit history start over (:125-140)
+    sdrhip_ctx *c = Device::get(_device);
+    const size_t bs = std::max(size_t(1), src_cfg.bufferSize());
+    detail::configCheck(sdrhip_bits_create(c, src_cfg.sampleRate(), _baud, _mode == TRANSITION ? SDRHIP_BITS_TRANSITION : SDRHIP_BITS_NORMAL,
+                                           1, bs, &_plan), "BitStream");
+    detail::configCheck(sdrhip_bits_out_capacity(_plan, bs, &_cap), "BitStream");
+    _in = detail::symAlloc(c, bs, "BitStream");
+    _out = detail::symAlloc(c, _cap, "BitStream");
+    _counts = detail::symAlloc(c, sizeof(uint32_t), "BitStream");
+    _buffer.unref();
+    _buffer = Buffer<uint8_t>(_cap);
+    LogMessage msg(LOG_DEBUG);
+    msg << "Config BitStream node: " << std::endl
+        << " symbol rate: " << src_cfg.sampleRate() << " Hz" << std::endl
+        << " baud rate:   " << _baud << std::endl
+        << " symbols/bit: " << 1. / float(_baud / src_cfg.sampleRate()) << std::endl
+        << " bit mode:    " << ((NORMAL == _mode) ? "normal" : "transition");
+    Logger::get().log(msg);
+    this->setConfig(Config(Config::typeId<uint8_t>(), _baud, _buffer.size(), 1));   // :154
+  }
+  virtual void process(const Buffer<uint8_t> &buffer, bool) {
+    if (!_plan) return;
+    sdrhip_ctx *c = Device::get(_device);
+    const std::map<const void *, detail::SymbolHandoff> &t = detail::symbolHandoffs();
+    std::map<const void *, detail::SymbolHandoff>::const_iterator it = t.find(buffer.data());
+    _onDevice = it != t.end() && it->second.device == _device;
+    const uint8_t *sym = _onDevice ? it->second.dev : reinterpret_cast<const uint8_t *>(_in);
+    if (!_onDevice && buffer.size() &&
+        !detail::processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), buffer.size()), "gpu::BitStream")) return;
+    if (!detail::processOk(sdrhip_bits_process_dev(_plan, sym, buffer.size(), 0, reinterpret_cast<uint8_t *>(_out), _cap,
+                                                   reinterpret_cast<uint32_t *>(_counts)), "gpu::BitStream")) return;
+    uint32_t o = 0;
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, &o, _counts, sizeof(o)), "gpu::BitStream")) return;
+    if (0 == o) return;                                                              // :201
+    if (!_buffer.isUnused()) return;   // still referenced downstream: the bits of this buffer are dropped
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _out, o), "gpu::BitStream")) return;
+    this->send(_buffer.head(o));
+  }
+  /** true: the last buffer's symbols were read from a gpu detector's device memory (no host copy in between). */
+  bool lastBufferOnDevice() const { return _onDevice; }
+  int device() const { return _device; }
+
+protected:
+  void _release() {
+    if (_plan) { sdrhip_bits_destroy(_plan); _plan = 0; }
+    sdrhip_ctx *c = (_in || _out || _counts) ? Device::get(_device) : 0;
+    if (_in) { sdrhip_free(c, _in); _in = 0; }
+    if (_out) { sdrhip_free(c, _out); _out = 0; }
+    if (_counts) { sdrhip_free(c, _counts); _counts = 0; }
+  }
+  float _baud;
+  Mode _mode;
+  int _device;
+  sdrhip_bits *_plan;
+  void *_in, *_out, *_counts;
+  size_t _cap;
+  bool _onDevice;
+  Buffer<uint8_t> _buffer;
+};
+
+namespace detail {
+/** What FSKDetector and ASKDetector share: int16 in, one symbol per sample out, sent as head(n) with overwrite disallowed
+ * (reference src/fsk.cc:94, src/fsk.hh:110). When every connected sink is connected direct and is a gpu::BitStream on the
+ * same device, the symbols stay on the device and the buffer sent is left unfilled; otherwise they are copied into it. */
+class DetectorBase : public Sink<int16_t>, public Source {
+public:
+  DetectorBase(const char *name, int device) : _name(name), _device(device), _plan(0), _in(0), _sym(0), _onDevice(false) {}
+  virtual ~DetectorBase() { _release(); _buffer.unref(); }
+  virtual void process(const Buffer<int16_t> &buffer, bool) {
+    if (!_plan) return;
+    sdrhip_ctx *c = Device::get(_device);
+    const size_t n = buffer.size();
+    if (n && (!processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), n * sizeof(int16_t)), _name) ||
+              !processOk(sdrhip_detector_process_dev(_plan, reinterpret_cast<const int16_t *>(_in), n, 0,
+                                                     reinterpret_cast<uint8_t *>(_sym), 0), _name))) return;
+    _onDevice = _deviceHandoff();
+    if (!_onDevice) {
+      if (n && !processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _sym, n), _name)) return;
+      this->send(_buffer.head(n), false);
+      return;
+    }
+    const SymbolHandoff rec = {reinterpret_cast<const uint8_t *>(_sym), _device};
+    symbolHandoffs()[_buffer.data()] = rec;
+    this->send(_buffer.head(n), false);
+    symbolHandoffs().erase(_buffer.data());
+  }
+  /** true: the last buffer's symbols went to the BitStream nodes on the device (no host copy). */
+  bool lastBufferOnDevice() const { return _onDevice; }
+
+protected:
+  void _plan_(int kind, const float *mark, const float *space, int corrLen, bool invert, size_t bufferSize) {
+    _release();
+    sdrhip_ctx *c = Device::get(_device);
+    const size_t bs = std::max(size_t(1), bufferSize);
+    configCheck(sdrhip_detector_create(c, kind, mark, space, corrLen, invert ? 1 : 0, 1, bs, &_plan), _name);
+    _in = symAlloc(c, bs * sizeof(int16_t), _name);
+    _sym = symAlloc(c, bs, _name);
+    _buffer.unref();
+    _buffer = Buffer<uint8_t>(bs);
+  }
+  bool _deviceHandoff() const {
+    if (_sinks.empty()) return false;
+    for (std::map<SinkBase *, bool>::const_iterator it = _sinks.begin(); it != _sinks.end(); ++it) {
+      const gpu::BitStream *s = dynamic_cast<const gpu::BitStream *>(it->first);
+      if (!it->second || !s || s->device() != _device) return false;
+    }
+    return true;
+  }
+  void _release() {
+    if (_plan) { sdrhip_detector_destroy(_plan); _plan = 0; }
+    sdrhip_ctx *c = (_in || _sym) ? Device::get(_device) : 0;
+    if (_in) { sdrhip_free(c, _in); _in = 0; }
+    if (_sym) { sdrhip_free(c, _sym); _sym = 0; }
+  }
+  const char *_name;
+  int _device;
+  sdrhip_detector *_plan;
+  void *_in, *_sym;
+  bool _onDevice;
+  Buffer<uint8_t> _buffer;
+};
+}  // namespace detail
+
+/** Drop-in for sdr::FSKDetector (reference src/fsk.hh:18-56, src/fsk.cc:12-95). */
+class FSKDetector : public detail::DetectorBase {
+public:
+  FSKDetector(float baud, float Fmark, float Fspace, int device = 0)
+    : detail::DetectorBase("FSKDetector", device), _baud(baud), _corrLen(0), _Fmark(Fmark), _Fspace(Fspace) {}
+  virtual void config(const Config &src_cfg) {
+    if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
+    if (Config::typeId<int16_t>() != src_cfg.type()) {
+      ConfigError err;
+      err << "Can not configure FSKBase: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
+      throw err;
+    }
+    _corrLen = size_t(design::fskCorrLen(src_cfg.sampleRate(), _baud));
+    std::vector<float> mark(2 * _corrLen), space(2 * _corrLen);
+    design::fskLut(src_cfg.sampleRate(), _Fmark, int(_corrLen), mark.data());
+    design::fskLut(src_cfg.sampleRate(), _Fspace, int(_corrLen), space.data());
+    _plan_(SDRHIP_DET_FSK, mark.data(), space.data(), int(_corrLen), false, src_cfg.bufferSize());   // rings zeroed, index 0 (:48-51)
+    LogMessage msg(LOG_DEBUG);
+    msg << "Config FSKDetector node: " << std::endl
+        << " sample/symbol rate: " << src_cfg.sampleRate() << " Hz" << std::endl
+        << " target baud rate: " << _baud << std::endl
+        << " approx. samples per bit: " << _corrLen;
+    Logger::get().log(msg);
+    this->setConfig(Config(Config::typeId<uint8_t>(), src_cfg.sampleRate(), src_cfg.bufferSize(), 1));   // :64
+  }
+
+protected:
+  float _baud;
+  size_t _corrLen;
+  float _Fmark, _Fspace;
+};
+
+/** Drop-in for sdr::ASKDetector<int16_t> (reference src/fsk.hh:69-118). */
+template <class Scalar> class ASKDetector;
+template <>
+class ASKDetector<int16_t> : public detail::DetectorBase {
+public:
+  explicit ASKDetector(bool invert = false, int device = 0) : detail::DetectorBase("ASKDetector", device), _invert(invert) {}
+  virtual void config(const Config &src_cfg) {
+    if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
+    if (Config::typeId<int16_t>() != src_cfg.type()) {
+      ConfigError err;
+      err << "Can not configure ASKDetector: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
+      throw err;
+    }
+    _plan_(SDRHIP_DET_ASK, 0, 0, 0, _invert, src_cfg.bufferSize());
+    LogMessage msg(LOG_DEBUG);
+    msg << "Config ASKDetector node: " << std::endl
+        << " threshold:   " << 0 << std::endl
+        << " invert:      " << (_invert ? "yes" : "no") << std::endl
+        << " symbol rate: " << src_cfg.sampleRate() << " Hz";
+    Logger::get().log(msg);
+    this->setConfig(Config(Config::typeId<uint8_t>(), src_cfg.sampleRate(), src_cfg.bufferSize(), 1));   // src/fsk.hh:103
+  }
+
+protected:
+  bool _invert;
 };
 
 // =================================================================================================

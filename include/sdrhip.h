@@ -323,6 +323,54 @@ int sdrhip_deemph_i16_kernel_names(sdrhip_deemph *h, size_t n, char *buf, size_t
 int sdrhip_deemph_i16_reset(sdrhip_deemph *h);
 int sdrhip_deemph_i16_destroy(sdrhip_deemph *h);
 
+/* ---- audio to bits: FSKDetector, ASKDetector<int16_t>, BitStream (reference src/fsk.hh, src/fsk.cc) ---- */
+/* One tone's correlator LUT as FSKDetector::config makes it (src/fsk.cc:32-44): corr_len = int(sample_rate / baud) complex
+ * floats exp(i phi_k), phi accumulated in double by += 2 pi freq / sample_rate from 0 and narrowed to float at the call.
+ * baud and freq are floats, as the node's members are. *corr_len is always set; lut (may be NULL to ask for the length
+ * only) receives corr_len x (re, im) when lut_cap >= corr_len, else SDRHIP_E_SIZE. */
+int sdrhip_design_fsk_lut(double sample_rate, float baud, float freq, int *corr_len, float *lut, int lut_cap);
+/* Symbol detectors: `channels` rows of int16 in, one symbol (0 / 1, uint8) per sample out, any n per call (0 included).
+ *   SDRHIP_DET_FSK  FSKDetector (src/fsk.cc:68-95): each sample times the two LUTs goes into two rings of corr_len complex
+ *                   floats; the rings are summed in SLOT order (float, no fused multiply-add, denormals kept) and the
+ *                   symbol is (|mark|^2 - |space|^2) > 0. Bit-exact: the order of the adds is reproduced. The LUTs
+ *                   (corr_len x (re, im) each) are inputs, shared by all channels; corr_len <= 2048. State per channel:
+ *                   the last corr_len - 1 samples and the sample index mod corr_len.
+ *   SDRHIP_DET_ASK  ASKDetector<int16_t> (src/fsk.hh:106-111): (x > 0) ^ invert; the LUT arguments are ignored.
+ * reset: a freshly configured node (rings zeroed, index 0; src/fsk.cc:48-51). Kernels: "fsk_detect_kernel" /
+ * "ask_detect_kernel". */
+enum { SDRHIP_DET_FSK = 0, SDRHIP_DET_ASK = 1 };
+typedef struct sdrhip_detector sdrhip_detector;
+int sdrhip_detector_create(sdrhip_ctx *ctx, int kind, const float *mark_lut, const float *space_lut, int corr_len, int invert,
+                           int channels, size_t max_in, sdrhip_detector **out);
+int sdrhip_detector_process(sdrhip_detector *h, const int16_t *in_host, size_t n, size_t in_stride, uint8_t *out_host,
+                            size_t out_stride);
+int sdrhip_detector_process_dev(sdrhip_detector *h, const int16_t *in_dev, size_t n, size_t in_stride, uint8_t *out_dev,
+                                size_t out_stride);
+int sdrhip_detector_kernel_names(sdrhip_detector *h, char *buf, size_t len);
+int sdrhip_detector_reset(sdrhip_detector *h);
+int sdrhip_detector_destroy(sdrhip_detector *h);
+/* BitStream (src/fsk.cc:109-202): symbols in, bits out — a majority vote over the last corr_len = int(sample_rate / baud)
+ * symbols, sampled by a PLL (float phase and rate, corrections in double, rate held within +/- 0.5 %) that locks to the sign
+ * changes of the vote. The number of bits a call produces depends on the data: row c of `bits` receives counts[c] bytes
+ * (0 / 1), at most the capacity ceil(n * omegaMax) + 1 that sdrhip_bits_out_capacity reports — the row stride of `bits`
+ * must be at least that (0 = exactly that); nothing is ever written beyond it. (The reference sizes its buffer
+ * 1 + bufferSize / corr_len, which the PLL can exceed when sample_rate / baud is close to an integer.) counts: `channels`
+ * uint32 (device memory for process_dev). mode NORMAL: bit = vote; TRANSITION: 0 on a change of the vote, 1 otherwise
+ * (:180-186). A call of n = 0 sets the counts to 0. Kernels: "bits_pll_kernel" (one lane per channel) behind
+ * "bits_flags_kernel" (window sums across lanes). reset: a freshly configured node (:125-140). */
+enum { SDRHIP_BITS_NORMAL = 0, SDRHIP_BITS_TRANSITION = 1 };
+typedef struct sdrhip_bits sdrhip_bits;
+int sdrhip_bits_create(sdrhip_ctx *ctx, double sample_rate, float baud, int mode, int channels, size_t max_in, sdrhip_bits **out);
+int sdrhip_bits_corr_len(sdrhip_bits *h, int *corr_len);
+int sdrhip_bits_out_capacity(sdrhip_bits *h, size_t n_in, size_t *cap);
+int sdrhip_bits_process(sdrhip_bits *h, const uint8_t *sym_host, size_t n, size_t in_stride, uint8_t *bits_host, size_t out_stride,
+                        uint32_t *counts_host);
+int sdrhip_bits_process_dev(sdrhip_bits *h, const uint8_t *sym_dev, size_t n, size_t in_stride, uint8_t *bits_dev, size_t out_stride,
+                            uint32_t *counts_dev);
+int sdrhip_bits_kernel_names(sdrhip_bits *h, char *buf, size_t len);
+int sdrhip_bits_reset(sdrhip_bits *h);
+int sdrhip_bits_destroy(sdrhip_bits *h);
+
 /* ---- K6: SubSample<complex<int16_t>|complex<float>> (src/subsample.hh:92-101) ------------- */
 int sdrhip_subsample_create(sdrhip_ctx *ctx, int dtype, size_t n, int channels, size_t max_in,
                             sdrhip_subsample **out);

@@ -22,6 +22,8 @@ T_CS16, T_CF32, T_CS8, T_CF64 = 0, 1, 2, 3
 IN_CS16, IN_CU8 = 0, 1
 KEEP_RING, KEEP_FM, KEEP_COUNTERS = 1, 2, 4
 FFTCONV_OLA, FFTCONV_OLS = 0, 1
+DET_FSK, DET_ASK = 0, 1
+BITS_NORMAL, BITS_TRANSITION = 0, 1
 
 
 class SdrHipError(RuntimeError):
@@ -116,6 +118,21 @@ def lib():
             "sdrhip_deemph_i16_kernel_names": (C.c_int, [vp, sz, C.c_char_p, sz]),
             "sdrhip_deemph_i16_reset": (C.c_int, [vp]),
             "sdrhip_deemph_i16_destroy": (C.c_int, [vp]),
+            "sdrhip_design_fsk_lut": (C.c_int, [C.c_double, C.c_float, C.c_float, C.POINTER(C.c_int), f32p, C.c_int]),
+            "sdrhip_detector_create": (C.c_int, [vp, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, sz, pvp]),
+            "sdrhip_detector_process": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_detector_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_detector_kernel_names": (C.c_int, [vp, C.c_char_p, sz]),
+            "sdrhip_detector_reset": (C.c_int, [vp]),
+            "sdrhip_detector_destroy": (C.c_int, [vp]),
+            "sdrhip_bits_create": (C.c_int, [vp, C.c_double, C.c_float, C.c_int, C.c_int, sz, pvp]),
+            "sdrhip_bits_corr_len": (C.c_int, [vp, C.POINTER(C.c_int)]),
+            "sdrhip_bits_out_capacity": (C.c_int, [vp, sz, psz]),
+            "sdrhip_bits_process": (C.c_int, [vp, vp, sz, sz, vp, sz, vp]),
+            "sdrhip_bits_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz, vp]),
+            "sdrhip_bits_kernel_names": (C.c_int, [vp, C.c_char_p, sz]),
+            "sdrhip_bits_reset": (C.c_int, [vp]),
+            "sdrhip_bits_destroy": (C.c_int, [vp]),
             "sdrhip_iqbb_i16_set_input_format": (C.c_int, [vp, C.c_int]),
             "sdrhip_subsample_create": (C.c_int, [vp, C.c_int, sz, C.c_int, sz, pvp]),
             "sdrhip_subsample_out_count": (C.c_int, [vp, sz, psz]),

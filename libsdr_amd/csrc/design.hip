@@ -64,6 +64,17 @@ int sdrhip_design_fmdeemph_alpha(double sample_rate, int *alpha) {
   });
 }
 
+int sdrhip_design_fsk_lut(double sample_rate, float baud, float freq, int *corr_len, float *lut, int lut_cap) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(corr_len && sample_rate > 0 && baud > 0, SDRHIP_E_INVALID, "bad argument");
+    SDRHIP_REQUIRE(sample_rate / baud < 2147483647.0, SDRHIP_E_INVALID, "sample_rate / baud out of range");
+    *corr_len = dz::fskCorrLen(sample_rate, baud);
+    if (!lut) return;
+    SDRHIP_REQUIRE(lut_cap >= *corr_len, SDRHIP_E_SIZE, "lut_cap %d < corr_len %d", lut_cap, *corr_len);
+    dz::fskLut(sample_rate, freq, *corr_len, lut);
+  });
+}
+
 int sdrhip_design_fftfilt_kernel(int n, double fmin, double fmax, double sample_rate, float *h) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && n >= 2 && sample_rate != 0, SDRHIP_E_INVALID, "bad argument");

@@ -511,6 +511,136 @@ class FMDeemphI16(_Node):
         check(abi.lib().sdrhip_deemph_i16_reset(self._h))
 
 
+def design_fsk_lut(Fs, baud, freq):
+    """One tone's LUT of FSKDetector::config (reference src/fsk.cc:32-44): [int(Fs / baud), 2] float32."""
+    L = C.c_int(0)
+    check(abi.lib().sdrhip_design_fsk_lut(Fs, baud, freq, C.byref(L), None, 0))
+    t = np.zeros((L.value, 2), np.float32)
+    check(abi.lib().sdrhip_design_fsk_lut(Fs, baud, freq, C.byref(L), t.ctypes.data_as(C.POINTER(C.c_float)), L.value))
+    return t
+
+
+class SymbolDetector(_Node):
+    """FSKDetector / ASKDetector<int16_t> on `channels` rows: int16 [channels, n] in, symbols uint8 [channels, n] out."""
+    _destroy = "sdrhip_detector_destroy"
+
+    def __init__(self, ctx, kind, mark_lut=None, space_lut=None, invert=False, channels=1, max_in=65536):
+        super().__init__()
+        self.ctx, self.kind, self.channels = ctx, kind, channels
+        f32p = C.POINTER(C.c_float)
+        if kind == abi.DET_FSK:
+            m = np.ascontiguousarray(mark_lut, np.float32).reshape(-1, 2)
+            s = np.ascontiguousarray(space_lut, np.float32).reshape(-1, 2)
+            assert m.shape == s.shape, (m.shape, s.shape)
+            check(abi.lib().sdrhip_detector_create(ctx.handle, kind, m.ctypes.data_as(f32p), s.ctypes.data_as(f32p), m.shape[0], 0,
+                                                   channels, max_in, C.byref(self._h)))
+        else:
+            check(abi.lib().sdrhip_detector_create(ctx.handle, kind, None, None, 0, int(bool(invert)), channels, max_in, C.byref(self._h)))
+
+    def process(self, x):
+        x = np.ascontiguousarray(x, np.int16)
+        if x.ndim == 1:
+            x = x[None]
+        assert x.shape[0] == self.channels, x.shape
+        n = x.shape[1]
+        out = np.zeros(x.shape, np.uint8)
+        if device_router is not None and n:
+            return device_router(self.ctx, x, out, lambda i, si, o, so: self.process_dev(i, n, si, o, so))
+        check(abi.lib().sdrhip_detector_process(self._h, _ptr(x), n, n, _ptr(out), n))
+        return out
+
+    def process_dev(self, in_ptr, n, in_stride, out_ptr, out_stride):
+        check(abi.lib().sdrhip_detector_process_dev(self._h, C.c_void_p(in_ptr), n, in_stride, C.c_void_p(out_ptr), out_stride))
+
+    @property
+    def kernel_names(self):
+        b = C.create_string_buffer(256)
+        check(abi.lib().sdrhip_detector_kernel_names(self._h, b, 256))
+        return b.value.decode().split(",")
+
+    def reset(self):
+        check(abi.lib().sdrhip_detector_reset(self._h))
+
+
+class FSKDetector(SymbolDetector):
+    """sdr::FSKDetector(baud, Fmark, Fspace) at sample rate Fs; pass mark_lut / space_lut to pin the LUTs (fixtures)."""
+
+    def __init__(self, ctx, Fs, baud, Fmark, Fspace, channels=1, max_in=65536, mark_lut=None, space_lut=None):
+        if mark_lut is None:
+            mark_lut, space_lut = design_fsk_lut(Fs, baud, Fmark), design_fsk_lut(Fs, baud, Fspace)
+        super().__init__(ctx, abi.DET_FSK, mark_lut, space_lut, channels=channels, max_in=max_in)
+
+
+class ASKDetector(SymbolDetector):
+    """sdr::ASKDetector<int16_t>(invert)."""
+
+    def __init__(self, ctx, invert=False, channels=1, max_in=65536):
+        super().__init__(ctx, abi.DET_ASK, invert=invert, channels=channels, max_in=max_in)
+
+
+class BitStream(_Node):
+    """sdr::BitStream(baud, mode) at sample rate Fs on `channels` rows: symbols uint8 [channels, n] in; process() returns the
+    list of the channels' bit arrays (their lengths depend on the data)."""
+    _destroy = "sdrhip_bits_destroy"
+
+    def __init__(self, ctx, Fs, baud, mode=abi.BITS_TRANSITION, channels=1, max_in=65536):
+        super().__init__()
+        self.ctx, self.channels, self._counts_dev = ctx, channels, 0
+        check(abi.lib().sdrhip_bits_create(ctx.handle, Fs, baud, mode, channels, max_in, C.byref(self._h)))
+
+    @property
+    def corr_len(self):
+        v = C.c_int(0)
+        check(abi.lib().sdrhip_bits_corr_len(self._h, C.byref(v)))
+        return v.value
+
+    def out_capacity(self, n):
+        v = C.c_size_t(0)
+        check(abi.lib().sdrhip_bits_out_capacity(self._h, n, C.byref(v)))
+        return v.value
+
+    @property
+    def kernel_names(self):
+        b = C.create_string_buffer(256)
+        check(abi.lib().sdrhip_bits_kernel_names(self._h, b, 256))
+        return b.value.decode().split(",")
+
+    def process_raw(self, x):
+        """-> (bits [channels, capacity(n)] uint8, counts [channels] uint32)"""
+        x = np.ascontiguousarray(x, np.uint8)
+        if x.ndim == 1:
+            x = x[None]
+        assert x.shape[0] == self.channels, x.shape
+        n = x.shape[1]
+        cap = self.out_capacity(n)
+        out, counts = np.zeros((self.channels, cap), np.uint8), np.zeros(self.channels, np.uint32)
+        if device_router is not None and n:
+            if not self._counts_dev:
+                self._counts_dev = self.ctx.malloc(4 * self.channels)
+            device_router(self.ctx, x, out, lambda i, si, o, so: self.process_dev(i, n, si, o, so, self._counts_dev))
+            self.ctx.d2h(counts, self._counts_dev)
+            return out, counts
+        check(abi.lib().sdrhip_bits_process(self._h, _ptr(x), n, n, _ptr(out), cap, _ptr(counts)))
+        return out, counts
+
+    def process(self, x):
+        out, counts = self.process_raw(x)
+        return [out[c, :counts[c]].copy() for c in range(self.channels)]
+
+    def process_dev(self, sym_ptr, n, in_stride, bits_ptr, out_stride, counts_ptr):
+        check(abi.lib().sdrhip_bits_process_dev(self._h, C.c_void_p(sym_ptr), n, in_stride, C.c_void_p(bits_ptr), out_stride,
+                                                C.c_void_p(counts_ptr)))
+
+    def reset(self):
+        check(abi.lib().sdrhip_bits_reset(self._h))
+
+    def close(self):
+        if self._h and self._counts_dev:
+            self.ctx.free(self._counts_dev)
+            self._counts_dev = 0
+        super().close()
+
+
 class SubSample(_Node):
     """K6 — SubSample<complex<int16>|complex<float>>."""
     _destroy = "sdrhip_subsample_destroy"
