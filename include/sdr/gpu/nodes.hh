@@ -1549,6 +1549,152 @@ protected:
 };
 
 // =================================================================================================
+// TunerBank<int16_t>: ONE wideband input, C IQBaseBand<int16_t>(+demod) channels each with its own tune and filter
+// =================================================================================================
+template <class Scalar> class TunerBank;
+
+/** Several IQBaseBand<int16_t> nodes connected to one source, as one node: a Sink<cs16> with one Source per channel
+ * (source(c), the ChannelBank::Out pattern). Every channel has its own centre frequency, filter frequency and width;
+ * order, sub-sampling and the fused demodulator are the bank's. Per buffer: one H2D copy, one launch for all channels
+ * (sdrhip_tuner_i16_*), one D2H copy of all rows into a pinned staging buffer, then one send per channel, in channel
+ * order, as views of it. addChannel() after config() rebuilds the device plan: every channel restarts as a freshly
+ * configured node (FIR history, decimator and LUT phases at zero). */
+template <>
+class TunerBank<int16_t> : public Sink<cs16> {
+public:
+  typedef ChannelBank<int16_t>::Out Out;
+
+  TunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
+    : _order(std::max(size_t(1), order)), _D(std::max(size_t(1), sub_sample)), _epilogue(epilogue), _device(device), _ctx(0), _plan(0),
+      _din(0), _dout(0), _bs(0), _outStride(0), _Fs(0) {}
+  virtual ~TunerBank() {
+    _release();
+    for (size_t c = 0; c < _outs.size(); c++) delete _outs[c];
+  }
+
+  /** A new channel; returns its index. Before or after config(). */
+  size_t addChannel(double Fc, double Ff, double width) {
+    _tunes.push_back(Tune(Fc, Ff, width));
+    _outs.push_back(new Out());
+    if (_plan) _rebuild();
+    return _tunes.size() - 1;
+  }
+  size_t channels() const { return _tunes.size(); }
+  Source *source(size_t c) { return _outs[c]; }
+
+  double centerFrequency(size_t c) const { return _tunes[c].Fc; }
+  double filterFrequency(size_t c) const { return _tunes[c].Ff; }
+  double filterWidth(size_t c) const { return _tunes[c].width; }
+  /** The reference setters' effects (src/baseband.hh:82-104) on channel c alone. */
+  void setCenterFrequency(size_t c, double Fc) {
+    Tune &t = _tunes[c];
+    t.Fc = int32_t(Fc); t.shift = t.Fc;   // (truncated before setFrequencyShift, src/baseband.hh:85)
+    if (_plan) detail::configCheck(sdrhip_tuner_i16_set_shift(_plan, int(c), design::freqShiftIncrement(t.shift, double(_Fs)), 0 > t.shift), "TunerBank");
+  }
+  void setFilterFrequency(size_t c, double Ff) { _tunes[c].Ff = int32_t(Ff); _retap(c); }
+  void setFilterWidth(size_t c, double width) { _tunes[c].width = int32_t(width); _retap(c); }
+
+  virtual void config(const Config &cfg) {
+    if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
+    if (Config::typeId<cs16>() != cfg.type()) {
+      ConfigError err;
+      err << "Can not configure TunerBank: Invalid type " << cfg.type() << ", expected " << Config::typeId<cs16>();
+      throw err;
+    }
+    _bs = cfg.bufferSize();
+    _Fs = int32_t(cfg.sampleRate());
+    _rebuild();
+  }
+
+  virtual void process(const Buffer<cs16> &b, bool) {
+    if (!_plan || b.size() > _bs) return;
+    // the per-channel outputs are views of _stageOut: while a consumer still holds one of the last round, this round is
+    // dropped, as every node drops its input while its output buffer is in use (src/baseband.hh:141-150)
+    if (!_stageOut.isUnused()) {
+      LogMessage msg(LOG_WARNING);
+      msg << "gpu::TunerBank: output of the last round still in use downstream; buffer dropped";
+      Logger::get().log(msg);
+      return;
+    }
+    const size_t C = _tunes.size(), per = _epilogue == SDRHIP_EPI_NONE ? 1 : 2;   // int16 elements fit twice into a cs16 row
+    size_t n = 0;
+    if (b.size() == 0) return;
+    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din, b.data(), b.size() * sizeof(cs16)), "gpu::TunerBank") ||
+        !detail::processOk(sdrhip_tuner_i16_process_dev(_plan, _din, b.size(), _dout, _outStride * per, &n), "gpu::TunerBank") ||
+        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout, C * _outStride * sizeof(cs16)), "gpu::TunerBank") ||
+        !detail::processOk(sdrhip_ctx_synchronize(_ctx), "gpu::TunerBank"))
+      return;
+    for (size_t ch = 0; ch < C; ch++) {
+      if (_epilogue == SDRHIP_EPI_NONE) _outs[ch]->emit(_stageOut.sub(ch * _outStride, n), false);
+      else if (!(_epilogue == SDRHIP_EPI_FM && n == 0))
+        _outs[ch]->emit(Buffer<int16_t>(_stageOut).sub(ch * _outStride * 2, n), false);
+    }
+  }
+
+protected:
+  // as the reference node keeps them (src/baseband.hh:266-272): int32 members, truncated; only the constructor's frequency
+  // shift is the untruncated double (gpu::IQBaseBand: _shift)
+  struct Tune {
+    int32_t Fc, Ff, width;
+    double shift;
+    Tune(double fc, double ff, double w) : Fc(int32_t(fc)), Ff(int32_t(ff)), width(int32_t(w)), shift(fc) {}
+  };
+
+  void _retap(size_t c) {
+    if (!_plan) return;
+    std::vector<int32_t> taps(2 * _order);
+    design::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data());
+    detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), taps.data()), "TunerBank");
+  }
+
+  void _release() {
+    if (_ctx) sdrhip_ctx_synchronize(_ctx);
+    if (_plan) sdrhip_tuner_i16_destroy(_plan);
+    if (_din) sdrhip_free(_ctx, _din);
+    if (_dout) sdrhip_free(_ctx, _dout);
+    _plan = 0; _din = 0; _dout = 0;
+    if (!_stageOut.isEmpty()) { sdrhip_host_unregister(_stageOut.data()); _stageOut.unref(); }
+  }
+
+  void _rebuild() {
+    _release();
+    const size_t C = _tunes.size();
+    if (C == 0 || _bs == 0) return;
+    _ctx = Device::get(_device);
+    std::vector<int32_t> taps(C * 2 * _order), lut(2 * design::kLutSize);
+    std::vector<uint32_t> inc(C);
+    std::vector<int> neg(C);
+    for (size_t c = 0; c < C; c++) {
+      design::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data() + c * 2 * _order);
+      inc[c] = design::freqShiftIncrement(_tunes[c].shift, double(_Fs));
+      neg[c] = 0 > _tunes[c].shift;
+    }
+    design::freqShiftLutI16(lut.data());
+    _outStride = (_bs + _D - 1) / _D + 1;
+    detail::configCheck(sdrhip_tuner_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), int(_D), int(C), _bs,
+                                                _epilogue, &_plan), "TunerBank");
+    detail::configCheck(sdrhip_malloc(_ctx, _bs * sizeof(cs16), &_din), "TunerBank");
+    detail::configCheck(sdrhip_malloc(_ctx, C * _outStride * sizeof(cs16), &_dout), "TunerBank");
+    _stageOut = Buffer<cs16>(C * _outStride);
+    detail::configCheck(sdrhip_host_register(_stageOut.data(), C * _outStride * sizeof(cs16)), "TunerBank");
+    const double oRate = double(size_t(_Fs) / _D);
+    for (size_t c = 0; c < C; c++)
+      _outs[c]->configure(Config(_epilogue == SDRHIP_EPI_NONE ? Config::typeId<cs16>() : Config::typeId<int16_t>(), oRate, _outStride, 1));
+  }
+
+  size_t _order, _D;
+  int _epilogue, _device;
+  sdrhip_ctx *_ctx;
+  sdrhip_tuner_i16 *_plan;
+  void *_din, *_dout;
+  size_t _bs, _outStride;
+  int32_t _Fs;
+  std::vector<Tune> _tunes;
+  std::vector<Out *> _outs;
+  Buffer<cs16> _stageOut;
+};
+
+// =================================================================================================
 // FFT::exec / FFTPlan<float|double> on host buffers (reference src/fftplan.hh:14-36, src/fftplan_fftw3.hh:12-142)
 // =================================================================================================
 /** The reference's FFT module: the same Direction enum, exec<Scalar>(in, out, dir) and exec<Scalar>(inplace, dir). */

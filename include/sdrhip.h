@@ -258,6 +258,40 @@ enum { SDRHIP_KEEP_RING = 1, SDRHIP_KEEP_FM = 2, SDRHIP_KEEP_COUNTERS = 4 };
 int sdrhip_iqbb_i16_adopt_state(sdrhip_iqbb_i16 *h, sdrhip_iqbb_i16 *from, int what);
 int sdrhip_iqbb_i16_destroy(sdrhip_iqbb_i16 *h);
 
+/* ---- tuner bank: ONE wideband input, per-channel tune and filter ---------------------------- */
+/* `channels` independent IQBaseBand<int16_t> nodes (+ the fused demodulator `epilogue`) connected to ONE source: for
+ * every channel c and every sequence of calls, retunes and resets, output row c is bit for bit what the reference node
+ * with channel c's taps and shift (followed by FMDemod / AMDemod / USBDemod<int16_t> run in place) produces from the same
+ * buffers. Shared by all channels: the input row, ONE FIR history, the absolute sample index, order, decimation,
+ * epilogue and the 128-entry LUT. Per channel: the taps (channels x order x (re,im) int32 Q14), lut_inc and negative
+ * (channels entries each), the LUT phase origin, the open window's partial sum, the FM angle.
+ * Valid plans: order 1 ... 513, decim 1 ... 512, channels 1 ... 8192, any call length 0 ... max_in.
+ * Kernels (sdrhip_tuner_i16_kernel_names: the kernel the last call ran; before the first call, the one a call of max_in
+ * samples will run): "tuner_i16_mfma_kernel" — the FIR as an int8 GEMM on the matrix cores, channels x time, the
+ * sample tile staged once per workgroup and walked by several tiles of 16 channels — for decimations 4 ... 512, taps
+ * whose high byte plane fits int8 (on every channel) and calls of at least 512 samples; "tuner_i16_valu_kernel" for every
+ * other plan and call. SDRHIP_TUNER_PATH=valu in the environment at create time: the plain kernel only (tests). */
+typedef struct sdrhip_tuner_i16 sdrhip_tuner_i16;
+int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                            const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out);
+int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len);
+/* outputs per channel the next call of n_in samples will produce (does not advance the state) */
+int sdrhip_tuner_i16_out_count(sdrhip_tuner_i16 *h, size_t n_in, size_t *n_out);
+/* in: ONE row of n_in samples (cs16, or complex<uint8> after set_input_format); out: channels rows of out_stride
+ * elements (cs16 for EPI_NONE, int16 otherwise; 0 = tightly packed). process_dev: the output must not overlap the input. */
+int sdrhip_tuner_i16_process(sdrhip_tuner_i16 *h, const void *in_host, size_t n_in, void *out_host, size_t out_stride, size_t *n_out);
+int sdrhip_tuner_i16_process_dev(sdrhip_tuner_i16 *h, const void *in_dev, size_t n_in, void *out_dev, size_t out_stride, size_t *n_out);
+/* setFilterFrequency / setFilterWidth of ONE channel (order x (re,im)): only that channel's kernel changes. Taps whose
+ * high byte plane does not fit int8 move the bank to the plain kernel until they are replaced. */
+int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *taps);
+/* setCenterFrequency of ONE channel: new increment and sign, that channel's LUT phase restarts with the next sample */
+int sdrhip_tuner_i16_set_shift(sdrhip_tuner_i16 *h, int channel, uint32_t lut_inc, int negative);
+/* SDRHIP_IN_CS16 | SDRHIP_IN_CU8, before the first buffer or right after a reset (sdrhip_iqbb_i16_set_input_format) */
+int sdrhip_tuner_i16_set_input_format(sdrhip_tuner_i16 *h, int format);
+/* every channel at once, flags as sdrhip_iqbb_i16_reset: bit 0 keeps the (shared) FIR ring, | 2 the FM angles */
+int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history);
+int sdrhip_tuner_i16_destroy(sdrhip_tuner_i16 *h);
+
 /* ---- K2/K3: FIRFilter<complex<int16_t>> (exact) and FIRFilter<complex<float>> ------------- */
 enum {
   SDRHIP_FIR_CS16_EXACT = 0, /* fp64, one truncation per tap, taps walked in order: bit-exact

@@ -98,6 +98,17 @@ def lib():
             "sdrhip_iqbb_i16_reset": (C.c_int, [vp, C.c_int]),
             "sdrhip_iqbb_i16_adopt_state": (C.c_int, [vp, vp, C.c_int]),
             "sdrhip_iqbb_i16_destroy": (C.c_int, [vp]),
+            "sdrhip_tuner_i16_create": (C.c_int, [vp, i32p, C.c_int, i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                  sz, C.c_int, pvp]),
+            "sdrhip_tuner_i16_kernel_names": (C.c_int, [vp, C.c_char_p, sz]),
+            "sdrhip_tuner_i16_out_count": (C.c_int, [vp, sz, psz]),
+            "sdrhip_tuner_i16_process": (C.c_int, [vp, vp, sz, vp, sz, psz]),
+            "sdrhip_tuner_i16_process_dev": (C.c_int, [vp, vp, sz, vp, sz, psz]),
+            "sdrhip_tuner_i16_set_taps": (C.c_int, [vp, C.c_int, i32p]),
+            "sdrhip_tuner_i16_set_shift": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_int]),
+            "sdrhip_tuner_i16_set_input_format": (C.c_int, [vp, C.c_int]),
+            "sdrhip_tuner_i16_reset": (C.c_int, [vp, C.c_int]),
+            "sdrhip_tuner_i16_destroy": (C.c_int, [vp]),
             "sdrhip_fir_create": (C.c_int, [vp, C.c_int, f64p, C.c_int, C.c_int, C.c_int, sz, C.c_int, pvp]),
             "sdrhip_fir_out_count": (C.c_int, [vp, sz, psz]),
             "sdrhip_fir_kernel_names": (C.c_int, [vp, sz, C.c_char_p, sz]),

@@ -1,0 +1,658 @@
+// tuner.hip — the tuner bank: C independent IQBaseBand<int16_t> channels (+ fused FM / AM / USB demodulator) over ONE
+// shared input row (sdrhip.h, "tuner bank"). Shared by all channels: the input, ONE FIR history, the absolute sample
+// index, order, decimation, epilogue, the LUT. Per channel: taps, LUT increment, sign and phase origin, the open window's
+// partial sum, the FM angle. Reference arithmetic as iqbb_common.hpp lists it; every helper of the one-tune plan
+// (load_x, rotate, finalize_group, epilogue_and_roll, box_div, am_i16, usb_i16, fm_phi) is used as it is: a channel of the
+// bank is presented to them as a one-channel IqbbArgs view (channel_view) and they are called with channel index 0.
+//
+// Two kernels, both bit-exact:
+//   tuner_i16_valu_kernel   v_dot2 FIR at 8 consecutive samples per lane, one workgroup per (time tile, channel): every
+//                           valid plan (order 1 ... 513, decimation 1 ... 512, any call length).
+//   tuner_i16_mfma_kernel   the FIR as an int8 GEMM on v_mfma_i32_32x32x32_i8 with CHANNELS as matrix rows:
+//                             Y[(channel, comp)][t] = sum_k A[(channel, comp)][k] * U[k][t],   U[k][t] = u[2 (t - KW + 1) + k]
+//                           u = the interleaved (re, im) int16 stream of the ONE input, KW = 16 S the padded filter length,
+//                           A = the interleaved tap vectors (re: Kr, -Ki ...; im: Ki, Kr ...) of 16 channels = 32 rows.
+//                           Products are made exact by byte planes (iqbb_i16.hip): u = 256 uh + ul' + 128, a = 256 ah + al,
+//                             S = 65536 sum(ah uh) + 256 sum(ah ul' + al uh) + sum(al ul') + 128 sum(a)   (mod 2^32).
+//                           A workgroup stages the two sample planes of its time tile (with the KW - 1 halo) into LDS ONCE
+//                           and walks several channel tiles over them; tap fragments are packed per channel tile on the
+//                           host (create / set_taps). A lane ends up with (re, im) of 8 channels at one time column:
+//                           recombine, >> 14, rotate by the channel's own increment and phase origin, and add into the
+//                           (channel, group) box sums in LDS (through a wave-private transpose tile; wrapping int32 adds commute: ds_add_u32). Decimations 4 ... 512,
+//                           taps whose high byte plane fits int8, calls of at least HOT_MIN_IN samples.
+#include "iqbb_common.hpp"
+
+#include <algorithm>
+#include <string>
+
+namespace {
+
+constexpr int TUNER_MAX_ORDER = 513, TUNER_MAX_DECIM = 512, TUNER_MAX_CHANNELS = 8192;
+constexpr int CT = 16;            // channels per matrix tile (32 rows: re and im of each)
+constexpr int TR_STRIDE = 33;    // row stride (int2) of a wave's [channel][column] transpose tile
+constexpr int HOT_COLS = 512;     // time columns a hot tile aims at (whole decimation groups)
+constexpr int HOT_MIN_D = 4;      // smaller decimations: (channel, group) sums of a tile would not fit LDS
+constexpr int HOT_MIN_IN = 512;   // shorter calls hold no tile worth the staging: the plain form
+
+struct TunerArgs {
+  IqbbArgs a;               // the call as ONE channel sees it; in / hist: the shared row and ring, taps / acc / fm / out: channel 0's
+  const uint32_t *inc;      // per channel: LUT increment
+  const int *negative;      // ... sign of the shift
+  const uint32_t *phase0;   // ... absolute sample index (low 32 bits) at which the LUT phase counter last restarted
+  const int2 *cst;          // ... 128 * sum(a) of the interleaved tap vectors (re, im): the byte-plane constant term
+  int C, S, ctiles, ctw;    // channels, K steps of 32 plane bytes, channel tiles, channel tiles walked by one workgroup
+  int PLB;                  // bytes of one staged sample plane
+};
+
+// Channel c of the bank as the one-tune helpers see a plan's only channel (they are called with channel index 0).
+// rolls: this workgroup's channel is the one that rolls the shared history in the call's last tile.
+template <int EPI, bool CU8>
+__device__ __forceinline__ IqbbArgs channel_view(const TunerArgs &t, int c, bool rolls) {
+  IqbbArgs b = t.a;
+  b.in_cu8 = CU8; b.in_real = 0; b.i8 = 0; b.epilogue = EPI;
+  b.taps = t.a.taps + (long)c * t.a.OP;
+  b.inc = t.inc[c]; b.negative = t.negative[c];
+  b.n0_lo = t.a.n0_lo - t.phase0[c];
+  b.acc_old = t.a.acc_old + c; b.acc_new = t.a.acc_new + c;
+  b.fm_old = t.a.fm_old + c; b.fm_new = t.a.fm_new + c;
+  b.out = reinterpret_cast<char *>(t.a.out) + (long)c * t.a.out_stride * (EPI == SDRHIP_EPI_NONE ? 4 : 2);
+  if (!rolls) b.tiles = 0;   // (epilogue_and_roll rolls in tile == tiles - 1)
+  return b;
+}
+
+// ---- plain form: iqbb_i16_kernel's general decimation path over the shared row, one channel per blockIdx.y -----------
+template <int EPI, bool CU8>
+__global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const int c = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const IqbbArgs a = channel_view<EPI, CU8>(t, c, c == 0);
+  const int XS = TI + a.OP + 8;
+  uint32_t *xs = smem;                                  // staged samples, x[tb-(OP-1) ...]
+  int2 *lut_s = reinterpret_cast<int2 *>(smem + XS);    // 128 entries
+  uint32_t *ybuf = smem + XS + 256;                     // CG packed cs16 results (+ the FM angle cache)
+  int2 *vbuf = reinterpret_cast<int2 *>(ybuf + 2 * a.CGr);  // TI rotated samples
+
+  const int q0 = tile * a.OG - a.ovl;    // first group (relative to the call's first group) of this tile
+  const int tb = a.base0_rel + q0 * a.D; // call-relative index of the tile's first sample
+  const int groups_here = min(a.CG, a.n_groups - q0);
+
+  {
+    const int first = tb - (a.OP - 1);
+    const int need = min(XS, groups_here * a.D + a.OP + 8);
+    for (int i = tid; i < need; i += TPB) xs[i] = load_x(a, 0, first + i);
+    if (tid < 128) lut_s[tid] = a.lut[tid];
+  }
+  __syncthreads();
+
+  if (R * tid < groups_here * a.D) {
+    int sre[R], sim[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) { sre[r] = 0; sim[r] = 0; }
+    const uint4 *win = reinterpret_cast<const uint4 *>(xs + R * tid);
+    uint32_t w[16];
+    {
+      const uint4 p0 = win[0], p1 = win[1];
+      w[0] = p0.x; w[1] = p0.y; w[2] = p0.z; w[3] = p0.w;
+      w[4] = p1.x; w[5] = p1.y; w[6] = p1.z; w[7] = p1.w;
+    }
+    const uint2 *__restrict__ tp = a.taps;
+    for (int i0 = 0; i0 < a.OP; i0 += TAPC) {
+      const uint4 p2 = win[i0 / 4 + 2], p3 = win[i0 / 4 + 3];
+      w[8] = p2.x; w[9] = p2.y; w[10] = p2.z; w[11] = p2.w;
+      w[12] = p3.x; w[13] = p3.y; w[14] = p3.z; w[15] = p3.w;
+#pragma unroll
+      for (int u = 0; u < TAPC; u++) {
+        const uint2 k = tp[i0 + u];   // workgroup-uniform -> scalar loads
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          sre[r] = dot2(w[u + r], k.x, sre[r]);
+          sim[r] = dot2(w[u + r], k.y, sim[r]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; u++) w[u] = w[u + 8];
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int rel = tb + R * tid + r;
+      int2 v = rotate(a, lut_s, make_int2(sre[r] >> 14, sim[r] >> 14), a.n0_lo + (uint32_t)rel);
+      if (rel < 0 || rel >= a.N) v = make_int2(0, 0);   // outside this call
+      vbuf[R * tid + r] = v;
+    }
+  }
+  __syncthreads();
+
+  for (int ql = tid; ql < groups_here; ql += TPB) {
+    const int q = q0 + ql;
+    if (q < 0) continue;                      // tile 0's overlap slot precedes the call
+    int2 s = make_int2(0, 0);
+    for (int k = 0; k < a.D; k++) {
+      const int2 v = vbuf[ql * a.D + k];
+      s.x = (int)((unsigned)s.x + (unsigned)v.x);
+      s.y = (int)((unsigned)s.y + (unsigned)v.y);
+    }
+    finalize_group(a, 0, lut_s, ybuf, ql, q, s, a.D);
+  }
+  __syncthreads();
+  epilogue_and_roll(a, 0, tile, tid, q0, groups_here, ybuf);
+}
+
+// ---- hot form -----------------------------------------------------------------------------------------------------------
+// LDS: [0, 1024) the rotation table; two sample planes (high bytes, low bytes - 128) of PLB bytes; the channel tile's
+// parameters; gsum[CT][CG] box sums; ybuf[CT][2 CGr] results and FM angle cache (finalize_group's layout per channel);
+// one [CT][TR_STRIDE] transpose tile per wave.
+// Tap fragments (host: pack_tile): v4i index ((ct * S + s) * 2 + plane) * 64 + lane; lane (m = l & 31, hh = l >> 5) holds
+// bytes k = 32 s + 16 hh + j of row m, and row m carries channel 8 hC + (r >> 1), component r & 1 with hC = (m >> 2) & 1,
+// r = (m & 3) + 4 (m >> 3): by the 32x32 C/D map lane (n, h) then holds, in accumulator registers 2j / 2j + 1, (re, im) of
+// channel 8 h + j of the tile at time column n.
+template <int EPI, bool CU8>
+__global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const IqbbArgs &g = t.a;
+  const int tile = blockIdx.x, tid = threadIdx.x, l = tid & 63, w = tid >> 6, n = l & 31, h = l >> 5;
+  int2 *lut_s = reinterpret_cast<int2 *>(smem);
+  unsigned char *plane_h = reinterpret_cast<unsigned char *>(smem + 256);
+  unsigned char *plane_l = plane_h + t.PLB;
+  uint32_t *cinc = reinterpret_cast<uint32_t *>(plane_l + t.PLB);
+  uint32_t *cn0 = cinc + CT;       // (n0 - phase origin) per channel of the tile
+  int *cneg = reinterpret_cast<int *>(cn0 + CT);
+  int2 *ccst = reinterpret_cast<int2 *>(cneg + CT);
+  int2 *gsum = ccst + CT;
+  uint32_t *ybuf = reinterpret_cast<uint32_t *>(gsum + CT * g.CG);
+  int2 *trbuf = reinterpret_cast<int2 *>(ybuf + CT * 2 * g.CGr);   // 4 waves x [CT][TR_STRIDE]
+
+  const int q0 = tile * g.OG - g.ovl;
+  const int tb = g.base0_rel + q0 * g.D;
+  const int groups_here = min(g.CG, g.n_groups - q0);
+  const int span = groups_here * g.D;          // time columns of this tile
+  const int KW = 16 * t.S;                     // padded filter length: plane byte 0 = re of sample tb - (KW - 1)
+
+  {   // ---- stage the tile's samples as two byte planes, once for every channel tile ------------------------------------
+    IqbbArgs a0 = g; a0.in_cu8 = CU8; a0.in_real = 0; a0.i8 = 0;
+    const int first = tb - (KW - 1), need = t.PLB / 2;
+    for (int i = tid; i < need; i += TPB) {
+      const uint32_t x = i < span + KW - 1 ? load_x(a0, 0, first + i) : 0u;
+      const uint32_t hi = ((x >> 8) & 0xffu) | ((x >> 16) & 0xff00u);
+      const uint32_t lo = ((x & 0xffu) | ((x >> 8) & 0xff00u)) ^ 0x8080u;
+      reinterpret_cast<uint16_t *>(plane_h)[i] = (uint16_t)hi;
+      reinterpret_cast<uint16_t *>(plane_l)[i] = (uint16_t)lo;
+    }
+    if (tid < 128) lut_s[tid] = g.lut[tid];
+  }
+
+  const int nblk = (span + 31) >> 5;
+  for (int ci = 0; ci < t.ctw; ci++) {
+    const int ct = blockIdx.y * t.ctw + ci;
+    if (ct >= t.ctiles) break;
+    const int c0 = ct * CT, chans = min(CT, t.C - c0);
+    __syncthreads();   // the planes are staged / the previous channel tile's epilogue is through with gsum and ybuf
+    for (int i = tid; i < CT * g.CG; i += TPB) gsum[i] = make_int2(0, 0);
+    if (tid < CT) {
+      const bool live = tid < chans;
+      cinc[tid] = live ? t.inc[c0 + tid] : 0u;
+      cneg[tid] = live ? t.negative[c0 + tid] : 0;
+      cn0[tid] = live ? g.n0_lo - t.phase0[c0 + tid] : 0u;
+      ccst[tid] = live ? t.cst[c0 + tid] : make_int2(0, 0);
+    }
+    __syncthreads();
+
+    // ---- matrix part: wave w takes the column blocks w, w + 4, ... -----------------------------------------------------
+    const v4i *frag = g.tapfrag + (size_t)ct * t.S * 2 * 64 + l;
+    for (int kb = w; kb < nblk; kb += 4) {
+      const int tc = 32 * kb + n;            // the lane's time column within the tile
+      v16i acc_hh = {0}, acc_mid = {0}, acc_ll;
+#pragma unroll
+      for (int r = 0; r < 16; r++) { const int2 k = ccst[8 * h + (r >> 1)]; acc_ll[r] = (r & 1) ? k.y : k.x; }
+      const int off = 2 * tc + 16 * h;       // plane byte of the lane's K slice at step 0 (2-byte aligned)
+      const uint32_t *ph = reinterpret_cast<const uint32_t *>(plane_h + (off & ~3));
+      const uint32_t *pl = reinterpret_cast<const uint32_t *>(plane_l + (off & ~3));
+      const uint32_t sh = (uint32_t)(off & 2);
+      for (int s = 0; s < t.S; s++) {
+        const v4i Ah = frag[(2 * s) * 64], Al = frag[(2 * s + 1) * 64];
+        uint32_t dh[5], dl[5];
+#pragma unroll
+        for (int i = 0; i < 5; i++) { dh[i] = ph[8 * s + i]; dl[i] = pl[8 * s + i]; }
+        v4i uh, ul;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          uh[i] = (int)__builtin_amdgcn_alignbyte(dh[i + 1], dh[i], sh);
+          ul[i] = (int)__builtin_amdgcn_alignbyte(dl[i + 1], dl[i], sh);
+        }
+        acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(Al, uh, acc_mid, 0, 0, 0);
+        acc_ll = __builtin_amdgcn_mfma_i32_32x32x32_i8(Al, ul, acc_ll, 0, 0, 0);
+        acc_hh = __builtin_amdgcn_mfma_i32_32x32x32_i8(Ah, uh, acc_hh, 0, 0, 0);
+        acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(Ah, ul, acc_mid, 0, 0, 0);
+      }
+      // ---- recombine, >> 14, the channel's rotation; then through a wave-private LDS tile [channel][column] so that four
+      // lanes per channel each add 8 consecutive columns in registers and touch the (channel, group) box sums once per
+      // group they meet (wrapping int32 adds commute: ds_add_u32), not once per column ------------------------------------
+      const int rel = tb + tc;               // call-relative sample index
+      const bool valid = tc < span && rel >= 0 && rel < g.N;
+      int2 *tr = trbuf + w * (CT * TR_STRIDE);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int cl = 8 * h + j;
+        const unsigned sr = ((unsigned)acc_hh[2 * j] << 16) + ((unsigned)acc_mid[2 * j] << 8) + (unsigned)acc_ll[2 * j];
+        const unsigned si = ((unsigned)acc_hh[2 * j + 1] << 16) + ((unsigned)acc_mid[2 * j + 1] << 8) + (unsigned)acc_ll[2 * j + 1];
+        int2 v = make_int2(0, 0);            // outside the call or the tile: r = 0 -> v = 0
+        if (valid) {
+          IqbbArgs rot; rot.i8 = 0; rot.inc = cinc[cl]; rot.negative = cneg[cl];
+          v = rotate(rot, lut_s, make_int2((int)sr >> 14, (int)si >> 14), cn0[cl] + (uint32_t)rel);
+        }
+        tr[cl * TR_STRIDE + n] = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      {
+        const int cl = l >> 2, cb = 8 * (l & 3);   // lane: channel cl of the tile, columns cb ... cb + 7 of the block
+        const int col0 = 32 * kb + cb;
+        if (cl < chans && col0 < span) {
+          int ql = col0 / g.D, left = g.D - (col0 - ql * g.D);   // the group of the lane's first column, its columns still to come
+          int2 s = make_int2(0, 0);
+          bool pending = false;
+          const int cnt = min(8, span - col0);
+          for (int i = 0; i < cnt; i++) {
+            const int2 v = tr[cl * TR_STRIDE + cb + i];
+            s.x = (int)((unsigned)s.x + (unsigned)v.x); s.y = (int)((unsigned)s.y + (unsigned)v.y);
+            pending = true;
+            if (--left == 0) {
+              atomicAdd(&gsum[cl * g.CG + ql].x, s.x); atomicAdd(&gsum[cl * g.CG + ql].y, s.y);
+              s = make_int2(0, 0); pending = false; ql++; left = g.D;
+            }
+          }
+          if (pending) { atomicAdd(&gsum[cl * g.CG + ql].x, s.x); atomicAdd(&gsum[cl * g.CG + ql].y, s.y); }
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();   // (the next block rewrites the tile)
+    }
+    __syncthreads();
+
+    // ---- per channel: carry / first-sample quirk / division / state, then demodulate and store --------------------------
+    for (int cl = 0; cl < chans; cl++) {
+      const IqbbArgs a = channel_view<EPI, CU8>(t, c0 + cl, c0 + cl == 0);
+      for (int ql = tid; ql < groups_here; ql += TPB) {
+        const int q = q0 + ql;
+        if (q < 0) continue;
+        finalize_group(a, 0, lut_s, ybuf + cl * 2 * g.CGr, ql, q, gsum[cl * g.CG + ql], g.D);
+      }
+    }
+    __syncthreads();
+    for (int cl = 0; cl < chans; cl++) {
+      const IqbbArgs a = channel_view<EPI, CU8>(t, c0 + cl, c0 + cl == 0);
+      epilogue_and_roll(a, 0, tile, tid, q0, groups_here, ybuf + cl * 2 * g.CGr);
+    }
+  }
+}
+
+bool taps_fit_planes(const int32_t *taps, int order) {
+  auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
+  for (int i = 0; i < 2 * order; i++)   // (both v and -v are packed: Kr, -Ki / Ki, Kr)
+    if (high_byte(taps[i]) > 127 || high_byte(-taps[i]) > 127) return false;
+  return true;
+}
+
+}  // namespace
+
+struct sdrhip_tuner_i16 {
+  sdrhip_ctx *ctx = nullptr;
+  int order = 0, OP = 0, S = 0, HH = 0, D = 1, C = 1, epi = 0, in_cu8 = 0, ovl = 0;
+  int ctiles = 0;
+  size_t max_in = 0, max_out = 0;
+  uint64_t n0 = 0;
+  int par = 0, par_fm = 0;
+  bool force_valu = false;
+  std::vector<int32_t> taps_host;      // C x order x 2
+  std::vector<uint32_t> inc_host;
+  std::vector<int> neg_host;
+  std::vector<char> fits;              // per channel: the taps' high byte plane fits int8
+  int misfits = 0;                     // channels whose taps do not (any: the plain form for the whole bank)
+  DevBuf<uint2> taps;                  // C x OP x {pack(Kr,-Ki), pack(Ki,Kr)}
+  DevBuf<v4i> tapfrag;                 // ctiles x S x 2 x 64
+  DevBuf<int2> cst, lut;
+  DevBuf<uint32_t> inc, phase0;
+  DevBuf<int> negative;
+  DevBuf<uint32_t> hist[2];            // ONE ring of HH samples
+  DevBuf<int2> acc[2];
+  DevBuf<short> fm[2];
+  DevBuf<uint32_t> stage_in, stage_out;
+  std::string last_names;
+
+  // the geometry of a call of N samples from absolute index n0 on (sdrhip_iqbb_i16::geometry for complex input:
+  // IQBaseBand closes its first window after D + 1 samples, src/baseband.hh:200,212)
+  struct Geometry { int n_groups, n_out, base0_rel, extra0; };
+  Geometry geometry(size_t N) const {
+    Geometry g{};
+    const uint64_t D64 = (uint64_t)D, shift1 = D > 1 ? 1 : 0;
+    auto group_of = [&](uint64_t n) -> uint64_t { return n < shift1 ? 0 : (n - shift1) / D64; };
+    const uint64_t gf = group_of(n0), gl = group_of(n0 + N - 1);
+    const uint64_t last_end = (gl + 1) * D64 - 1 + shift1;
+    g.n_groups = (int)(gl - gf + 1);
+    g.n_out = g.n_groups - (last_end <= n0 + N - 1 ? 0 : 1);
+    g.base0_rel = (int)((int64_t)(gf * D64 + shift1) - (int64_t)n0);
+    g.extra0 = (n0 == 0 && shift1) ? 1 : 0;
+    return g;
+  }
+  size_t out_elem_bytes() const { return epi == SDRHIP_EPI_NONE ? 4 : 2; }
+  size_t in_elem_bytes() const { return in_cu8 ? 2 : 4; }
+  bool hot_plan() const { return !force_valu && misfits == 0 && D >= HOT_MIN_D; }
+  bool hot_call(size_t N) const { return hot_plan() && N >= (size_t)HOT_MIN_IN; }
+  const char *kernel_name(bool hot) const { return hot ? "tuner_i16_mfma_kernel" : "tuner_i16_valu_kernel"; }
+
+  void pack_valu(int c, std::vector<uint2> &tp) const {   // zero-padded at the FRONT: the newest sample meets K[order-1]
+    const int32_t *k = taps_host.data() + (size_t)c * order * 2;
+    const int pad = OP - order;
+    for (int i = 0; i < OP; i++) tp[i] = make_uint2(0, 0);
+    for (int i = 0; i < order; i++) {
+      const int kr = k[2 * i], ki = k[2 * i + 1];
+      tp[pad + i].x = ((uint32_t)(uint16_t)(int16_t)kr) | ((uint32_t)(uint16_t)(int16_t)(-ki) << 16);
+      tp[pad + i].y = ((uint32_t)(uint16_t)(int16_t)ki) | ((uint32_t)(uint16_t)(int16_t)kr << 16);
+    }
+  }
+  // channel tile ct's fragments (S x 2 x 64 x 16 bytes) and its channels' constant terms (layout: tuner_i16_mfma_kernel)
+  void pack_tile(int ct, std::vector<int8_t> &frag, int2 *cst_tile) const {
+    const int KW = 16 * S, pad = KW - order;
+    std::vector<int> are((size_t)CT * 2 * KW, 0), aim((size_t)CT * 2 * KW, 0);
+    for (int cl = 0; cl < CT; cl++) {
+      const int c = ct * CT + cl;
+      unsigned sre = 0, sim = 0;
+      if (c < C && fits[c]) {
+        const int32_t *k = taps_host.data() + (size_t)c * order * 2;
+        int *re = are.data() + (size_t)cl * 2 * KW, *im = aim.data() + (size_t)cl * 2 * KW;
+        for (int i = 0; i < order; i++) {
+          const int kr = k[2 * i], ki = k[2 * i + 1];
+          re[2 * (pad + i)] = kr; re[2 * (pad + i) + 1] = -ki;
+          im[2 * (pad + i)] = ki; im[2 * (pad + i) + 1] = kr;
+        }
+        for (int x = 0; x < 2 * KW; x++) { sre += (unsigned)re[x]; sim += (unsigned)im[x]; }
+      }
+      cst_tile[cl] = make_int2((int)(128u * sre), (int)(128u * sim));
+    }
+    frag.assign((size_t)S * 2 * 64 * 16, 0);
+    for (int st = 0; st < S; st++)
+      for (int l = 0; l < 64; l++) {
+        const int m = l & 31, hh = l >> 5, hC = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
+        const int cl = 8 * hC + (r >> 1), comp = r & 1;
+        const int *row = (comp ? aim.data() : are.data()) + (size_t)cl * 2 * KW;
+        for (int j = 0; j < 16; j++) {
+          const int v = row[32 * st + 16 * hh + j];
+          const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
+          frag[((size_t)(2 * st) * 64 + l) * 16 + j] = (int8_t)ah;
+          frag[((size_t)(2 * st + 1) * 64 + l) * 16 + j] = (int8_t)al;
+        }
+      }
+  }
+  void upload_tile(int ct) {
+    std::vector<int8_t> frag; int2 cst_tile[CT];
+    pack_tile(ct, frag, cst_tile);
+    const size_t per = (size_t)S * 2 * 64;
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(tapfrag.p + (size_t)ct * per, frag.data(), per * sizeof(v4i), hipMemcpyHostToDevice, ctx->stream));
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(cst.p + (size_t)ct * CT, cst_tile, sizeof(cst_tile), hipMemcpyHostToDevice, ctx->stream));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  void upload_valu(int c) {
+    std::vector<uint2> tp(OP);
+    pack_valu(c, tp);
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(taps.p + (size_t)c * OP, tp.data(), (size_t)OP * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+
+  template <int EPI, bool CU8>
+  void launch_kernels(bool hot, const TunerArgs &t, dim3 grid, size_t lds) {
+    if (hot) hipLaunchKernelGGL((tuner_i16_mfma_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+    else hipLaunchKernelGGL((tuner_i16_valu_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+  }
+  template <bool CU8>
+  void launch_epi(bool hot, const TunerArgs &t, dim3 grid, size_t lds) {
+    switch (epi) {
+      case SDRHIP_EPI_FM: launch_kernels<SDRHIP_EPI_FM, CU8>(hot, t, grid, lds); break;
+      case SDRHIP_EPI_AM: launch_kernels<SDRHIP_EPI_AM, CU8>(hot, t, grid, lds); break;
+      case SDRHIP_EPI_USB: launch_kernels<SDRHIP_EPI_USB, CU8>(hot, t, grid, lds); break;
+      default: launch_kernels<SDRHIP_EPI_NONE, CU8>(hot, t, grid, lds); break;
+    }
+  }
+
+  void launch(const void *in_dev, size_t N, void *out_dev, size_t out_stride, size_t *n_out) {
+    ctx->use();
+    if (N == 0) { if (n_out) *n_out = 0; return; }   // empty buffer: nothing moves (src/baseband.hh:200)
+    const Geometry g = geometry(N);
+    SDRHIP_REQUIRE(out_stride >= (size_t)g.n_out, SDRHIP_E_SIZE, "out_stride %zu < outputs %d", out_stride, g.n_out);
+    const bool hot = hot_call(N);
+    TunerArgs t{};
+    IqbbArgs &a = t.a;
+    a.in = reinterpret_cast<const uint32_t *>(in_dev); a.in_stride = 0; a.in_cu8 = in_cu8;
+    a.hist_old = hist[par].p; a.hist_new = hist[par ^ 1].p; a.HH = HH;
+    a.acc_old = acc[par].p; a.acc_new = acc[par ^ 1].p;
+    const bool fm_flip = epi == SDRHIP_EPI_FM && g.n_out >= 2;
+    a.fm_old = fm[par_fm].p; a.fm_new = fm[par_fm ^ 1].p;
+    a.taps = taps.p; a.lut = lut.p; a.tapfrag = tapfrag.p;
+    a.OP = OP; a.D = D; a.N = (int)N; a.n0_lo = (uint32_t)n0;
+    a.base0_rel = g.base0_rel; a.n_groups = g.n_groups; a.n_out = g.n_out; a.extra0 = g.extra0;
+    a.ovl = ovl;
+    a.CG = hot ? std::max(HOT_COLS / D, ovl ? 4 : 1) : TI / D;   // (FM recomputes one group per tile: at least 3 of 4 are new)
+    a.OG = a.CG - ovl; a.CGr = (a.CG + 3) & ~3;
+    a.out = out_dev; a.out_stride = (long)out_stride; a.epilogue = epi;
+    a.tiles = (int)ceil_div((size_t)g.n_groups, (size_t)a.OG); a.tpw = 1; a.lpg = 1;
+    t.inc = inc.p; t.negative = negative.p; t.phase0 = phase0.p; t.cst = cst.p;
+    t.C = C; t.S = S; t.ctiles = ctiles;
+    dim3 grid; size_t lds;
+    if (hot) {
+      // enough workgroups to fill the device, as many channel tiles per staged sample tile as that leaves
+      int ctw = 8; while (ctw > 1 && (size_t)a.tiles * ceil_div((size_t)ctiles, (size_t)ctw) < 1024) ctw >>= 1;
+      t.ctw = ctw;
+      const int cols = (a.CG * D + 31) & ~31;
+      t.PLB = (2 * (cols + 16 * S) + 16 + 15) & ~15;
+      grid = dim3((unsigned)a.tiles, (unsigned)ceil_div((size_t)ctiles, (size_t)ctw));
+      lds = 1024 + 2 * (size_t)t.PLB + CT * (4 + 4 + 4 + 8) + (size_t)CT * a.CG * 8 + (size_t)CT * 2 * a.CGr * 4 + 4 * (size_t)CT * TR_STRIDE * 8;
+    } else {
+      grid = dim3((unsigned)a.tiles, (unsigned)C);
+      lds = (TI + (size_t)OP + 8 + 256 + 2 * (size_t)a.CGr) * 4 + (size_t)TI * 8;
+    }
+    // (every valid plan fits: the plain form needs at most 44 KB at decimation 1, the matrix form 57 KB at decimation 4 and 513 taps)
+    SDRHIP_REQUIRE(lds <= 64 * 1024, SDRHIP_E_HIP, "internal error: %zu B of LDS for a valid plan", lds);
+    if (in_cu8) launch_epi<true>(hot, t, grid, lds); else launch_epi<false>(hot, t, grid, lds);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    par ^= 1;
+    if (fm_flip) par_fm ^= 1;
+    n0 += N;
+    last_names = kernel_name(hot);
+    if (n_out) *n_out = (size_t)g.n_out;
+  }
+};
+
+extern "C" {
+
+int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                            const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(ctx && taps && lut && lut_inc && negative && out, SDRHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
+    SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
+    SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
+    SDRHIP_REQUIRE(channels >= 1 && channels <= TUNER_MAX_CHANNELS, SDRHIP_E_INVALID, "channels %d outside [1,%d]", channels, TUNER_MAX_CHANNELS);
+    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
+    SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
+    for (size_t i = 0; i < (size_t)channels * order * 2; i++)
+      SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
+                     i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
+    for (int i = 0; i < 256; i++)
+      SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
+    ctx->use();
+    sdrhip_tuner_i16 *h = new sdrhip_tuner_i16;
+    try {
+      h->ctx = ctx; h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
+      h->ovl = epilogue == SDRHIP_EPI_FM ? 1 : 0;
+      h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;
+      h->S = (int)ceil_div((size_t)order, (size_t)16);
+      h->HH = 16 * h->S;   // >= OP, and the whole ring (reset with keep_history)
+      h->ctiles = (int)ceil_div((size_t)channels, (size_t)CT);
+      { const char *force = getenv("SDRHIP_TUNER_PATH"); h->force_valu = force && !strcmp(force, "valu"); }
+      h->taps_host.assign(taps, taps + (size_t)channels * order * 2);
+      h->inc_host.assign(lut_inc, lut_inc + channels);
+      h->neg_host.resize(channels);
+      for (int c = 0; c < channels; c++) h->neg_host[c] = negative[c] ? 1 : 0;
+      h->fits.resize(channels);
+      for (int c = 0; c < channels; c++) { h->fits[c] = taps_fit_planes(taps + (size_t)c * order * 2, order); h->misfits += h->fits[c] ? 0 : 1; }
+      hipStream_t st = ctx->stream;
+      h->taps.alloc((size_t)channels * h->OP);
+      {
+        std::vector<uint2> all((size_t)channels * h->OP), one(h->OP);
+        for (int c = 0; c < channels; c++) { h->pack_valu(c, one); std::copy(one.begin(), one.end(), all.begin() + (size_t)c * h->OP); }
+        h->taps.upload(all.data(), all.size(), st);
+      }
+      h->tapfrag.alloc((size_t)h->ctiles * h->S * 2 * 64);
+      h->cst.alloc((size_t)h->ctiles * CT);
+      for (int ct = 0; ct < h->ctiles; ct++) h->upload_tile(ct);
+      h->lut.alloc(128); h->lut.upload(reinterpret_cast<const int2 *>(lut), 128, st);
+      h->inc.alloc(channels); h->inc.upload(h->inc_host.data(), channels, st);
+      h->negative.alloc(channels); h->negative.upload(h->neg_host.data(), channels, st);
+      h->phase0.alloc(channels); h->phase0.zero(st);
+      for (int p = 0; p < 2; p++) {
+        h->hist[p].alloc(h->HH); h->hist[p].zero(st);
+        h->acc[p].alloc(channels); h->acc[p].zero(st);
+        h->fm[p].alloc(channels); h->fm[p].zero(st);
+      }
+      h->max_out = max_in / decim + 2;
+      h->last_names = h->kernel_name(h->hot_call(max_in));
+      SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+    } catch (...) { delete h; throw; }
+    *out = h;
+  });
+}
+
+int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
+    snprintf(buf, len, "%s", h->last_names.c_str());
+  });
+}
+
+int sdrhip_tuner_i16_out_count(sdrhip_tuner_i16 *h, size_t n_in, size_t *n_out) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
+    *n_out = n_in ? (size_t)h->geometry(n_in).n_out : 0;
+  });
+}
+
+int sdrhip_tuner_i16_process_dev(sdrhip_tuner_i16 *h, const void *in_dev, size_t n_in, void *out_dev, size_t out_stride, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_tuner_i16_process_dev");
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
+    if (n_in == 0) { if (n_out) *n_out = 0; return; }
+    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
+    const size_t no = (size_t)h->geometry(n_in).n_out;
+    if (out_stride == 0) out_stride = no;
+    require_disjoint(in_dev, n_in, n_in, h->in_elem_bytes(), out_dev, out_stride, no, h->out_elem_bytes(), 1, (size_t)h->C);
+    h->launch(in_dev, n_in, out_dev, out_stride, n_out);
+  });
+}
+
+int sdrhip_tuner_i16_process(sdrhip_tuner_i16 *h, const void *in_host, size_t n_in, void *out_host, size_t out_stride, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_tuner_i16_process");
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
+    if (n_in == 0) { if (n_out) *n_out = 0; return; }
+    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
+    h->ctx->use();
+    const size_t no = (size_t)h->geometry(n_in).n_out;
+    if (out_stride == 0) out_stride = no;
+    SDRHIP_REQUIRE(out_stride >= no, SDRHIP_E_SIZE, "out_stride %zu < outputs %zu", out_stride, no);
+    if (!h->stage_in.p) {
+      h->stage_in.alloc(h->max_in);
+      h->stage_out.alloc((size_t)h->C * h->max_out);
+    }
+    const size_t ib = h->in_elem_bytes(), eb = h->out_elem_bytes();
+    copy_h2d_rows(h->ctx, h->stage_in.p, n_in * ib, in_host, n_in * ib, n_in * ib, 1);
+    size_t produced = 0;
+    h->launch(h->stage_in.p, n_in, h->stage_out.p, h->max_out * 4 / eb, &produced);
+    copy_d2h_rows(h->ctx, out_host, out_stride * eb, h->stage_out.p, h->max_out * 4, produced * eb, h->C);
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    if (n_out) *n_out = produced;
+  });
+}
+
+int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *taps) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    for (int i = 0; i < 2 * h->order; i++)
+      SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
+    h->ctx->use();
+    std::copy(taps, taps + (size_t)h->order * 2, h->taps_host.begin() + (size_t)channel * h->order * 2);
+    // (taps whose high byte plane does not fit int8 move the whole bank to the plain form until they are replaced)
+    const bool fit = taps_fit_planes(taps, h->order);
+    h->misfits += (h->fits[channel] ? 0 : -1) + (fit ? 0 : 1);
+    h->fits[channel] = fit;
+    h->upload_valu(channel);   // stream-ordered after the launches already enqueued
+    h->upload_tile(channel / CT);
+    if (h->n0 == 0) h->last_names = h->kernel_name(h->hot_call(h->max_in));
+  });
+}
+
+int sdrhip_tuner_i16_set_shift(sdrhip_tuner_i16 *h, int channel, uint32_t lut_inc, int negative) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    h->ctx->use();
+    hipStream_t st = h->ctx->stream;
+    h->inc_host[channel] = lut_inc; h->neg_host[channel] = negative ? 1 : 0;
+    const uint32_t p0 = (uint32_t)h->n0;   // _lut_count = 0 (src/freqshift.hh:86): the phase is a closed form of (n - origin)
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->inc.p + channel, &h->inc_host[channel], 4, hipMemcpyHostToDevice, st));
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->negative.p + channel, &h->neg_host[channel], 4, hipMemcpyHostToDevice, st));
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->phase0.p + channel, &p0, 4, hipMemcpyHostToDevice, st));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int sdrhip_tuner_i16_set_input_format(sdrhip_tuner_i16 *h, int format) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(format == SDRHIP_IN_CS16 || format == SDRHIP_IN_CU8, SDRHIP_E_INVALID, "bad input format %d", format);
+    SDRHIP_REQUIRE(h->n0 == 0, SDRHIP_E_INVALID, "the input format can only change before the first buffer / after a reset");
+    h->in_cu8 = format == SDRHIP_IN_CU8;
+  });
+}
+
+int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    h->ctx->use();
+    hipStream_t st = h->ctx->stream;
+    // bit 0: the FIR ring survives, read ROTATED afterwards (IQBaseBand::_reconfigure, src/baseband.hh:175-177: _ring_offset = 0,
+    // the contents stay where they lie); bit 1: so do the fused FMDemod's last angles (sdrhip_iqbb_i16_reset)
+    const bool keep_fm = (keep_history & 2) != 0;
+    keep_history &= 1;
+    for (int p = 0; p < 2; p++) { h->acc[p].zero(st); if (!keep_fm) h->fm[p].zero(st); }
+    const int P = (int)(h->n0 % (uint64_t)h->order);   // the reference's _ring_offset
+    if (!keep_history) {
+      for (int p = 0; p < 2; p++) h->hist[p].zero(st);
+    } else if (P != 0) {
+      // apparent history afterwards, oldest first: ring[1 .. order-1], ring[i] = t[order-P+i] (i < P) or t[i-P] (i >= P),
+      // t = the last `order` samples in time order (the tail of the row)
+      const int order = h->order, HH = h->HH;
+      std::vector<uint32_t> old(HH), neu(HH, 0u);
+      SDRHIP_CHECK_HIP(hipMemcpyAsync(old.data(), h->hist[h->par].p, (size_t)HH * 4, hipMemcpyDeviceToHost, st));
+      SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+      const uint32_t *t = old.data() + (HH - order);
+      uint32_t *d = neu.data() + (HH - (order - 1));
+      for (int k = 0; k + 1 < order; k++) { const int i = k + 1; d[k] = i < P ? t[order - P + i] : t[i - P]; }
+      SDRHIP_CHECK_HIP(hipMemcpyAsync(h->hist[h->par].p, neu.data(), (size_t)HH * 4, hipMemcpyHostToDevice, st));
+      SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    h->phase0.zero(st);
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+    h->n0 = 0;
+  });
+}
+
+int sdrhip_tuner_i16_destroy(sdrhip_tuner_i16 *h) {
+  return guarded([&] {
+    if (!h) return;
+    h->ctx->use();
+    (void)hipStreamSynchronize(h->ctx->stream);
+    delete h;
+  });
+}
+
+}  // extern "C"

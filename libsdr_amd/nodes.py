@@ -335,6 +335,79 @@ class IQBaseBandI16(_Node):
         self._cu8 = fmt == abi.IN_CU8
 
 
+class TunerBankI16(_Node):
+    """Tuner bank — C IQBaseBand<int16_t> channels (+ fused FM/AM/USB) over ONE shared input row, each with its own taps
+    and frequency shift. Mirrors sdr::gpu::TunerBank<int16_t>."""
+    _destroy = "sdrhip_tuner_i16_destroy"
+
+    def __init__(self, ctx, taps, lut, lut_inc, negative, decim, max_in=65536, epilogue=EPI_NONE):
+        super().__init__()
+        taps = np.ascontiguousarray(taps, np.int32)
+        assert taps.ndim == 3 and taps.shape[2] == 2, taps.shape
+        lut = np.ascontiguousarray(lut, np.int32).reshape(128, 2)
+        inc = np.ascontiguousarray(lut_inc, np.uint32).reshape(-1)
+        neg = np.ascontiguousarray(np.asarray(negative, bool), np.int32).reshape(-1)
+        channels, order = taps.shape[0], taps.shape[1]
+        assert inc.size == channels and neg.size == channels
+        self.ctx, self.channels, self.order, self.decim, self.epilogue, self.max_in = ctx, channels, order, decim, epilogue, max_in
+        self._cu8 = False
+        check(abi.lib().sdrhip_tuner_i16_create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
+                                                lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                neg.ctypes.data_as(C.POINTER(C.c_int)), decim, channels, max_in, epilogue,
+                                                C.byref(self._h)))
+
+    @property
+    def kernel_names(self):
+        """The kernel the last call ran (before the first call: the one a call of max_in samples will run)."""
+        b = C.create_string_buffer(256)
+        check(abi.lib().sdrhip_tuner_i16_kernel_names(self._h, b, 256))
+        return b.value.decode().split(",")
+
+    def out_count(self, n_in):
+        n = C.c_size_t(0)
+        check(abi.lib().sdrhip_tuner_i16_out_count(self._h, n_in, C.byref(n)))
+        return n.value
+
+    def process(self, x):
+        """x: ONE row [n, 2] (int16, or uint8 after set_input_format(IN_CU8)); returns [C, n_out(, 2)]."""
+        x = np.ascontiguousarray(x, np.uint8 if self._cu8 else np.int16)
+        assert x.ndim == 2 and x.shape[1] == 2, x.shape
+        n_in = x.shape[0]
+        no = self.out_count(n_in)
+        out = np.zeros((self.channels, no, 2) if self.epilogue == EPI_NONE else (self.channels, no), np.int16)
+        if device_router is not None and n_in and no:
+            return device_router(self.ctx, x[None], out, lambda i, si, o, so: self._dev_checked(i, n_in, o, so, no))
+        got = C.c_size_t(0)
+        check(abi.lib().sdrhip_tuner_i16_process(self._h, _ptr(x), n_in, _ptr(out), no, C.byref(got)))
+        assert got.value == no
+        return out
+
+    def _dev_checked(self, i, n_in, o, so, no):
+        assert self.process_dev(i, n_in, o, so) == no
+
+    def process_dev(self, in_ptr, n_in, out_ptr, out_stride):
+        got = C.c_size_t(0)
+        check(abi.lib().sdrhip_tuner_i16_process_dev(self._h, C.c_void_p(in_ptr), n_in, C.c_void_p(out_ptr), out_stride, C.byref(got)))
+        return got.value
+
+    def set_taps(self, c, taps):
+        """setFilterFrequency / setFilterWidth of channel c: that channel's kernel only."""
+        taps = np.ascontiguousarray(taps, np.int32).reshape(-1, 2)
+        assert taps.shape[0] == self.order
+        check(abi.lib().sdrhip_tuner_i16_set_taps(self._h, int(c), taps.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def set_shift(self, c, lut_inc, negative):
+        """setCenterFrequency of channel c: increment, sign, that channel's LUT phase restarts."""
+        check(abi.lib().sdrhip_tuner_i16_set_shift(self._h, int(c), lut_inc, int(bool(negative))))
+
+    def set_input_format(self, fmt):
+        check(abi.lib().sdrhip_tuner_i16_set_input_format(self._h, fmt))
+        self._cu8 = fmt == abi.IN_CU8
+
+    def reset(self, keep_history=False, keep_fm=False):
+        check(abi.lib().sdrhip_tuner_i16_reset(self._h, int(bool(keep_history)) | (2 if keep_fm else 0)))
+
+
 class BaseBandI16(IQBaseBandI16):
     """BaseBand<int16_t>, the real-input node (reference src/baseband.hh:305-529): int16 samples in, cs16 (or the
     demodulated int16) out. Shares the handle type and every call except create with IQBaseBandI16."""

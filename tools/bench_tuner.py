@@ -1,0 +1,172 @@
+"""Device-resident timing of the tuner bank (sdrhip_tuner_i16_*): ONE input row of 65536 samples per step, C channels each with
+its own tune, for C in {16, 128, 1024} and two plans — "fm127d8" (cs16, 127 taps, /8, FM) and "sdr_fm" (cu8, 21 taps, /125, FM).
+Candidates, all timed in the SAME process, interleaved round by round (HIP events over `reps` steps, `rounds` rounds after
+warm-up; median and range):
+  a  what the library offered before the bank: C one-channel IQBaseBandI16 plans, each with its own tune, run back to back on
+     the same device row
+  b  the headline plan at the same C: C separate input rows, ONE tune (the same arithmetic per channel, C times the input)
+  c  the bank, matrix form          d  the bank, plain form (SDRHIP_TUNER_PATH=valu)
+Before anything is timed one step of c is compared with a's rows bit for bit. Writes profiles/tuner_bench.json, then exits
+non-zero when c was not verified or is not faster than a at some C. c against b is reported (c_over_b), not gated.
+usage: python tools/bench_tuner.py [reps] [rounds] [out.json]"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import libsdr_amd as sa
+
+REPS = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 50
+ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "tuner_bench.json")
+N = 65536
+CHANNELS = (16, 128, 1024)
+PLANS = {"fm127d8": dict(order=127, D=8, Fs=2.4e6, cu8=False), "sdr_fm": dict(order=21, D=125, Fs=1e6, cu8=True)}
+
+
+def tunes(C, order, Fs):
+    """C different tunes spread over 80 % of the band, widths 1 ... 4 % of it."""
+    out = []
+    for c in range(C):
+        Fc = float(int((-0.4 + 0.8 * (c + 0.5) / C) * Fs))
+        out.append((sa.design_iqbb_taps(Fc, (0.01 + 0.03 * (c % 7) / 7) * Fs, Fs, order), sa.design_freqshift_inc(Fc, Fs), Fc < 0))
+    return out
+
+
+def signal(rng, cu8):
+    n = np.arange(N)
+    ph = 2 * np.pi * (0.04 * n + 0.3 * np.sin(2 * np.pi * n / 5000.0))
+    x = np.stack([np.cos(ph), np.sin(ph)], axis=1) * 9000 + rng.normal(0, 2500, (N, 2))
+    if cu8:
+        return np.clip(np.rint(x / 256 + 127.5), 0, 255).astype(np.uint8)
+    return np.rint(x).astype(np.int16)
+
+
+def measure(ctx, fns):
+    """{name: fn} -> {name: {ms, min_ms, max_ms}}: every round times each candidate once, in turn."""
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    ctx.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(ROUNDS):
+        for k, fn in fns.items():
+            t = sa.Timer(ctx)
+            t.start()
+            for _ in range(REPS):
+                fn()
+            t.stop()
+            ms[k].append(t.elapsed_ms() / REPS)
+    out = {}
+    for k, v in ms.items():
+        v.sort()
+        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
+    return out
+
+
+def bank(ctx, tn, lut, D, cu8, valu):
+    old = os.environ.pop("SDRHIP_TUNER_PATH", None)
+    if valu:
+        os.environ["SDRHIP_TUNER_PATH"] = "valu"
+    try:
+        b = sa.TunerBankI16(ctx, np.stack([np.asarray(t[0], np.int32).reshape(-1, 2) for t in tn]), lut, [t[1] for t in tn],
+                            [t[2] for t in tn], D, max_in=N, epilogue=sa.EPI_FM)
+    finally:
+        os.environ.pop("SDRHIP_TUNER_PATH", None)
+        if old is not None:
+            os.environ["SDRHIP_TUNER_PATH"] = old
+    if cu8:
+        b.set_input_format(sa.abi.IN_CU8)
+    return b
+
+
+def singles(ctx, tn, lut, D, cu8):
+    nodes = []
+    for t in tn:
+        nd = sa.IQBaseBandI16(ctx, t[0], lut, t[1], t[2], D, channels=1, max_in=N, epilogue=sa.EPI_FM)
+        if cu8:
+            nd.set_input_format(sa.abi.IN_CU8)
+        nodes.append(nd)
+    return nodes
+
+
+def run_case(ctx, rng, name, p, C):
+    order, D, Fs, cu8 = p["order"], p["D"], p["Fs"], p["cu8"]
+    lut = sa.design_freqshift_lut_i16()
+    tn = tunes(C, order, Fs)
+    x = signal(rng, cu8)
+    eb = 2 if cu8 else 4
+    M = N // D + 2
+    din, dbig = ctx.malloc(N * eb), ctx.malloc(C * N * eb)
+    da, dc = ctx.malloc(C * M * 2), ctx.malloc(C * M * 2)
+    try:
+        ctx.h2d(din, x)
+        ctx.h2d(dbig, np.ascontiguousarray(np.broadcast_to(x, (C,) + x.shape)))
+        # ---- c against a, bit for bit, both from a fresh state --------------------------------------------------------
+        ya, yc = np.full((C, M), 0x5A5A, np.int16), np.full((C, M), 0x5A5A, np.int16)
+        ctx.h2d(da, ya); ctx.h2d(dc, yc)
+        a_nodes, c_bank = singles(ctx, tn, lut, D, cu8), bank(ctx, tn, lut, D, cu8, False)
+        no = c_bank.process_dev(din, N, dc, M)
+        for c, nd in enumerate(a_nodes):
+            assert nd.process_dev(din, N, N, da + c * M * 2, M) == no
+        ctx.synchronize()
+        ctx.d2h(ya, da); ctx.d2h(yc, dc)
+        verified = bool(np.array_equal(ya, yc)) and c_bank.kernel_names == ["tuner_i16_mfma_kernel"]
+        # ---- timing ---------------------------------------------------------------------------------------------------
+        d_bank = bank(ctx, tn, lut, D, cu8, True)
+        b_node = sa.IQBaseBandI16(ctx, tn[0][0], lut, tn[0][1], tn[0][2], D, channels=C, max_in=N, epilogue=sa.EPI_FM)
+        if cu8:
+            b_node.set_input_format(sa.abi.IN_CU8)
+
+        def run_a():
+            for c, nd in enumerate(a_nodes):
+                nd.process_dev(din, N, N, da + c * M * 2, M)
+
+        r = measure(ctx, {"a_one_channel_plans": run_a,
+                          "b_headline_plan": lambda: b_node.process_dev(dbig, N, N, da, M),
+                          "c_bank_hot": lambda: c_bank.process_dev(din, N, dc, M),
+                          "d_bank_plain": lambda: d_bank.process_dev(din, N, dc, M)})
+        r.update({"verified_c_equals_a": verified, "outputs_per_channel": no,
+                  "kernels": {"a": a_nodes[0].kernel_names, "b": b_node.kernel_names, "c": c_bank.kernel_names, "d": d_bank.kernel_names},
+                  "a_over_c": round(r["a_one_channel_plans"]["ms"] / r["c_bank_hot"]["ms"], 2),
+                  "c_over_b": round(r["c_bank_hot"]["ms"] / r["b_headline_plan"]["ms"], 2),
+                  "d_over_c": round(r["d_bank_plain"]["ms"] / r["c_bank_hot"]["ms"], 2)})
+        r["c_faster_than_a"] = r["c_bank_hot"]["ms"] < r["a_one_channel_plans"]["ms"]
+        for nd in a_nodes + [b_node, c_bank, d_bank]:
+            nd.close()
+        return r
+    finally:
+        for q in (din, dbig, da, dc):
+            ctx.free(q)
+
+
+def main():
+    ctx = sa.Context(0)
+    rng = np.random.default_rng(7)
+    result = {"device": ctx.device_name(), "samples_per_step": N, "reps": REPS, "rounds": ROUNDS, "plans": {}}
+    for name, p in PLANS.items():
+        result["plans"][name] = dict(p, channels={})
+        for C in CHANNELS:
+            r = run_case(ctx, rng, name, p, C)
+            result["plans"][name]["channels"][str(C)] = r
+            print(json.dumps({name: {C: r}}), flush=True)
+    ctx.close()
+    cases = [r for p in result["plans"].values() for r in p["channels"].values()]
+    result["conditions"] = {"c_verified_everywhere": all(r["verified_c_equals_a"] for r in cases),
+                            "c_faster_than_a_everywhere": all(r["c_faster_than_a"] for r in cases),
+                            "c_over_b_at_1024": {n: p["channels"]["1024"]["c_over_b"] for n, p in result["plans"].items()}}
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    ok = result["conditions"]["c_verified_everywhere"] and result["conditions"]["c_faster_than_a_everywhere"]
+    print("conditions:", json.dumps(result["conditions"]), "->", "ok" if ok else "FAILED")
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
