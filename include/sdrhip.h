@@ -270,11 +270,20 @@ int sdrhip_iqbb_i16_destroy(sdrhip_iqbb_i16 *h);
  * samples will run): "tuner_i16_mfma_kernel" — the FIR as an int8 GEMM on the matrix cores, channels x time, the
  * sample tile staged once per workgroup and walked by several tiles of 16 channels — for decimations 4 ... 512, taps
  * whose high byte plane fits int8 (on every channel) and calls of at least 512 samples; "tuner_i16_valu_kernel" for every
- * other plan and call. SDRHIP_TUNER_PATH=valu in the environment at create time: the plain kernel only (tests). */
+ * other plan and call. SDRHIP_TUNER_PATH=valu in the environment at create time: the plain kernel only (tests).
+ * SDRHIP_TUNER_CTW=1|2|4|8 in the environment at create time (tests): every matrix-kernel call of the plan walks that many
+ * channel tiles per workgroup instead of the number the launcher picks from the call's size, and the grid follows; any
+ * other value is ignored. Neither changes results. */
 typedef struct sdrhip_tuner_i16 sdrhip_tuner_i16;
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                             const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out);
 int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len);
+/* What a call of n_in samples (1 ... max_in) would launch from the bank's current state, which it does not advance (tests):
+ * info[0] = 1 the matrix kernel, 0 the plain one, info[1] = K steps S of 32 plane bytes, info[2] = decimation groups a time
+ * tile holds (CG), info[3] = of which new ones (OG: FM recomputes one), info[4] = time tiles (grid.x), info[5] = tiles of 16
+ * channels, info[6] = channel tiles one workgroup walks (ctw; 0 for the plain kernel), info[7] = grid.y, info[8] = bytes of
+ * one staged sample plane (0 for the plain kernel), info[9] = dynamic LDS bytes. n >= 10. */
+int sdrhip_tuner_i16_plan_info(sdrhip_tuner_i16 *h, size_t n_in, int *info, int n);
 /* outputs per channel the next call of n_in samples will produce (does not advance the state) */
 int sdrhip_tuner_i16_out_count(sdrhip_tuner_i16 *h, size_t n_in, size_t *n_out);
 /* in: ONE row of n_in samples (cs16, or complex<uint8> after set_input_format); out: channels rows of out_stride

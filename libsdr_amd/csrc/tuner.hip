@@ -300,6 +300,7 @@ struct sdrhip_tuner_i16 {
   uint64_t n0 = 0;
   int par = 0, par_fm = 0;
   bool force_valu = false;
+  int force_ctw = 0;                   // SDRHIP_TUNER_CTW: channel tiles per workgroup of every hot call (0: the launcher's own choice)
   std::vector<int32_t> taps_host;      // C x order x 2
   std::vector<uint32_t> inc_host;
   std::vector<int> neg_host;
@@ -336,6 +337,30 @@ struct sdrhip_tuner_i16 {
   bool hot_plan() const { return !force_valu && misfits == 0 && D >= HOT_MIN_D; }
   bool hot_call(size_t N) const { return hot_plan() && N >= (size_t)HOT_MIN_IN; }
   const char *kernel_name(bool hot) const { return hot ? "tuner_i16_mfma_kernel" : "tuner_i16_valu_kernel"; }
+
+  // what a call of N >= 1 samples with the geometry g launches (launch and sdrhip_tuner_i16_plan_info)
+  struct Plan { bool hot; int CG, OG, tiles, ctw, grid_y, PLB; size_t lds; };
+  Plan plan(size_t N, const Geometry &g) const {
+    Plan p{};
+    p.hot = hot_call(N);
+    p.CG = p.hot ? std::max(HOT_COLS / D, ovl ? 4 : 1) : TI / D;   // (FM recomputes one group per tile: at least 3 of 4 are new)
+    p.OG = p.CG - ovl;
+    const int CGr = (p.CG + 3) & ~3;
+    p.tiles = (int)ceil_div((size_t)g.n_groups, (size_t)p.OG);
+    if (p.hot) {
+      // enough workgroups to fill the device, as many channel tiles per staged sample tile as that leaves
+      int ctw = 8; while (ctw > 1 && (size_t)p.tiles * ceil_div((size_t)ctiles, (size_t)ctw) < 1024) ctw >>= 1;
+      p.ctw = force_ctw ? force_ctw : ctw;
+      const int cols = (p.CG * D + 31) & ~31;
+      p.PLB = (2 * (cols + 16 * S) + 16 + 15) & ~15;
+      p.grid_y = (int)ceil_div((size_t)ctiles, (size_t)p.ctw);
+      p.lds = 1024 + 2 * (size_t)p.PLB + CT * (4 + 4 + 4 + 8) + (size_t)CT * p.CG * 8 + (size_t)CT * 2 * CGr * 4 + 4 * (size_t)CT * TR_STRIDE * 8;
+    } else {
+      p.grid_y = C;
+      p.lds = (TI + (size_t)OP + 8 + 256 + 2 * (size_t)CGr) * 4 + (size_t)TI * 8;
+    }
+    return p;
+  }
 
   void pack_valu(int c, std::vector<uint2> &tp) const {   // zero-padded at the FRONT: the newest sample meets K[order-1]
     const int32_t *k = taps_host.data() + (size_t)c * order * 2;
@@ -415,7 +440,8 @@ struct sdrhip_tuner_i16 {
     if (N == 0) { if (n_out) *n_out = 0; return; }   // empty buffer: nothing moves (src/baseband.hh:200)
     const Geometry g = geometry(N);
     SDRHIP_REQUIRE(out_stride >= (size_t)g.n_out, SDRHIP_E_SIZE, "out_stride %zu < outputs %d", out_stride, g.n_out);
-    const bool hot = hot_call(N);
+    const Plan p = plan(N, g);
+    const bool hot = p.hot;
     TunerArgs t{};
     IqbbArgs &a = t.a;
     a.in = reinterpret_cast<const uint32_t *>(in_dev); a.in_stride = 0; a.in_cu8 = in_cu8;
@@ -427,26 +453,14 @@ struct sdrhip_tuner_i16 {
     a.OP = OP; a.D = D; a.N = (int)N; a.n0_lo = (uint32_t)n0;
     a.base0_rel = g.base0_rel; a.n_groups = g.n_groups; a.n_out = g.n_out; a.extra0 = g.extra0;
     a.ovl = ovl;
-    a.CG = hot ? std::max(HOT_COLS / D, ovl ? 4 : 1) : TI / D;   // (FM recomputes one group per tile: at least 3 of 4 are new)
-    a.OG = a.CG - ovl; a.CGr = (a.CG + 3) & ~3;
+    a.CG = p.CG; a.OG = p.OG; a.CGr = (a.CG + 3) & ~3;
     a.out = out_dev; a.out_stride = (long)out_stride; a.epilogue = epi;
-    a.tiles = (int)ceil_div((size_t)g.n_groups, (size_t)a.OG); a.tpw = 1; a.lpg = 1;
+    a.tiles = p.tiles; a.tpw = 1; a.lpg = 1;
     t.inc = inc.p; t.negative = negative.p; t.phase0 = phase0.p; t.cst = cst.p;
-    t.C = C; t.S = S; t.ctiles = ctiles;
-    dim3 grid; size_t lds;
-    if (hot) {
-      // enough workgroups to fill the device, as many channel tiles per staged sample tile as that leaves
-      int ctw = 8; while (ctw > 1 && (size_t)a.tiles * ceil_div((size_t)ctiles, (size_t)ctw) < 1024) ctw >>= 1;
-      t.ctw = ctw;
-      const int cols = (a.CG * D + 31) & ~31;
-      t.PLB = (2 * (cols + 16 * S) + 16 + 15) & ~15;
-      grid = dim3((unsigned)a.tiles, (unsigned)ceil_div((size_t)ctiles, (size_t)ctw));
-      lds = 1024 + 2 * (size_t)t.PLB + CT * (4 + 4 + 4 + 8) + (size_t)CT * a.CG * 8 + (size_t)CT * 2 * a.CGr * 4 + 4 * (size_t)CT * TR_STRIDE * 8;
-    } else {
-      grid = dim3((unsigned)a.tiles, (unsigned)C);
-      lds = (TI + (size_t)OP + 8 + 256 + 2 * (size_t)a.CGr) * 4 + (size_t)TI * 8;
-    }
-    // (every valid plan fits: the plain form needs at most 44 KB at decimation 1, the matrix form 57 KB at decimation 4 and 513 taps)
+    t.C = C; t.S = S; t.ctiles = ctiles; t.ctw = p.ctw; t.PLB = p.PLB;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.grid_y);
+    const size_t lds = p.lds;
+    // (every valid plan fits: the plain form needs at most 44 KB at decimation 1, the matrix form 55200 B at decimation 4 and 513 taps)
     SDRHIP_REQUIRE(lds <= 64 * 1024, SDRHIP_E_HIP, "internal error: %zu B of LDS for a valid plan", lds);
     if (in_cu8) launch_epi<true>(hot, t, grid, lds); else launch_epi<false>(hot, t, grid, lds);
     SDRHIP_CHECK_HIP(hipGetLastError());
@@ -486,6 +500,7 @@ int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, con
       h->HH = 16 * h->S;   // >= OP, and the whole ring (reset with keep_history)
       h->ctiles = (int)ceil_div((size_t)channels, (size_t)CT);
       { const char *force = getenv("SDRHIP_TUNER_PATH"); h->force_valu = force && !strcmp(force, "valu"); }
+      if (const char *f = getenv("SDRHIP_TUNER_CTW")) { if (f[0] && !f[1] && strchr("1248", f[0])) h->force_ctw = f[0] - '0'; }
       h->taps_host.assign(taps, taps + (size_t)channels * order * 2);
       h->inc_host.assign(lut_inc, lut_inc + channels);
       h->neg_host.resize(channels);
@@ -523,6 +538,16 @@ int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
     snprintf(buf, len, "%s", h->last_names.c_str());
+  });
+}
+
+int sdrhip_tuner_i16_plan_info(sdrhip_tuner_i16 *h, size_t n_in, int *info, int n) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && info && n >= 10, SDRHIP_E_INVALID, "info must hold 10 ints");
+    SDRHIP_REQUIRE(n_in >= 1 && n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu outside [1, max_in %zu]", n_in, h->max_in);
+    const sdrhip_tuner_i16::Plan p = h->plan(n_in, h->geometry(n_in));
+    info[0] = p.hot ? 1 : 0; info[1] = h->S; info[2] = p.CG; info[3] = p.OG; info[4] = p.tiles; info[5] = h->ctiles;
+    info[6] = p.ctw; info[7] = p.grid_y; info[8] = p.PLB; info[9] = (int)p.lds;
   });
 }
 

@@ -363,6 +363,13 @@ class TunerBankI16(_Node):
         check(abi.lib().sdrhip_tuner_i16_kernel_names(self._h, b, 256))
         return b.value.decode().split(",")
 
+    def plan_info(self, n_in):
+        """{hot, S, CG, OG, tiles, ctiles, ctw, grid_y, PLB, lds} of a call of n_in samples from the bank's current state
+        (sdrhip.h: sdrhip_tuner_i16_plan_info)."""
+        v = (C.c_int * 10)()
+        check(abi.lib().sdrhip_tuner_i16_plan_info(self._h, n_in, v, 10))
+        return dict(zip(("hot", "S", "CG", "OG", "tiles", "ctiles", "ctw", "grid_y", "PLB", "lds"), list(v)))
+
     def out_count(self, n_in):
         n = C.c_size_t(0)
         check(abi.lib().sdrhip_tuner_i16_out_count(self._h, n_in, C.byref(n)))

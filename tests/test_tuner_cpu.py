@@ -11,7 +11,7 @@ from libsdr_amd import abi, nodes
 
 LLVM = "/opt/rocm/lib/llvm/bin/"
 TUNER_FUNCTIONS = ["sdrhip_tuner_i16_create", "sdrhip_tuner_i16_destroy", "sdrhip_tuner_i16_kernel_names", "sdrhip_tuner_i16_out_count",
-                   "sdrhip_tuner_i16_process", "sdrhip_tuner_i16_process_dev", "sdrhip_tuner_i16_reset", "sdrhip_tuner_i16_set_input_format",
+                   "sdrhip_tuner_i16_plan_info", "sdrhip_tuner_i16_process", "sdrhip_tuner_i16_process_dev", "sdrhip_tuner_i16_reset", "sdrhip_tuner_i16_set_input_format",
                    "sdrhip_tuner_i16_set_shift", "sdrhip_tuner_i16_set_taps"]
 
 
