@@ -16,21 +16,7 @@ namespace {
 
 constexpr int TPB = 256;
 
-// trunc(num/den) for |num| <= 4096*den, 0 < den < 2^16 (the only divisions fast_atan2 makes): float
-// estimate (|q| <= 4096, error < 1) + one exact remainder correction, instead of the generic 32-bit sequence
-__device__ __forceinline__ int div_small(int num, int den) {
-  const unsigned nu = (unsigned)(num < 0 ? -num : num), de = (unsigned)den;
-  unsigned q = (unsigned)((float)nu * __builtin_amdgcn_rcpf((float)de));   // v_rcp_f32: 1 ulp, |q| <= 4096
-  int r = (int)(nu - __umul24(q, de));
-  if (r < 0) { q -= 1; r += (int)de; }
-  if (r >= (int)de) q += 1;
-  return num < 0 ? -(int)q : (int)q;
-}
-__device__ __forceinline__ short am_i16(int re, int im) {
-  const int m = (int)((unsigned)(re * re) + (unsigned)(im * im));
-  return (short)(int)sqrt((double)m);
-}
-__device__ __forceinline__ short usb_i16(int re, int im) { return (short)((re + im) / 2); }
+// (div_small, am_i16, usb_i16: fm_phi.hpp)
 __device__ __forceinline__ int lo16(uint32_t v) { return (short)(v & 0xffffu); }
 __device__ __forceinline__ int hi16(uint32_t v) { return (short)(v >> 16); }
 

@@ -38,3 +38,24 @@ __device__ __forceinline__ float fm_phi_f(int a, int b) {
 }
 
 __device__ __forceinline__ int fm_phi(int a, int b) { return (int)fm_phi_f(a, b); }
+
+// ---- the other int16 demodulator helpers (fir.hip, demod.hip, iqbb_common.hpp and what includes it) --------------------
+__device__ __forceinline__ int mulw(int a, int b) { return (int)((unsigned)a * (unsigned)b); }   // the reference's wrapping int32 product
+
+// trunc(num/den) for |num| <= 4096*den, 0 < den < 2^16 (the only divisions fast_atan2 makes): float
+// estimate (|q| <= 4096, error < 1) + one exact remainder correction, instead of the generic 32-bit sequence
+__device__ __forceinline__ int div_small(int num, int den) {
+  const unsigned nu = (unsigned)(num < 0 ? -num : num), de = (unsigned)den;
+  unsigned q = (unsigned)((float)nu * __builtin_amdgcn_rcpf((float)de));   // v_rcp_f32: 1 ulp, |q| <= 4096
+  int r = (int)(nu - __umul24(q, de));
+  if (r < 0) { q -= 1; r += (int)de; }
+  if (r >= (int)de) q += 1;
+  return num < 0 ? -(int)q : (int)q;
+}
+
+// AMDemod<int16_t> (src/demod.hh:73-76) and USBDemod<int16_t> (:156-161)
+__device__ __forceinline__ short am_i16(int re, int im) {
+  const int m = (int)((unsigned)mulw(re, re) + (unsigned)mulw(im, im));
+  return (short)(int)sqrt((double)m);
+}
+__device__ __forceinline__ short usb_i16(int re, int im) { return (short)((re + im) / 2); }

@@ -116,12 +116,20 @@ __device__ __forceinline__ int dot2(uint32_t x, uint32_t k, int acc) {
   return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x), __builtin_bit_cast(s16x2, k), acc, false);
 }
 
-__device__ __forceinline__ int mulw(int a, int b) { return (int)((unsigned)a * (unsigned)b); }
-
 // FreqShiftBase<int16_t>::applyFrequencyShift at absolute index n (low 32 bits suffice).
 // Full-rate 24-bit multiplies: only the low 15 bits of n*inc matter; |LUT| < 2^23 (checked at create,
 // the reference's is <= 2^16) and r = S>>14 lies in [-2^17, 2^17), so v_mul_i32_i24's low 32 bits equal
 // the reference's wrapping 32-bit products.
+__device__ __forceinline__ int2 rotate_i16(uint32_t inc, int negative, const int2 *lut_s, int2 r, uint32_t n_lo) {
+  if (inc == 0) return r;
+  uint32_t idx = (__umul24(n_lo & 32767u, inc & 32767u) & 32767u) >> 8;
+  if (negative) idx = 127u - idx;
+  const int2 L = lut_s[idx];
+  int2 v;
+  v.x = (int)((unsigned)__mul24(L.x, r.x) - (unsigned)__mul24(L.y, r.y)) >> 16;
+  v.y = (int)((unsigned)__mul24(L.x, r.y) + (unsigned)__mul24(L.y, r.x)) >> 16;
+  return v;
+}
 __device__ __forceinline__ int2 rotate(const IqbbArgs &a, const int2 *lut_s, int2 r, uint32_t n_lo) {
   if (a.i8) {
     // FreqShiftBase<int8_t> computes in complex<int16_t> (src/freqshift.hh:18-22, src/traits.hh:58-73): the FIR value
@@ -137,14 +145,7 @@ __device__ __forceinline__ int2 rotate(const IqbbArgs &a, const int2 *lut_s, int
     v.y = (int)(short)(mulw(L.x, r.y) + mulw(L.y, r.x)) >> 8;
     return v;
   }
-  if (a.inc == 0) return r;
-  uint32_t idx = (__umul24(n_lo & 32767u, a.inc & 32767u) & 32767u) >> 8;
-  if (a.negative) idx = 127u - idx;
-  const int2 L = lut_s[idx];
-  int2 v;
-  v.x = (int)((unsigned)__mul24(L.x, r.x) - (unsigned)__mul24(L.y, r.y)) >> 16;
-  v.y = (int)((unsigned)__mul24(L.x, r.y) + (unsigned)__mul24(L.y, r.x)) >> 16;
-  return v;
+  return rotate_i16(a.inc, a.negative, lut_s, r, n_lo);
 }
 
 // libstdc++ complex<int32>::operator/=(complex<int32>(D,0)): (a*D)/(D*D), wrapping, truncating
@@ -156,24 +157,7 @@ __device__ __forceinline__ int box_div(int s, int D) {
   return r / n;
 }
 
-// trunc(num/den) for |num| <= 4096*den, 0 < den < 2^16 (the only divisions fast_atan2 makes): float
-// estimate (|q| <= 4096, error < 1) + one exact remainder correction, instead of the generic 32-bit sequence
-__device__ __forceinline__ int div_small(int num, int den) {
-  const unsigned nu = (unsigned)(num < 0 ? -num : num), de = (unsigned)den;
-  unsigned q = (unsigned)((float)nu * __builtin_amdgcn_rcpf((float)de));   // v_rcp_f32: 1 ulp, |q| <= 4096
-  int r = (int)(nu - __umul24(q, de));
-  if (r < 0) { q -= 1; r += (int)de; }
-  if (r >= (int)de) q += 1;
-  return num < 0 ? -(int)q : (int)q;
-}
-
-
-__device__ __forceinline__ short am_i16(int re, int im) {
-  const int m = (int)((unsigned)mulw(re, re) + (unsigned)mulw(im, im));
-  return (short)(int)sqrt((double)m);
-}
-
-__device__ __forceinline__ short usb_i16(int re, int im) { return (short)((re + im) / 2); }
+// (mulw, am_i16, usb_i16, fm_phi: fm_phi.hpp)
 
 // Decimations above 256 on the hot structure (iqbb_hot.hpp, PART): the hot kernel left, per slice of 512 samples, the sums
 // of its stretches between group boundaries; one lane per group adds the stretches that are its own (a group spans

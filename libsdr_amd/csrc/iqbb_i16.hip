@@ -17,6 +17,7 @@
 // against taps packed (Kr,-Ki) and (Ki,Kr)); each lane owns 8 consecutive samples and slides a
 // 16-sample register window over an LDS-staged tile; taps arrive through the scalar cache.
 #include "iqbb_common.hpp"
+#include "iqbb_host.hpp"
 #include "iqbb_hot.hpp"
 
 namespace {
@@ -803,12 +804,11 @@ namespace {
 // A tap set's values must fit the plan's sample type (complex input: int16, real input: 24 bits). Returns whether the high
 // bytes of every value and of its negation fit int8 (the matrix formulations' byte planes); need_planes: an error where not.
 bool check_taps(const int32_t *taps, int order, bool real, bool need_planes) {
-  auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
   bool planes = true;
-  for (int i = 0; i < 2 * order; i++) {   // (both v and -v are packed: Kr, -Ki / Ki, Kr)
-    if (real) SDRHIP_REQUIRE(taps[i] > -(1 << 23) && taps[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "tap %d = %d exceeds 24 bits", i / 2, taps[i]);
-    else SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
-    const bool fits = high_byte(taps[i]) <= 127 && high_byte(-taps[i]) <= 127;
+  for (int i = 0; i < 2 * order; i++) {
+    SDRHIP_REQUIRE(tap_in_range(taps[i], real), SDRHIP_E_UNSUPPORTED,
+                   real ? "tap %d = %d exceeds 24 bits" : "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
+    const bool fits = tap_fits_planes(taps[i]);
     if (need_planes)
       SDRHIP_REQUIRE(fits, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the plan's int8 byte planes: create a new plan", i / 2, taps[i]);
     planes = planes && fits;
@@ -875,34 +875,25 @@ struct sdrhip_iqbb_i16 {
   // Toeplitz byte-plane fragments, their constant term and high- and low-plane step masks (MFMA paths). create and retap.
   void load_taps(const int32_t *taps) {
     ah_mask = 0; al_mask = 0; hot_range = -1; lo_range = -1;
-    // taps: zero-padded at the FRONT (older samples) so that the newest sample still meets K[order-1]
-    std::vector<uint2> tp(OP, make_uint2(0, 0));
-    const int pad = OP - order;
-    for (int i = 0; i < order; i++) {
-      const int kr = taps[2 * i], ki = taps[2 * i + 1];
-      if (real) { tp[pad + i].x = (uint32_t)kr; tp[pad + i].y = (uint32_t)ki; continue; }
-      tp[pad + i].x = ((uint32_t)(uint16_t)(int16_t)kr) | ((uint32_t)(uint16_t)(int16_t)(-ki) << 16);
-      tp[pad + i].y = ((uint32_t)(uint16_t)(int16_t)ki) | ((uint32_t)(uint16_t)(int16_t)kr << 16);
-    }
+    std::vector<uint2> tp(OP);
+    pack_valu_taps(taps, order, OP, real, tp.data());
     if (path == 4) {
       // real input: TapT[m = (t, comp)][k] = K_comp[k - t] over the real sample stream (window of a block = OP - 1 + 16
       // elements, OP = 32S - 15), rows permuted as for path 1; lane (m = l&31, hh = l>>5), byte j of K step s <-> k = 32s+16hh+j
       // (OPm: the window the matrix part covers; the plan's OP is the same at decimation 8 and the VALU kernel's at the others)
       const int OPm = 32 * S - 15, padm = OPm - order;
       std::vector<int> kre(OPm, 0), kim(OPm, 0);
-      unsigned sre = 0, sim = 0;
-      for (int i = 0; i < order; i++) { kre[padm + i] = taps[2 * i]; kim[padm + i] = taps[2 * i + 1]; sre += (unsigned)taps[2 * i]; sim += (unsigned)taps[2 * i + 1]; }
-      cre = (int)(128u * sre); cim = (int)(128u * sim);
+      for (int i = 0; i < order; i++) { kre[padm + i] = taps[2 * i]; kim[padm + i] = taps[2 * i + 1]; }
+      cre = planes_const(kre.data(), OPm); cim = planes_const(kim.data(), OPm);
       std::vector<int8_t> frag((size_t)S * 2 * 64 * 16, 0);
       for (int st = 0; st < S; st++)
         for (int l = 0; l < 64; l++)
           for (int j = 0; j < 16; j++) {
-            const int m = l & 31, hh = l >> 5;
-            const int hC = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
-            const int t = 8 * hC + (r >> 1), comp = r & 1;
+            const int hh = l >> 5;
+            int t, comp, ah, al;
+            hot_row(l & 31, t, comp);
             const int idx = 32 * st + 16 * hh + j - t;
-            const int v = (idx >= 0 && idx < OPm) ? (comp ? kim[idx] : kre[idx]) : 0;
-            const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
+            split_planes((idx >= 0 && idx < OPm) ? (comp ? kim[idx] : kre[idx]) : 0, ah, al);
             frag[(((size_t)(2 * st) * 64 + l) * 16) + j] = (int8_t)ah;
             if (ah != 0) ah_mask |= (uint64_t)1 << st;
             if (al != 0) al_mask |= (uint64_t)1 << st;
@@ -921,25 +912,17 @@ struct sdrhip_iqbb_i16 {
         are[2 * (padm + i)] = kr; are[2 * (padm + i) + 1] = -ki;
         aim[2 * (padm + i)] = ki; aim[2 * (padm + i) + 1] = kr;
       }
-      unsigned sre = 0, sim = 0;
-      for (int k = 0; k < 2 * OPm; k++) { sre += (unsigned)are[k]; sim += (unsigned)aim[k]; }
-      cre = (int)(128u * sre); cim = (int)(128u * sim);
+      cre = planes_const(are.data(), 2 * OPm); cim = planes_const(aim.data(), 2 * OPm);
       std::vector<int8_t> frag((size_t)S * 2 * 64 * 16, 0);
       auto build = [&](bool permuted) {
         for (int st = 0; st < S; st++)
           for (int l = 0; l < 64; l++)
             for (int j = 0; j < 16; j++) {
               const int m = l & 31, hh = l >> 5;
-              int t = m >> 1, comp = m & 1;
-              if (permuted) {   // row permutation: the 32x32 C/D map gives lane half hC = (m>>2)&1 the rows m with register
-                                // r = (m&3) + 4*(m>>3); row m carries sample t = 8*hC + (r>>1), component r&1, so that
-                                // a lane ends up with 8 consecutive samples (decimation 8: one whole group)
-                const int hC = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
-                t = 8 * hC + (r >> 1); comp = r & 1;
-              }
+              int t = m >> 1, comp = m & 1, ah, al;
+              if (permuted) hot_row(m, t, comp);   // a lane ends up with 8 consecutive samples (decimation 8: one whole group)
               const int idx = 32 * st + 16 * hh + j - 2 * t;
-              const int v = (idx >= 0 && idx < 2 * OPm) ? (comp ? aim[idx] : are[idx]) : 0;
-              const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
+              split_planes((idx >= 0 && idx < 2 * OPm) ? (comp ? aim[idx] : are[idx]) : 0, ah, al);
               frag[(((size_t)(2 * st) * 64 + l) * 16) + j] = (int8_t)ah;
               if (ah != 0) ah_mask |= (uint64_t)1 << st;
               if (al != 0) al_mask |= (uint64_t)1 << st;
@@ -990,21 +973,7 @@ struct sdrhip_iqbb_i16 {
   size_t valu_lds() const { return (TI + (size_t)OP + 8 + 256 + 2 * (((size_t)CG + 3) & ~(size_t)3)) * 4 + (fast8 ? 0 : (size_t)TI * 8); }
   int hot_nw() const { int n = 0; const HotRange *rg = hot_ranges(S, &n); return rg[std::min(hot_range, n - 1)].NW; }
 
-  struct Geometry { uint64_t g_first; int n_groups, n_out, base0_rel, extra0; };
-  Geometry geometry(size_t N) const {
-    Geometry g{};
-    // IQBaseBand closes its first window after D+1 samples (:200,:212); the real BaseBand after D (:431-438)
-    const uint64_t D64 = (uint64_t)D, shift1 = (D > 1 && !real) ? 1 : 0;
-    auto group_of = [&](uint64_t n) -> uint64_t { return n < shift1 ? 0 : (n - shift1) / D64; };
-    const uint64_t gf = group_of(n0), gl = group_of(n0 + N - 1);
-    const uint64_t last_end = (gl + 1) * D64 - 1 + shift1;
-    g.g_first = gf;
-    g.n_groups = (int)(gl - gf + 1);
-    g.n_out = g.n_groups - (last_end <= n0 + N - 1 ? 0 : 1);
-    g.base0_rel = (int)((int64_t)(gf * D64 + shift1) - (int64_t)n0);
-    g.extra0 = (n0 == 0 && shift1) ? 1 : 0;
-    return g;
-  }
+  Geometry geometry(size_t N) const { return call_geometry(n0, N, D, real != 0); }
   size_t out_elem_bytes() const { return epi == SDRHIP_EPI_NONE ? (i8 ? 2 : 4) : 2; }
   size_t in_elem_bytes() const { return (in_cu8 || real || i8) ? 2 : 4; }
 
@@ -1507,22 +1476,16 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
 
 }  // namespace
 
-// What IQBaseBand::_reconfigure leaves of the FIR ring (src/baseband.hh:175-177: _ring_offset = 0, the ring's contents
-// stay where they lie), as the history rows (HH_dst entries per channel, oldest first, the newest at the end) of a plan
-// that starts counting at zero: with P = (samples so far) mod order the node afterwards reads the old ring ROTATED —
-// the apparent history, oldest first, is ring[1..order-1], ring[i] = t[order-P+i] (i < P) or t[i-P] (i >= P),
-// t = the last `order` samples in time order (the tail of the source plan's rows).
+// What IQBaseBand::_reconfigure leaves of the source plan's FIR rings, as the history rows (HH_dst entries per channel) of
+// a plan that starts counting at zero (reconfigured_ring_row, iqbb_host.hpp).
 static std::vector<uint32_t> reconfigured_ring(const sdrhip_iqbb_i16 *src, int HH_dst) {
-  const int order = src->order, HH = src->HH, P = src->ring_offset();
+  const int HH = src->HH;
   hipStream_t st = src->ctx->stream;
   std::vector<uint32_t> old((size_t)src->C * HH), neu((size_t)src->C * HH_dst, 0u);
   SDRHIP_CHECK_HIP(hipMemcpyAsync(old.data(), src->hist[src->par].p, old.size() * 4, hipMemcpyDeviceToHost, st));
   SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
-  for (int c = 0; c < src->C; c++) {
-    const uint32_t *t = old.data() + (size_t)c * HH + (HH - order);
-    uint32_t *d = neu.data() + (size_t)c * HH_dst + (HH_dst - (order - 1));
-    for (int k = 0; k + 1 < order; k++) { const int i = k + 1; d[k] = i < P ? t[order - P + i] : t[i - P]; }
-  }
+  for (int c = 0; c < src->C; c++)
+    reconfigured_ring_row(old.data() + (size_t)c * HH, HH, src->order, src->ring_offset(), neu.data() + (size_t)c * HH_dst, HH_dst);
   return neu;
 }
 

@@ -1,13 +1,18 @@
 // tuner.hip — the tuner bank: C independent IQBaseBand<int16_t> channels (+ fused FM / AM / USB demodulator) over ONE
 // shared input row (sdrhip.h, "tuner bank"). Shared by all channels: the input, ONE FIR history, the absolute sample
 // index, order, decimation, epilogue, the LUT. Per channel: taps, LUT increment, sign and phase origin, the open window's
-// partial sum, the FM angle. Reference arithmetic as iqbb_common.hpp lists it; every helper of the one-tune plan
-// (load_x, rotate, finalize_group, epilogue_and_roll, box_div, am_i16, usb_i16, fm_phi) is used as it is: a channel of the
-// bank is presented to them as a one-channel IqbbArgs view (channel_view) and they are called with channel index 0.
+// partial sum, the FM angle. Reference arithmetic as iqbb_common.hpp lists it. A channel of the bank is presented to the
+// one-tune plan's device helpers as a one-channel IqbbArgs view (channel_view) with channel index 0, and the host rules
+// come from the header the one-tune plan (iqbb_i16.hip) takes them from:
+//   iqbb_common.hpp   load_x, rotate / rotate_i16, finalize_group, epilogue_and_roll (and through them box_div; am_i16,
+//                     usb_i16, fm_phi: fm_phi.hpp)
+//   iqbb_host.hpp     call_geometry, tap_in_range, tap_fits_planes, pack_valu_taps, split_planes, planes_const, hot_row,
+//                     reconfigured_ring_row
 //
 // Two kernels, both bit-exact:
 //   tuner_i16_valu_kernel   v_dot2 FIR at 8 consecutive samples per lane, one workgroup per (time tile, channel): every
-//                           valid plan (order 1 ... 513, decimation 1 ... 512, any call length).
+//                           valid plan (order 1 ... 513, decimation 1 ... 512, any call length). Still a COPY of
+//                           iqbb_i16_kernel<false, false>'s body (iqbb_common.hpp), to be kept equal line for line.
 //   tuner_i16_mfma_kernel   the FIR as an int8 GEMM on v_mfma_i32_32x32x32_i8 with CHANNELS as matrix rows:
 //                             Y[(channel, comp)][t] = sum_k A[(channel, comp)][k] * U[k][t],   U[k][t] = u[2 (t - KW + 1) + k]
 //                           u = the interleaved (re, im) int16 stream of the ONE input, KW = 16 S the padded filter length,
@@ -21,6 +26,7 @@
 //                           (channel, group) box sums in LDS (through a wave-private transpose tile; wrapping int32 adds commute: ds_add_u32). Decimations 4 ... 512,
 //                           taps whose high byte plane fits int8, calls of at least HOT_MIN_IN samples.
 #include "iqbb_common.hpp"
+#include "iqbb_host.hpp"
 
 #include <algorithm>
 #include <string>
@@ -142,9 +148,9 @@ __global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) 
 // parameters; gsum[CT][CG] box sums; ybuf[CT][2 CGr] results and FM angle cache (finalize_group's layout per channel);
 // one [CT][TR_STRIDE] transpose tile per wave.
 // Tap fragments (host: pack_tile): v4i index ((ct * S + s) * 2 + plane) * 64 + lane; lane (m = l & 31, hh = l >> 5) holds
-// bytes k = 32 s + 16 hh + j of row m, and row m carries channel 8 hC + (r >> 1), component r & 1 with hC = (m >> 2) & 1,
-// r = (m & 3) + 4 (m >> 3): by the 32x32 C/D map lane (n, h) then holds, in accumulator registers 2j / 2j + 1, (re, im) of
-// channel 8 h + j of the tile at time column n.
+// bytes k = 32 s + 16 hh + j of row m, and row m carries the channel and component that hot_row (iqbb_host.hpp) gives:
+// by the 32x32 C/D map lane (n, h) then holds, in accumulator registers 2j / 2j + 1, (re, im) of channel 8 h + j of the
+// tile at time column n.
 template <int EPI, bool CU8>
 __global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -235,10 +241,7 @@ __global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs 
         const unsigned sr = ((unsigned)acc_hh[2 * j] << 16) + ((unsigned)acc_mid[2 * j] << 8) + (unsigned)acc_ll[2 * j];
         const unsigned si = ((unsigned)acc_hh[2 * j + 1] << 16) + ((unsigned)acc_mid[2 * j + 1] << 8) + (unsigned)acc_ll[2 * j + 1];
         int2 v = make_int2(0, 0);            // outside the call or the tile: r = 0 -> v = 0
-        if (valid) {
-          IqbbArgs rot; rot.i8 = 0; rot.inc = cinc[cl]; rot.negative = cneg[cl];
-          v = rotate(rot, lut_s, make_int2((int)sr >> 14, (int)si >> 14), cn0[cl] + (uint32_t)rel);
-        }
+        if (valid) v = rotate_i16(cinc[cl], cneg[cl], lut_s, make_int2((int)sr >> 14, (int)si >> 14), cn0[cl] + (uint32_t)rel);
         tr[cl * TR_STRIDE + n] = v;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -283,13 +286,6 @@ __global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs 
   }
 }
 
-bool taps_fit_planes(const int32_t *taps, int order) {
-  auto high_byte = [](int v) { const int al = ((v + 128) & 255) - 128; return (v - al) >> 8; };
-  for (int i = 0; i < 2 * order; i++)   // (both v and -v are packed: Kr, -Ki / Ki, Kr)
-    if (high_byte(taps[i]) > 127 || high_byte(-taps[i]) > 127) return false;
-  return true;
-}
-
 }  // namespace
 
 struct sdrhip_tuner_i16 {
@@ -317,21 +313,7 @@ struct sdrhip_tuner_i16 {
   DevBuf<uint32_t> stage_in, stage_out;
   std::string last_names;
 
-  // the geometry of a call of N samples from absolute index n0 on (sdrhip_iqbb_i16::geometry for complex input:
-  // IQBaseBand closes its first window after D + 1 samples, src/baseband.hh:200,212)
-  struct Geometry { int n_groups, n_out, base0_rel, extra0; };
-  Geometry geometry(size_t N) const {
-    Geometry g{};
-    const uint64_t D64 = (uint64_t)D, shift1 = D > 1 ? 1 : 0;
-    auto group_of = [&](uint64_t n) -> uint64_t { return n < shift1 ? 0 : (n - shift1) / D64; };
-    const uint64_t gf = group_of(n0), gl = group_of(n0 + N - 1);
-    const uint64_t last_end = (gl + 1) * D64 - 1 + shift1;
-    g.n_groups = (int)(gl - gf + 1);
-    g.n_out = g.n_groups - (last_end <= n0 + N - 1 ? 0 : 1);
-    g.base0_rel = (int)((int64_t)(gf * D64 + shift1) - (int64_t)n0);
-    g.extra0 = (n0 == 0 && shift1) ? 1 : 0;
-    return g;
-  }
+  Geometry geometry(size_t N) const { return call_geometry(n0, N, D, false); }
   size_t out_elem_bytes() const { return epi == SDRHIP_EPI_NONE ? 4 : 2; }
   size_t in_elem_bytes() const { return in_cu8 ? 2 : 4; }
   bool hot_plan() const { return !force_valu && misfits == 0 && D >= HOT_MIN_D; }
@@ -362,44 +344,32 @@ struct sdrhip_tuner_i16 {
     return p;
   }
 
-  void pack_valu(int c, std::vector<uint2> &tp) const {   // zero-padded at the FRONT: the newest sample meets K[order-1]
-    const int32_t *k = taps_host.data() + (size_t)c * order * 2;
-    const int pad = OP - order;
-    for (int i = 0; i < OP; i++) tp[i] = make_uint2(0, 0);
-    for (int i = 0; i < order; i++) {
-      const int kr = k[2 * i], ki = k[2 * i + 1];
-      tp[pad + i].x = ((uint32_t)(uint16_t)(int16_t)kr) | ((uint32_t)(uint16_t)(int16_t)(-ki) << 16);
-      tp[pad + i].y = ((uint32_t)(uint16_t)(int16_t)ki) | ((uint32_t)(uint16_t)(int16_t)kr << 16);
-    }
-  }
   // channel tile ct's fragments (S x 2 x 64 x 16 bytes) and its channels' constant terms (layout: tuner_i16_mfma_kernel)
   void pack_tile(int ct, std::vector<int8_t> &frag, int2 *cst_tile) const {
     const int KW = 16 * S, pad = KW - order;
     std::vector<int> are((size_t)CT * 2 * KW, 0), aim((size_t)CT * 2 * KW, 0);
     for (int cl = 0; cl < CT; cl++) {
       const int c = ct * CT + cl;
-      unsigned sre = 0, sim = 0;
+      int *re = are.data() + (size_t)cl * 2 * KW, *im = aim.data() + (size_t)cl * 2 * KW;
       if (c < C && fits[c]) {
         const int32_t *k = taps_host.data() + (size_t)c * order * 2;
-        int *re = are.data() + (size_t)cl * 2 * KW, *im = aim.data() + (size_t)cl * 2 * KW;
         for (int i = 0; i < order; i++) {
           const int kr = k[2 * i], ki = k[2 * i + 1];
           re[2 * (pad + i)] = kr; re[2 * (pad + i) + 1] = -ki;
           im[2 * (pad + i)] = ki; im[2 * (pad + i) + 1] = kr;
         }
-        for (int x = 0; x < 2 * KW; x++) { sre += (unsigned)re[x]; sim += (unsigned)im[x]; }
       }
-      cst_tile[cl] = make_int2((int)(128u * sre), (int)(128u * sim));
+      cst_tile[cl] = make_int2(planes_const(re, 2 * KW), planes_const(im, 2 * KW));
     }
     frag.assign((size_t)S * 2 * 64 * 16, 0);
     for (int st = 0; st < S; st++)
       for (int l = 0; l < 64; l++) {
-        const int m = l & 31, hh = l >> 5, hC = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
-        const int cl = 8 * hC + (r >> 1), comp = r & 1;
+        const int hh = l >> 5;
+        int cl, comp, ah, al;
+        hot_row(l & 31, cl, comp);
         const int *row = (comp ? aim.data() : are.data()) + (size_t)cl * 2 * KW;
         for (int j = 0; j < 16; j++) {
-          const int v = row[32 * st + 16 * hh + j];
-          const int al = ((v + 128) & 255) - 128, ah = (v - al) >> 8;
+          split_planes(row[32 * st + 16 * hh + j], ah, al);
           frag[((size_t)(2 * st) * 64 + l) * 16 + j] = (int8_t)ah;
           frag[((size_t)(2 * st + 1) * 64 + l) * 16 + j] = (int8_t)al;
         }
@@ -415,7 +385,7 @@ struct sdrhip_tuner_i16 {
   }
   void upload_valu(int c) {
     std::vector<uint2> tp(OP);
-    pack_valu(c, tp);
+    pack_valu_taps(taps_host.data() + (size_t)c * order * 2, order, OP, false, tp.data());
     SDRHIP_CHECK_HIP(hipMemcpyAsync(taps.p + (size_t)c * OP, tp.data(), (size_t)OP * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
     SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   }
@@ -486,7 +456,7 @@ int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, con
     SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
     SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
     for (size_t i = 0; i < (size_t)channels * order * 2; i++)
-      SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
+      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
                      i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
     for (int i = 0; i < 256; i++)
       SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
@@ -506,12 +476,12 @@ int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, con
       h->neg_host.resize(channels);
       for (int c = 0; c < channels; c++) h->neg_host[c] = negative[c] ? 1 : 0;
       h->fits.resize(channels);
-      for (int c = 0; c < channels; c++) { h->fits[c] = taps_fit_planes(taps + (size_t)c * order * 2, order); h->misfits += h->fits[c] ? 0 : 1; }
+      for (int c = 0; c < channels; c++) { const int32_t *k = taps + (size_t)c * order * 2; h->fits[c] = std::all_of(k, k + 2 * order, tap_fits_planes); h->misfits += h->fits[c] ? 0 : 1; }
       hipStream_t st = ctx->stream;
       h->taps.alloc((size_t)channels * h->OP);
       {
-        std::vector<uint2> all((size_t)channels * h->OP), one(h->OP);
-        for (int c = 0; c < channels; c++) { h->pack_valu(c, one); std::copy(one.begin(), one.end(), all.begin() + (size_t)c * h->OP); }
+        std::vector<uint2> all((size_t)channels * h->OP);
+        for (int c = 0; c < channels; c++) pack_valu_taps(taps + (size_t)c * order * 2, order, h->OP, false, all.data() + (size_t)c * h->OP);
         h->taps.upload(all.data(), all.size(), st);
       }
       h->tapfrag.alloc((size_t)h->ctiles * h->S * 2 * 64);
@@ -602,11 +572,11 @@ int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *t
     SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
     SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
     for (int i = 0; i < 2 * h->order; i++)
-      SDRHIP_REQUIRE(taps[i] >= -32767 && taps[i] <= 32767, SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
+      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
     h->ctx->use();
     std::copy(taps, taps + (size_t)h->order * 2, h->taps_host.begin() + (size_t)channel * h->order * 2);
     // (taps whose high byte plane does not fit int8 move the whole bank to the plain form until they are replaced)
-    const bool fit = taps_fit_planes(taps, h->order);
+    const bool fit = std::all_of(taps, taps + 2 * h->order, tap_fits_planes);
     h->misfits += (h->fits[channel] ? 0 : -1) + (fit ? 0 : 1);
     h->fits[channel] = fit;
     h->upload_valu(channel);   // stream-ordered after the launches already enqueued
@@ -644,8 +614,8 @@ int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history) {
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     h->ctx->use();
     hipStream_t st = h->ctx->stream;
-    // bit 0: the FIR ring survives, read ROTATED afterwards (IQBaseBand::_reconfigure, src/baseband.hh:175-177: _ring_offset = 0,
-    // the contents stay where they lie); bit 1: so do the fused FMDemod's last angles (sdrhip_iqbb_i16_reset)
+    // bit 0: the FIR ring survives, read ROTATED afterwards (reconfigured_ring_row, iqbb_host.hpp); bit 1: so do the fused
+    // FMDemod's last angles (sdrhip_iqbb_i16_reset)
     const bool keep_fm = (keep_history & 2) != 0;
     keep_history &= 1;
     for (int p = 0; p < 2; p++) { h->acc[p].zero(st); if (!keep_fm) h->fm[p].zero(st); }
@@ -653,15 +623,11 @@ int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history) {
     if (!keep_history) {
       for (int p = 0; p < 2; p++) h->hist[p].zero(st);
     } else if (P != 0) {
-      // apparent history afterwards, oldest first: ring[1 .. order-1], ring[i] = t[order-P+i] (i < P) or t[i-P] (i >= P),
-      // t = the last `order` samples in time order (the tail of the row)
-      const int order = h->order, HH = h->HH;
+      const int HH = h->HH;
       std::vector<uint32_t> old(HH), neu(HH, 0u);
       SDRHIP_CHECK_HIP(hipMemcpyAsync(old.data(), h->hist[h->par].p, (size_t)HH * 4, hipMemcpyDeviceToHost, st));
       SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
-      const uint32_t *t = old.data() + (HH - order);
-      uint32_t *d = neu.data() + (HH - (order - 1));
-      for (int k = 0; k + 1 < order; k++) { const int i = k + 1; d[k] = i < P ? t[order - P + i] : t[i - P]; }
+      reconfigured_ring_row(old.data(), HH, h->order, P, neu.data(), HH);
       SDRHIP_CHECK_HIP(hipMemcpyAsync(h->hist[h->par].p, neu.data(), (size_t)HH * 4, hipMemcpyHostToDevice, st));
       SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
     }
