@@ -140,11 +140,7 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
   // of 4 per 64: a lane's 64-byte group then starts 16 (t >> 2) + 64 t bytes in, so the 16 lanes of one ds_read_b128 /
   // ds_write_b128 cover all 16 slots of a bank row, and the radix-16 stride-8 pass (8 lanes per 64 contiguous bytes,
   // neighbouring octets 1088 bytes apart) stays conflict-free as before.
-#ifdef K7_NO_TAIL8   // (A/B: the four-pass LDS form)
-  constexpr bool TAIL8 = false;
-#else
   constexpr bool TAIL8 = LG == 11 && NT == 128;
-#endif
   auto P = [](int i) { return TAIL8 ? i + ((i >> 5) << 1) : PAD(i); };
   const int L = LG ? (1 << LG) : p.L, np = LG ? plan_npass(LG) : p.npass;
   const int np_lds = TAIL8 ? np - 1 : np;   // passes that go through LDS (TAIL8: the last two are one register step)
@@ -166,35 +162,17 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
   // the loop and spilled there: 79 registers' worth, reloaded one by one through scratch, i.e. through vmcnt)
   auto lane = [&]() { int t = tid0; if (LG == 0 || PIPE) { asm volatile("" : "+v"(t)); __builtin_assume(t >= 0 && t < NT); } return t; };
   // WAVE_LOCAL: the passes between the first forward and the last inverse pass need no workgroup barrier (see below). 16384 points
-  // on 1024 lanes (a segment = one wave). -DK7_WL_MID=1: also 8192 points on 512 lanes and 4096 on 256 (a segment = 32 / 16 lanes of
-  // ONE wave; the radix-2 butterflies of the 8192-point middle pass re-mapped to the lane group's own segment) — parity green, time
-  // +-0 on FilterNode(2048) / (4096) / (1000) (0.114 / 0.096 / 0.087 ms either way: two to eight workgroups per CU cover each other's
-  // barriers), so they keep their barrier per pass
-#ifndef K7_WL_MID
-#define K7_WL_MID 0
-#endif
-  constexpr bool WAVE_LOCAL = !BANK && ((LG == 14 && NT == 1024) || (K7_WL_MID && ((LG == 13 && NT == 512) || (LG == 12 && NT == 256))));
-  // (K7_PRIO, 16384 points) between two barriers the waves of a SIMD run at their own pace and the arbiter prefers the oldest: wave 0
+  // on 1024 lanes (a segment = one wave). The smaller sizes keep their barrier per pass: two to eight workgroups per CU cover each
+  // other's barriers (wave-local 8192 / 4096 points measured +-0 on FilterNode(2048) / (4096) / (1000)).
+  constexpr bool WAVE_LOCAL = !BANK && LG == 14 && NT == 1024;
+  // (16384 points) between two barriers the waves of a SIMD run at their own pace and the arbiter prefers the oldest: wave 0
   // arrives at the next barrier 12 600 clocks of a 32 300-clock turn before the last one (stamps), and the last one runs alone, its
   // LDS latencies uncovered. Priority by progress — the further along, the lower — keeps the four together.
 // sites: forward passes 1, 2, the middle pass, inverse pass 2 (and behind its butterfly), inverse pass 1 (and in front of its
-// butterfly), the last pass (and behind its butterfly), pass 0 (and behind its butterfly); K7_PRIO picks the level table
-#ifndef K7_PRIO
-#define K7_PRIO 1   // (A/B on one box, 4097 taps: table 1 0.3868 ms, 3 0.3903, 2 0.3944, none 0.4135; -DK7_PRIO=0: none)
-#endif
-#if K7_PRIO
+// butterfly), the last pass (and behind its butterfly), pass 0 (and behind its butterfly). The levels: A/B on one box, 4097 taps,
+// 0.3868 ms against 0.3903 / 0.3944 for two other tables and 0.4135 without priorities
   enum { S_F1, S_F2, S_MID, S_I2, S_I2B, S_I1, S_I1B, S_LAST, S_LASTB, S_P0, S_P0B };
-#if K7_PRIO == 1
-#define K7_PRIO_TAB {3, 2, 2, 1, 1, 0, 0, 3, 3, 1, 1}
-#elif K7_PRIO == 2
-#define K7_PRIO_TAB {3, 3, 2, 1, 1, 0, 0, 3, 2, 1, 0}
-#else
-#define K7_PRIO_TAB {3, 3, 3, 2, 1, 1, 0, 3, 2, 1, 0}
-#endif
-#define K7_SETPRIO(site_) do { if (WAVE_LOCAL) { constexpr int tab_[] = K7_PRIO_TAB; __builtin_amdgcn_s_setprio(tab_[site_]); } } while (0)
-#else
-#define K7_SETPRIO(site_) do { } while (0)
-#endif
+#define K7_SETPRIO(site_) do { if (WAVE_LOCAL) { constexpr int tab_[] = {3, 2, 2, 1, 1, 0, 0, 3, 3, 1, 1}; __builtin_amdgcn_s_setprio(tab_[site_]); } } while (0)
 #ifdef K7_STAMPS   // diagnostic build: wave 0 of every workgroup sums the shader clocks between its phase boundaries
   const bool st_on = PIPE && __builtin_amdgcn_readfirstlane(tid0) == 0;
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_amdgcn_s_memtime(), st_turns = 0;
@@ -262,21 +240,6 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
     lp_mid = xl + P(4 * ((tid0 >> 6) * 256 + (tid0 & 63)));
   }
   auto X = [&](float2 *lp, int base, int off) -> float2 & { return PIPE ? lp[off + ((off >> 6) << 2)] : xl[P(base + off)]; };
-  // (PIPE, tuning variant -DK7_LDS_TW=1) the twiddles of the stride-64 and stride-4 passes in LDS behind the image (15 x 64 + 15 x 4
-  // entries, 8 KB of the 21 KB the image leaves), copied once per workgroup from the plan's tables: 15 ds_read_b64 per pass instead
-  // of 2 global loads + 11 complex products. Measured +-0 (0.3655 against 0.3636 ms, profiles/r18_k7_pipe_ab.txt) and no longer
-  // bit-identical to the one-block kernel (table entries against products): off.
-#ifndef K7_LDS_TW
-#define K7_LDS_TW 0
-#endif
-  constexpr bool LTW = PIPE && K7_LDS_TW;
-  float2 *ltw64 = xl, *ltw4 = xl;
-  if (LTW) {
-    float2 *tab = xl + (L + (L >> 6) * 4);
-    if (tid0 < 15 * 64) tab[tid0] = p.T[p.toff[1] + tid0];
-    if (tid0 < 15 * 4) tab[15 * 64 + tid0] = p.T[p.toff[2] + tid0];
-    ltw64 = tab + (tid0 & 63); ltw4 = tab + 15 * 64 + (tid0 & 3);   // (visible behind the barrier that closes the first pass 0)
-  }
   // (PIPE) pass 0 of the block whose inputs the prefetch brought: registers -> LDS. Runs at the END of a turn (and once in front
   // of the loop), so that the prefetched registers are written and read inside one turn: carried around the loop's back edge the
   // register allocator moved two of the 32 to other registers there — a copy of a register a load is still writing, i.e. a full wait
@@ -327,11 +290,7 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
       pass0_pipe(blk * a.hop - a.HH - a.delay, false);
     }
   } else {
-#ifdef FFTCONV_NO_XCD   // (tuning: launch-order assignment)
-    c = blockIdx.y; blk = blockIdx.x;
-#else
     xcd_unit_order(blk, c);
-#endif
   }
   // After the first radix-16 pass the transform splits into 16 independent segments of L/16 points, and with one
   // butterfly per lane (NT = L/16) the butterflies of a segment belong to consecutive lanes: for L = 16384 a segment is
@@ -360,12 +319,6 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
     const bool vec_in = first >= 0 && first + L <= a.N && ((reinterpret_cast<uintptr_t>(src) & 15) == 0) && (s & 1) == 0 && s >= FT;
     for (int j = tid; j < s; j += FT) {
       float2 v[16], w[16];
-#ifdef K7_PROBE_NOLOAD   // (ceiling probe, results wrong: pass 0 makes its inputs up — what the block costs with its global loads hidden completely)
-      if (a.N > 0) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = make_float2((float)(j + k), (float)(tid - k));
-      } else
-#endif
       if (vec_in) {
         const int odd = j & 1, je = j & ~1;
 #pragma unroll
@@ -404,10 +357,7 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = X(s == 64 ? lp_s64 : lp_s4, base, k * s);
         dft16<-1>(v);
-        if (LTW) {
-#pragma unroll
-          for (int k = 1; k < 16; k++) w[k] = (s == 64 ? ltw64 : ltw4)[(k - 1) * s];
-        } else twiddles16(p, pass, s, j, w);
+        twiddles16(p, pass, s, j, w);
 #pragma unroll
         for (int k = 1; k < 16; k++) v[k] = cmul(v[k], w[k]);
 #pragma unroll
@@ -453,17 +403,10 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
     for (int m = 0; m < 4; m++)
       *reinterpret_cast<float4 *>(img + P(8 * g + 2 * m)) = make_float4(e[2 * m].x, e[2 * m].y, e[2 * m + 1].x, e[2 * m + 1].y);
   };
-  // which group a lane owns: lane order. (-DK7_GROUP_PERM: lane bits (0, 1, 2, 3) -> group bits (0, 2, 3, 1), which makes
-  // the ds_write_b128 groups of 8 lanes conflict-free — in lane order they land on 4 of the 8 slots of a 128-byte row, two
-  // by two: every conflict cycle the TAIL8 kernel has left, counter = model = 256 per wave and block — at the price of one
-  // extra cycle on each ds_read_b128. Counters: SQ_LDS_BANK_CONFLICT 33.5 M -> 4.2 M of 180 M / 151 M LDS cycles; time,
-  // three interleaved runs on one box: 1.040 -> 1.115 ms. The reads sit on the dependent path, the stores do not (a
-  // ds_write_b128 costs its 13-cycle register transfer either way): the layout with FEWER conflicts is 7 % slower. Off.)
-#ifdef K7_GROUP_PERM
-  auto group_of = [](int t) { return (t & ~0xE) | (((t >> 1) & 1) << 2) | (((t >> 2) & 1) << 3) | (((t >> 3) & 1) << 1); };
-#else
+  // which group a lane owns: lane order. (The ds_write_b128 groups of 8 lanes land on 4 of the 8 slots of a 128-byte row — every
+  // conflict cycle the TAIL8 kernel has left. A conflict-free lane-to-group permutation cost one cycle more on each ds_read_b128, which
+  // sits on the dependent path: 7 % slower with an eighth of the conflicts.)
   auto group_of = [](int t) { return t; };
-#endif
   if (BANK && TAIL8) {
     const int tid = group_of(lane());
     load8(xl, tid, fwd); load8(xl, tid + FT, fwd + 8);
@@ -601,10 +544,8 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
     n *= r;
     const int tw = L / n;
     if (PIPE && pass == 1) {   // the tail's own global loads first, then the next block's inputs (vmcnt is in issue order)
-      if (!LTW) {
-        const float2 *t1 = p.T + p.toff[1] + (tid & (s - 1));
-        pf_tw[0] = t1[0]; pf_tw[1] = t1[3 * s];
-      }
+      const float2 *t1 = p.T + p.toff[1] + (tid & (s - 1));
+      pf_tw[0] = t1[0]; pf_tw[1] = t1[3 * s];
       K7_STAMP(0, tid);
       __builtin_amdgcn_sched_barrier(0);
       prefetch(uk + uk_step < uk_end ? uk + uk_step : uk, uk + uk_step < uk_end);
@@ -617,10 +558,7 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
         float2 v[16], w[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = X(s == 64 ? lp_s64 : lp_s4, base, k * s);   // (xw is xl: one band)
-        if (LTW) {
-#pragma unroll
-          for (int k = 1; k < 16; k++) v[k] = cmulc(v[k], (s == 64 ? ltw64 : ltw4)[(k - 1) * s]);
-        } else if (PIPE && pass == 1) twiddle_apply_seeded<true>(v, pf_tw[0], pf_tw[1]);
+        if (PIPE && pass == 1) twiddle_apply_seeded<true>(v, pf_tw[0], pf_tw[1]);
         else {
           twiddles16(p, pass, s, j, w);
 #pragma unroll
@@ -723,11 +661,7 @@ __global__ __launch_bounds__(NT) void fftconv_fused_kernel(const ConvArgs a) {
           const float rx = lane_xor1(give.x), ry = lane_xor1(give.y);
           const float4 q = odd ? make_float4(rx, ry, v[2 * m + 1].x, v[2 * m + 1].y) : make_float4(v[2 * m].x, v[2 * m].y, rx, ry);
           const int i = je + (2 * m + odd) * s;
-#ifdef K7_PROBE_NOSTORE   // (ceiling probe, results missing: the stores sit behind a condition that is never true at run time)
-          if (i >= a.HH && a.N < 0) {
-#else
           if (i >= a.HH) {
-#endif
             if (ACC) { const float4 t = *reinterpret_cast<const float4 *>(dst + i); *reinterpret_cast<float4 *>(dst + i) = make_float4(q.x + t.x, q.y + t.y, q.z + t.z, q.w + t.w); }
             else *reinterpret_cast<float4 *>(dst + i) = q;
           }
@@ -1242,7 +1176,7 @@ struct sdrhip_fftconv {
       const bool pv = even(hop) && even(HH) && even(HL) && even(a.delay) && even(N) && even(in_stride) && even(out_stride) &&
                       (reinterpret_cast<uintptr_t>(in_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
                       getenv("SDRHIP_K7_PIPE_X2") == nullptr;   // (A/B hook: the 8-byte form everywhere)
-      const size_t lds_p = lds + (15 * 64 + 15 * 4) * sizeof(float2);   // (+ room for the K7_LDS_TW variant's tables)
+      const size_t lds_p = lds + (15 * 64 + 15 * 4) * sizeof(float2);   // (7.5 KB beyond the image that the kernel does not use: the launches were measured with it)
       auto go = [&](auto kernel) {
         allow_big_lds(kernel, lds_p);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), lds_p, ctx->stream, a);

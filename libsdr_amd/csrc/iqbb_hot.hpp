@@ -61,27 +61,15 @@ constexpr int hot_win(int S, int in) { return 512 + hot_halo(S, in) + (in == HOT
 // bytes per byte plane: complex kinds 2 per sample (+ one chunk pair: both parity halves 16-byte aligned), real 1 per sample
 constexpr int hot_plb(int S, int in) { return in == HOT_REAL ? hot_win(S, in) : 2 * hot_win(S, in) + 32; }
 constexpr int hot_bufb(int S, int in) { return hot_one_plane(in) ? hot_plb(S, in) : 2 * hot_plb(S, in); }   // one window buffer
-// -DK1_PAIR (tuning variant, D = 8, complex<int16>, 4-wave workgroups; build with -DK1_MINWAVES=2, run with
-// SDRHIP_IQBB_WGPCU=2): a wave works on TWO slices at a time — consecutive tiles of its unit — so that one read of a tap
-// fragment feeds the MFMAs of both (6 accumulators, 4 window buffers per wave, 2 waves per SIMD)
-#ifdef K1_PAIR
-constexpr bool hot_pair(int in, int NW, bool dg) { return !dg && in == HOT_CS16 && NW == 4; }
-#else
-constexpr bool hot_pair(int, int, bool) { return false; }
-#endif
-constexpr int hot_lds_bytes(int S, int NH, int in, int NW, bool wide, bool pair = false) {
-  return (wide ? 4096 : 1024) + (S + NH) * 1024 + NW * (pair ? 4 : 2) * hot_bufb(S, in);
+constexpr int hot_lds_bytes(int S, int NH, int in, int NW, bool wide) {
+  return (wide ? 4096 : 1024) + (S + NH) * 1024 + NW * 2 * hot_bufb(S, in);
 }
 // 4 waves per SIMD: 160 KB / workgroups per CU. (S = 33, orders 258 ... 513: 33 ... 66 KB of tap fragments and 1024-sample windows —
 // ONE 8-wave workgroup per CU, two waves per SIMD: its 70 ... 132 MFMAs per slice keep the matrix pipe busy behind one
 // wave's vector phase)
-constexpr int hot_lds_cap(int NW, bool pair = false, int S = 0) { return S >= 33 ? 163840 : NW == 4 ? (pair ? 81920 : 40960) : NW == 8 ? 81920 : 163840; }
+constexpr int hot_lds_cap(int NW, int S = 0) { return S >= 33 ? 163840 : NW == 4 ? 40960 : NW == 8 ? 81920 : 163840; }
 // 4 KB rotation table ({Lx, Ly, -Ly, 0} x 256: one SDWA shift makes the address, no subtraction) while it fits
-#ifdef K1_NARROW_LUT   // (tuning: the 1 KB {Lx, Ly} table everywhere — half the rotation's LDS bytes, one subtraction more per sample)
-constexpr bool hot_wide(int, int, int, int, int = 0, bool = false) { return false; }
-#else
-constexpr bool hot_wide(int S, int NH, int in, int NW, int extra = 0, bool pair = false) { return hot_lds_bytes(S, NH, in, NW, true, pair) + extra <= hot_lds_cap(NW, pair, S); }
-#endif
+constexpr bool hot_wide(int S, int NH, int in, int NW, int extra = 0) { return hot_lds_bytes(S, NH, in, NW, true) + extra <= hot_lds_cap(NW, S); }
 // the any-D form's additions to a workgroup's LDS: parked group sums, and the rotated samples where the window buffer is too small
 // (rot = false, plans without a shift: the unrotated values have 18 bits — two arrays of dwords instead of one of int16 pairs)
 // (the team sums stay in registers: only the parked group sums, 512 bytes per wave)
@@ -244,21 +232,12 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // `b` serves the cold phase only. Left to itself the compiler loads the whole block at kernel entry and keeps it in
   // scalar registers ACROSS the hot loop — in the any-D forms that pushed the loop's own scalars into spill lanes (27 to
   // 49 v_readlane per slice in kernels that are bound by vector issue). It is copied out of the kernarg segment behind
-  // the hot loop instead, through a pointer the compiler cannot see through (K1_LATE_B=0: the old behaviour, A/B).
-#ifndef K1_LATE_B
-#define K1_LATE_B 1
-#endif
-#ifndef K1_LATE_A
-#define K1_LATE_A 0
-#endif
+  // the hot loop instead, through a pointer the compiler cannot see through.
   // Only the any-D forms do this: in the /8 kernels nothing was spilled to begin with, and there the late copies cost
   // vector registers instead (16 of them spilled to scratch in the USB and no-demodulator kernels of the 9-step class:
   // +11 % time, +28 % HBM traffic on the 127-tap USB workload when it was tried for all kernels).
-  constexpr bool LATE_B = K1_LATE_B && DG, LATE_A = K1_LATE_A && DG;
   IqbbArgs b_late;
-  const IqbbArgs &b = LATE_B ? b_late : b_kernarg;
-  HotArgs a_late;                                        // (K1_LATE_A: likewise the cold phase's copy of `a`; off — it left 8 to
-  const HotArgs &ac = LATE_A ? a_late : a;               //  24 bytes of scratch in a dozen any-D kernels for -0.8 % in the others)
+  const IqbbArgs &b = DG ? b_late : b_kernarg;
   // CU8: ONE byte plane per sample (complex<uint8> after AutoCast: the high plane; complex<int8>: the sample itself) — two MFMAs
   // per K step, no low-plane accumulator. CS8 marks what differs for IQBaseBand<int8_t>: no plane conversion, the FIR value is
   // (hh << 8) + mid wrapped to int16 after the shift (src/baseband.hh:206), the rotation wraps to int16 and shifts by 8
@@ -286,11 +265,10 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   constexpr int NDMA = (NPIECE + 63) / 64;                     // DMA wave-instructions per window
   constexpr int LASTL = NPIECE - 64 * (NDMA - 1);              // lanes of the last one
   static_assert(NDMA <= 4, "immediate offsets 0 / 1024 / 2048 / 3072");
-  constexpr bool PAIR = hot_pair(IN, NW, DG);
-  constexpr bool WIDE = SD ? false : hot_wide(S, NH, IN, NW, DG ? hot_anyd_extra(S, IN, ROT, NW) : 0, PAIR);   // (SD: the narrow table, the LDS goes to the sample arrays)
+  constexpr bool WIDE = SD ? false : hot_wide(S, NH, IN, NW, DG ? hot_anyd_extra(S, IN, ROT, NW) : 0);   // (SD: the narrow table, the LDS goes to the sample arrays)
   static_assert(!SD || hot_sd_fits(S, NH, IN, ROT, NW), "small-decimation form: LDS budget");
-  constexpr int NBUF = PAIR ? 4 : 2;   // window buffers per wave
-  static_assert(hot_lds_bytes(S, NH, IN, NW, WIDE, PAIR) <= hot_lds_cap(NW, PAIR, S), "LDS budget for 4 waves per SIMD");
+  constexpr int NBUF = 2;   // window buffers per wave
+  static_assert(hot_lds_bytes(S, NH, IN, NW, WIDE) <= hot_lds_cap(NW, S), "LDS budget for 4 waves per SIMD");
   constexpr int TBLW = WIDE ? 1024 : 256;   // dwords
   constexpr int TPBH = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -309,13 +287,8 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   char *pendb = reinterpret_cast<char *>(smem + TBLW + (S + NH) * 64 * 4) + NW * (NBUF * BUFB) + w * 512;    // (DG) the wave's parked group sums (64 x int2)
   char *gscb = reinterpret_cast<char *>(smem + TBLW + (S + NH) * 64 * 4) + NW * (NBUF * BUFB) + (SD ? 0 : NW * 512) + w * 2048;   // (DG) the wave's rotated samples (when its window buffer is too small; SD: no parked sums in front)
   char *gscb2 = gscb + NW * 2048;   // (DG, no shift, small window buffers) the second array
-#ifdef K1_ABL_ASAME   // (tuning ablation, results wrong: every step reads the SAME fragment values — K1_ABL_AREG's operand data with the reads kept)
-  for (int i = tid; i < S * 64; i += TPBH) taps_s[i] = a.tapfrag[64 + (i & 63)];
-  for (int i = tid; i < NH * 64; i += TPBH) taps_s[S * 64 + i] = a.tapfrag[(2 * S0) * 64 + (i & 63)];
-#else
   for (int i = tid; i < S * 64; i += TPBH) taps_s[i] = a.tapfrag[(2 * (i >> 6) + 1) * 64 + (i & 63)];
   for (int i = tid; i < NH * 64; i += TPBH) taps_s[S * 64 + i] = a.tapfrag[(2 * (S0 + (i >> 6))) * 64 + (i & 63)];
-#endif
   if (tid < 256) {
     const int2 e = a.lut[(tid & 127) ^ (a.negative ? 127 : 0)];
     if (WIDE) reinterpret_cast<v4i *>(smem)[tid] = v4i{e.x, e.y, -e.y, 0};
@@ -367,7 +340,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // untracked load only ever makes a compiler-generated vmcnt wait longer, never shorter: VMEM retires in order).
   // LDS address = M0 + instruction offset + 16 * lane; SALU write of M0 -> LDS-DMA needs one wait state.
   auto dma_issue = [&](const char *src, char *buf) {
-#ifndef K1_ABL_NOFETCH
     const unsigned ldsb = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)buf);
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -385,12 +357,8 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       if (l < LASTL) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off offset:3072" :: "v"(src), "s"(ldsb) : "memory", "m0");
     }
 #pragma clang diagnostic pop
-#endif
   };
-  if (u < a.U) {
-    dma_issue(srcb + (long)tile * tile_in_bytes + lane_byte, wbase);
-    if (PAIR && tile + 1 < tend) dma_issue(srcb + (long)(tile + 1) * tile_in_bytes + lane_byte, wbase + BUFB);
-  }
+  if (u < a.U) dma_issue(srcb + (long)tile * tile_in_bytes + lane_byte, wbase);
   __syncthreads();   // tap fragments and table in place (the only workgroup barrier)
 
   // plane byte offsets of this lane's pieces. cs16: piece p = 4 samples = half of chunk j = p >> 1 (a chunk = 8 samples =
@@ -427,12 +395,9 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #else
 #define K1_STAMP(i_) do { } while (0)
 #endif
-#ifndef K1_PRIO_ROT
-#define K1_PRIO_ROT 1
-#endif
-#ifndef K1_PRIO_SHIFT
-#define K1_PRIO_SHIFT 11
-#endif
+  // wave priorities: 1 = rotating, one step per slice (shipped); 2 / 3 = the matrix phase first / last; 4 = rotating with the shader
+  // clock, one step per 2^K1_PRIO_SHIFT cycles. 0, 2, 3: +1.3 ... +2.1 % (docs/history/ROUND5_notes.md); 4: profiles/r18_ab_prio_time.txt
+  constexpr int K1_PRIO_ROT = 1, K1_PRIO_SHIFT = 11;
   unsigned prio_it = 0;
   const unsigned prio_slot = __builtin_amdgcn_s_getreg((3 << 11) | 4) & 3u;   // HW_REG_HW_ID[3:0]: the wave's slot in its SIMD
 
@@ -445,7 +410,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
     for (int k = 0; k < NDMA; k++)
       if (k < NDMA - 1 || l < LASTL) x[k] = *reinterpret_cast<const uint4 *>(cb + 16 * (l + 64 * k));
     asm volatile("" ::: "memory");
-#ifndef K1_ABL_NOCONV
 #pragma unroll
     for (int k = 0; k < NDMA; k++) {
       if (k < NDMA - 1 || l < LASTL) {
@@ -464,132 +428,33 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         }
       }
     }
-#endif
   };
   // K: the K loop out of the planes in `cb`: operands of step s+1 in flight while the MFMAs of step s issue
-#ifndef K1_AREG
-#define K1_AREG 0
-#endif
-  // (tuning variant K1_AREG=1: the tap fragments live in 4(S + NH) registers — build with -DK1_MINWAVES=3, run with
-  // SDRHIP_IQBB_WGPCU=3)
-  v4i AlR[K1_AREG ? S : 1], AhR[K1_AREG ? NH : 1];
-  if (K1_AREG) {
-#pragma unroll
-    for (int s = 0; s < S; s++) AlR[s] = taps_s[s * 64 + l];
-#pragma unroll
-    for (int s = 0; s < NH; s++) AhR[s] = taps_s[(S + s) * 64 + l];
-  }
-  // (K1_ARES = n: the HIGH-plane tap fragments of the first n high steps stay in registers for the whole kernel — the headline
-  // kernel uses 114 of the 128 registers four waves per SIMD leave it; a fragment read is 1 KB per wave and slice, and LDS
-  // reads are a fifth of the energy of a launch that runs at the power limit. Not for the AM epilogue: 126 registers.)
-#ifndef K1_ARES
-#define K1_ARES 0
-#endif
-  constexpr int NRES = (K1_AREG || CU8 || REAL || EPI == SDRHIP_EPI_AM || NW != 4) ? 0 : (K1_ARES < NH ? K1_ARES : NH);
-  v4i AhRes[NRES > 0 ? NRES : 1];
-#pragma unroll
-  for (int s = 0; s < NRES; s++) AhRes[s] = taps_s[(S + s) * 64 + l];
   struct KOps { v4i uh, ul, Al, Ah; };
   auto stageK_begin = [&](const char *cb, KOps &o) __attribute__((always_inline)) {
     const char *pl = cb + coff + KSB * L0, *ph = cb + (CU8 ? 0 : PLB) + coff + KSB * L0;   // (the loop's first step: L0)
     o.uh = *reinterpret_cast<const v4i *>(ph); o.ul = o.uh;
     if (!CU8) o.ul = *reinterpret_cast<const v4i *>(pl);
-    if (K1_AREG) { o.Al = AlR[L0]; o.Ah = AhR[0]; }
-    else {
-      o.Al = taps_s[L0 * 64 + l]; o.Ah = o.Al;
-      if (S0 == L0) o.Ah = NRES > 0 ? AhRes[0] : taps_s[S * 64 + l];
-    }
+    o.Al = taps_s[L0 * 64 + l]; o.Ah = o.Al;
+    if (S0 == L0) o.Ah = taps_s[S * 64 + l];
   };
   auto stageK = [&](const char *cb, KOps &o, v16i &acc_hh, v16i &acc_mid, v16i &acc_ll) __attribute__((always_inline)) {
     constexpr int SA = L0, SB = L0 + NL;   // (the steps outside multiply all-zero tap fragments: not issued)
     const char *pl = cb + coff, *ph = cb + (CU8 ? 0 : PLB) + coff;
-#ifdef K1_ABL_NOKLOOP
-    if (SA == 0) acc_mid[0] = o.uh.x ^ o.ul.x ^ o.Al.x ^ o.Ah.x;
-#else
 #pragma unroll
     for (int s = SA; s < SB; s++) {
-#ifdef K1_BSHIFT
-      // (the two-lane reads below are invisible to the compiler's wait counts: this step's operands — issued a whole step
-      // of MFMAs ago — are waited for here, BEFORE the next step's reads are issued)
-      if (!REAL && s > SA) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o.uh), "+v"(o.ul) :: "memory");
-#endif
       KOps nx = o;
       if (s + 1 < SB) {
-#ifdef K1_BSHIFT
-        // (-DK1_BSHIFT) The sample-plane operand of step s + 1 IS the operand of step s one lane to the left inside each
-        // half of the wave (lane (n, h) reads piece n + s of half h): the next operand comes by four DPP moves per plane
-        // (wave_shl:1) and only the lanes (31, h) read their fresh piece from LDS — 32 bytes per plane and step instead of
-        // 1 KB. An LDS read costs energy by the byte (tools/probes/mfma_energy.hip: one wave-wide ds_read_b128 is half an
-        // MFMA's worth), and the kernel runs at the power limit.
-        if (!REAL) {
-#if K1_BSHIFT == 2
-          // (round 5's second cut: the moves have no tied old operand — bound_ctrl zero-fills the lanes without a source, which
-          // the two-lane reads overwrite anyway — and the reads run under an exec mask set INSIDE the asm statement: no
-          // branch, no memory clobber that would pin the tap-fragment loads)
-          auto shl1 = [](v4i x) __attribute__((always_inline)) {
-            v4i r;
-#pragma unroll
-            for (int q = 0; q < 4; q++) r[q] = __builtin_amdgcn_mov_dpp(x[q], 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
-            return r;
-          };
-          nx.uh = shl1(o.uh);
-          if (!CU8) nx.ul = shl1(o.ul);
-          const unsigned ah_ = (unsigned)(uintptr_t)(ph + KSB * (s + 1)), al_ = (unsigned)(uintptr_t)(pl + KSB * (s + 1));
-          const unsigned long long m2 = 0x8000000080000000ull;   // lanes 31 and 63
-          if (!CU8)
-            asm volatile("s_mov_b64 exec, %4\n\tds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_mov_b64 exec, -1"
-                         : "+v"(nx.uh), "+v"(nx.ul) : "v"(ah_), "v"(al_), "s"(m2));
-          else
-            asm volatile("s_mov_b64 exec, %2\n\tds_read_b128 %0, %1\n\ts_mov_b64 exec, -1" : "+v"(nx.uh) : "v"(ah_), "s"(m2));
-#else
-          auto shl1 = [](v4i x) __attribute__((always_inline)) {
-            v4i r;
-#pragma unroll
-            for (int q = 0; q < 4; q++) r[q] = __builtin_amdgcn_update_dpp(x[q], x[q], 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-            return r;
-          };
-          nx.uh = shl1(o.uh);
-          if (!CU8) nx.ul = shl1(o.ul);
-          if (n == 31) {   // (lanes 31 and 63; asm: the compiler must not turn the branch into a wave-wide read and a select)
-            const unsigned ah_ = (unsigned)(uintptr_t)(ph + KSB * (s + 1));
-            asm volatile("ds_read_b128 %0, %1" : "+v"(nx.uh) : "v"(ah_) : "memory");
-            if (!CU8) {
-              const unsigned al_ = (unsigned)(uintptr_t)(pl + KSB * (s + 1));
-              asm volatile("ds_read_b128 %0, %1" : "+v"(nx.ul) : "v"(al_) : "memory");
-            }
-          }
-#endif
-        } else
-#endif
-        {
-#if defined(K1_ABL_BSAME_NOREAD)   // (tuning ablation, results wrong: step 0's sample planes serve every step, no reads)
-#elif defined(K1_ABL_BSAME_READ)   // (... the same operand values with the reads KEPT: their difference prices the reads alone)
-        { const v4i t0 = *reinterpret_cast<const v4i *>(ph + KSB * (s + 1)), t1 = *reinterpret_cast<const v4i *>(pl + KSB * (s + 1));
-          asm volatile("" :: "v"(t0), "v"(t1)); }
-#else
         nx.uh = *reinterpret_cast<const v4i *>(ph + KSB * (s + 1));
         if (!CU8) nx.ul = *reinterpret_cast<const v4i *>(pl + KSB * (s + 1));
-#endif
-        }
-#ifndef K1_ABL_AREG   // (tuning ablation, results wrong: the tap fragments of step 0 serve every step — what resident fragments would save)
-        if (K1_AREG) {
-          nx.Al = AlR[s + 1];
-          if (s + 1 >= S0 && s + 1 < S0 + NH) nx.Ah = AhR[s + 1 - S0];
-        } else {
-          nx.Al = taps_s[(s + 1) * 64 + l];
-          if (s + 1 >= S0 && s + 1 < S0 + NH) nx.Ah = (s + 1 - S0 < NRES) ? AhRes[s + 1 - S0 < NRES ? s + 1 - S0 : 0] : taps_s[(S + s + 1 - S0) * 64 + l];
-        }
-#endif
+        nx.Al = taps_s[(s + 1) * 64 + l];
+        if (s + 1 >= S0 && s + 1 < S0 + NH) nx.Ah = taps_s[(S + s + 1 - S0) * 64 + l];
       }
-#ifndef K1_MFMA_ORDER
-#define K1_MFMA_ORDER 1
-#endif
-#if K1_MFMA_ORDER == 1
       // A step's four MFMAs in an order in which ONE operand stays between neighbours — (Al,uh) (Ah,uh) (Ah,ul) (Al,ul): two
       // changes of the tap operand and one of the sample plane inside a step, where (Al,uh) (Al,ul) (Ah,uh) (Ah,ul) changed
       // the sample plane every time. The kernel runs at the socket's power limit and an int8 MFMA's energy follows what its
       // multipliers' inputs switch: -1.4 % per launch, FM and USB alike (tools/abk1.py, 9 interleaved rounds, bands that
-      // do not overlap: profiles/r17_ab_mfma_order.txt; -DK1_MFMA_ORDER=0: the old order). The asm statements pin the order.
+      // do not overlap: profiles/r17_ab_mfma_order.txt). The asm statements pin the order.
       acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uh, acc_mid, 0, 0, 0);
       asm volatile("" : "+v"(acc_mid));
       if (s >= S0 && s < S0 + NH) {
@@ -598,64 +463,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         if (!CU8) { acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ul, acc_mid, 0, 0, 0); asm volatile("" : "+v"(acc_mid)); }
       }
       if (!CU8) { acc_ll = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ul, acc_ll, 0, 0, 0); asm volatile("" : "+v"(acc_ll)); }
-#elif K1_MFMA_ORDER == 2
-      // (tuning variant: alternate the step's direction — even steps (Al,uh) (Ah,uh) (Ah,ul) (Al,ul), odd steps the reverse —
-      // so that the tap operand Al also carries over the step boundary's neighbours as little changed as the algebra allows)
-      if ((s & 1) == 0) {
-        acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uh, acc_mid, 0, 0, 0); asm volatile("" : "+v"(acc_mid));
-        if (s >= S0 && s < S0 + NH) {
-          acc_hh = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.uh, acc_hh, 0, 0, 0); asm volatile("" : "+v"(acc_hh));
-          if (!CU8) { acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ul, acc_mid, 0, 0, 0); asm volatile("" : "+v"(acc_mid)); }
-        }
-        if (!CU8) { acc_ll = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ul, acc_ll, 0, 0, 0); asm volatile("" : "+v"(acc_ll)); }
-      } else {
-        if (!CU8) { acc_ll = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ul, acc_ll, 0, 0, 0); asm volatile("" : "+v"(acc_ll)); }
-        if (s >= S0 && s < S0 + NH) {
-          if (!CU8) { acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ul, acc_mid, 0, 0, 0); asm volatile("" : "+v"(acc_mid)); }
-          acc_hh = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.uh, acc_hh, 0, 0, 0); asm volatile("" : "+v"(acc_hh));
-        }
-        acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uh, acc_mid, 0, 0, 0); asm volatile("" : "+v"(acc_mid));
-      }
-#else
-      acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uh, acc_mid, 0, 0, 0);
-      if (!CU8) acc_ll = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ul, acc_ll, 0, 0, 0);
-      if (s >= S0 && s < S0 + NH) {
-        acc_hh = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.uh, acc_hh, 0, 0, 0);
-        if (!CU8) acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ul, acc_mid, 0, 0, 0);
-      }
-#endif
-      o = nx;
-    }
-#endif
-  };
-  // (PAIR) the K loop over TWO windows: the tap fragments of a step are read once and feed the MFMAs of both slices
-  struct KOps2 { v4i uhA, ulA, uhB, ulB, Al, Ah; };
-  auto stageK2 = [&](const char *cbA, const char *cbB, v16i &hhA, v16i &midA, v16i &llA, v16i &hhB, v16i &midB, v16i &llB) __attribute__((always_inline)) {
-    const char *plA = cbA + coff, *phA = cbA + PLB + coff, *plB = cbB + coff, *phB = cbB + PLB + coff;
-    KOps2 o;
-    o.uhA = *reinterpret_cast<const v4i *>(phA); o.ulA = *reinterpret_cast<const v4i *>(plA);
-    o.uhB = *reinterpret_cast<const v4i *>(phB); o.ulB = *reinterpret_cast<const v4i *>(plB);
-    o.Al = taps_s[l]; o.Ah = o.Al;
-    if (S0 == 0) o.Ah = taps_s[S * 64 + l];
-#pragma unroll
-    for (int s = 0; s < S; s++) {
-      KOps2 nx = o;
-      if (s + 1 < S) {
-        nx.uhA = *reinterpret_cast<const v4i *>(phA + KSB * (s + 1)); nx.ulA = *reinterpret_cast<const v4i *>(plA + KSB * (s + 1));
-        nx.uhB = *reinterpret_cast<const v4i *>(phB + KSB * (s + 1)); nx.ulB = *reinterpret_cast<const v4i *>(plB + KSB * (s + 1));
-        nx.Al = taps_s[(s + 1) * 64 + l];
-        if (s + 1 >= S0 && s + 1 < S0 + NH) nx.Ah = taps_s[(S + s + 1 - S0) * 64 + l];
-      }
-      midA = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uhA, midA, 0, 0, 0);
-      midB = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.uhB, midB, 0, 0, 0);
-      llA = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ulA, llA, 0, 0, 0);
-      llB = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Al, o.ulB, llB, 0, 0, 0);
-      if (s >= S0 && s < S0 + NH) {
-        hhA = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.uhA, hhA, 0, 0, 0);
-        hhB = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.uhB, hhB, 0, 0, 0);
-        midA = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ulA, midA, 0, 0, 0);
-        midB = __builtin_amdgcn_mfma_i32_32x32x32_i8(o.Ah, o.ulB, midB, 0, 0, 0);
-      }
       o = nx;
     }
   };
@@ -692,11 +499,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
                     int2 *pdst = nullptr, int ob0 = 0) __attribute__((always_inline)) {   // (PART: where the slice's partial sums go, its first group boundary)
     constexpr bool EDGE = decltype(edge_)::value;
     int L[8][3];
-#ifdef K1_ABL_NOEPI
-    if (false) {
-#else
     if (ROT) {
-#endif
       typedef int v2i __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int jj = 0; jj < 4; jj++) {
@@ -720,12 +523,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
     }
     int2 sum = make_int2(0, 0);
     int vx[8], vy[8];   // (DG) the lane's samples after the rotation (32-bit products: the sample is the high half), or (no shift) the FIR values
-#ifdef K1_ABL_NOEPI
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) { sum.x += acc_hh[r] ^ acc_mid[r] ^ acc_ll[r]; sum.y += acc_hh[r + 1] ^ acc_mid[r + 1] ^ acc_ll[r + 1]; }
-#pragma unroll
-    for (int j = 0; j < 8; j++) { vx[j] = sum.x; vy[j] = sum.y; }
-#else
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       unsigned tre = ((unsigned)acc_hh[2 * j] << 8) + (unsigned)acc_mid[2 * j];   // (compiler code: it pads the MFMA -> VALU hazard)
@@ -763,7 +560,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         sum.x = (int)((unsigned)sum.x + (unsigned)rr); sum.y = (int)((unsigned)sum.y + (unsigned)ri);
       }
     }
-#endif
     if (SD) {
       // the wave's 512 rotated samples in stream order: lane (n, h) holds 16n + 8h + {0 ... 7}, the wave writes 64 contiguous
       // 32-byte pieces ({x >> 16, y >> 16} as two int16 per sample; without a shift the 18-bit parts in two arrays)
@@ -781,9 +577,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       asm volatile("" ::: "memory");   // (the group sums below read them: same wave, in order)
       return sum;
     }
-#ifdef K1_ABL_NOTEAM   // (timing only: no team sums)
-    if (DG) { for (int j = 0; j < 8; j++) { sum.x ^= vx[j]; sum.y ^= vy[j]; } return sum; }
-#endif
     if (DG) {
       // Group sums as differences of PREFIX sums over the wave's 512 samples, all in registers. Per block: its total tX / tY
       // and the part in front of its group boundary aX / aY (0 where it has none). The totals of a lane pair's 16 samples are
@@ -903,37 +696,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // demodulator (28 slots for FM alone) — would cost every slice a fifth of its vector instructions for a handful of
   // lanes. The leaders PARK their sums in a 64-entry per-wave LDS array instead, slice after slice of the unit (a unit's
   // tiles are consecutive), and one pass finishes up to 64 groups, one per lane, when the unit ends or the array is full.
-  // (HS) FM in the any-D forms where the units are not whole channels: a slice's first output is the difference between the
-  // last angle of the slice BEFORE it — another wave's, possibly on another XCD — and its own first angle. Both owners post
-  // their angle in device memory (agent-scope stores: written through the XCD's L2), wait for the stores, then look for the
-  // other's entry (agent-scope loads): whoever finds it — at least one of the two does, both may — writes the output
-  // (again through the L2; the two values are the same). The entry carries the call's number, so nothing of an older call
-  // is mistaken for this one's. A lane passes first / last for the group it holds; sid: its slice, phi: its angle.
-  // Compiled in only under -DK1_FM_HANDSHAKE (tools/build_variant.sh hs "-DK1_FM_HANDSHAKE"; run with SDRHIP_IQBB_FM_HANDSHAKE=1):
-  // it measured no faster than the fix-up launch at any channel count, and its mere presence — a kernel-uniform branch at
-  // the four emission sites — cost the any-D FM kernels 2-4 % (profiles/r17_ab_fm_handshake.txt, r17_ab_nohs.txt).
-#ifdef K1_FM_HANDSHAKE
-#define HS_ON(A_) ((A_).hs != nullptr)
-#else
-#define HS_ON(A_) false
-#endif
-  auto hs_exchange = [&](const HotArgs &A, bool first, bool last, int cc, int sid, int phi) __attribute__((always_inline)) {
-    long long *plast = A.hs + (long)cc * A.hs_stride + sid + 1;              // slice sid's last angle
-    long long *pfirst = A.hs + ((long)A.C + cc) * A.hs_stride + sid + 1;     // slice sid's first angle
-    const long long mine = ((long long)A.hs_seq << 32) | (long long)(unsigned)phi;
-    if (last) __hip_atomic_store(plast, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (first) __hip_atomic_store(pfirst, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the stores are acknowledged from beyond the L2 before the loads go out)
-    short *row = reinterpret_cast<short *>(A.out) + (long)cc * A.out_stride;
-    if (first) {
-      const long long v = __hip_atomic_load(plast - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((int)(v >> 32) == A.hs_seq) __hip_atomic_store(row + (long)sid * GS, (short)((int)(unsigned)v - phi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (last) {
-      const long long v = __hip_atomic_load(pfirst + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((int)(v >> 32) == A.hs_seq) __hip_atomic_store(row + (long)(sid + 1) * GS, (short)(phi - (int)(unsigned)v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
   int2 *pend = reinterpret_cast<int2 *>(pendb);
   int npend = 0, ptile0 = 0;          // (scalar) groups parked, tile of the first parked slice
   // the lane's place in a flush: parked entry l is group k_f of the j_f-th parked slice
@@ -967,13 +729,8 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       // the previous slice's last angle, which that slice's last group leaves in philast
       const int phi = fm_phi(yr, yi);
       const int prev = __builtin_amdgcn_update_dpp(0, phi, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);   // entry l - 1: the group before, within a slice
-      if (HS_ON(a)) {   // (kernel-uniform) few channels: the slices' first outputs by the neighbours' handshake
-        if (live && k_f > 0) *reinterpret_cast<short *>(orow) = (short)(prev - phi);
-        hs_exchange(a, live && k_f == 0, live && k_f == GS - 1, c_, 4 * (ptile0 + j_f) + wv, phi);
-      } else {
-        if (live) *reinterpret_cast<short *>(orow) = (short)((k_f > 0 ? prev : 0) - phi);
-        if (live && k_f == GS - 1) a.philast[(long)c_ * a.philast_stride + 4 * (ptile0 + j_f) + wv] = (short)phi;
-      }
+      if (live) *reinterpret_cast<short *>(orow) = (short)((k_f > 0 ? prev : 0) - phi);
+      if (live && k_f == GS - 1) a.philast[(long)c_ * a.philast_stride + 4 * (ptile0 + j_f) + wv] = (short)phi;
     }
     npend = 0;
   };
@@ -1032,13 +789,8 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         const int phi = fm_phi(yr, yi);
         int prev = __builtin_amdgcn_update_dpp(0, phi, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);   // lane l - 1: group k - 1
         if (l == 0) prev = carry_phi;   // (i = 0: the slice's first group, -phi for now)
-        if (HS_ON(a)) {   // (kernel-uniform)
-          if (live && k > 0) reinterpret_cast<short *>(orow)[k] = (short)(prev - phi);
-          if (i == 0 || 64 * (i + 1) >= GS) hs_exchange(a, live && k == 0, live && k == GS - 1, c_, 4 * tile_ + wv, phi);   // (scalar: the chunks that hold the first / last group)
-        } else {
-          if (live) reinterpret_cast<short *>(orow)[k] = (short)(prev - phi);
-          if (live && k == GS - 1) a.philast[(long)c_ * a.philast_stride + 4 * tile_ + wv] = (short)phi;
-        }
+        if (live) reinterpret_cast<short *>(orow)[k] = (short)(prev - phi);
+        if (live && k == GS - 1) a.philast[(long)c_ * a.philast_stride + 4 * tile_ + wv] = (short)phi;
         carry_phi = __builtin_amdgcn_readlane(phi, 63);
       }
     }
@@ -1070,13 +822,13 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       if (lead && q == b.n_groups - 1) b.acc_new[cc] = emits ? make_int2(0, 0) : sum;
       const int yr = div_d(sum.x), yi = div_d(sum.y);
       if (EPI == SDRHIP_EPI_NONE) {
-        if (emits) reinterpret_cast<uint32_t *>(ac.out)[(long)cc * ac.out_stride + q] = ((uint32_t)(uint16_t)yr) | ((uint32_t)(uint16_t)yi << 16);
+        if (emits) reinterpret_cast<uint32_t *>(a.out)[(long)cc * a.out_stride + q] = ((uint32_t)(uint16_t)yr) | ((uint32_t)(uint16_t)yi << 16);
       } else if (EPI == SDRHIP_EPI_AM) {
         const short o = am_i16(yr, yi);
-        if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
+        if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
       } else if (EPI == SDRHIP_EPI_USB) {
         const short o = usb_i16(yr, yi);
-        if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
+        if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
       } else {
         const int phi = fm_phi(yr, yi);
         int prev = __builtin_amdgcn_update_dpp(0, phi, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
@@ -1085,14 +837,8 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         if (q == 0) o = (short)yr;                                   // index 0 is never written by FMDemod (in place)
         else if (q == 1) o = (short)((int)b.fm_old[cc] - phi);       // y[0] is never looked at: the previous call's last angle
         else o = (short)(prev - phi);                                // (a slice's first group: prev = 0, the fix-up launch adds philast)
-        if (HS_ON(ac)) {   // (kernel-uniform)
-          const bool hfirst = emits && k == 0 && q >= 2;   // (outputs 0 and 1 have their own rules above)
-          if (emits && !hfirst) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
-          if (i == 0 || 64 * (i + 1) >= GS) hs_exchange(ac, hfirst, emits && k == GS - 1, cc, sid, phi);
-        } else {
-          if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
-          if (emits && k == GS - 1) ac.philast[(long)cc * ac.philast_stride + sid] = (short)phi;
-        }
+        if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
+        if (emits && k == GS - 1) a.philast[(long)cc * a.philast_stride + sid] = (short)phi;
         if (emits && q == b.n_out - 1 && b.n_out >= 2) b.fm_new[cc] = (short)phi;
         carry_phi = __builtin_amdgcn_readlane(phi, 63);
       }
@@ -1159,9 +905,6 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       // tie goes to the older one and the drift feeds itself. The counter is read one slice ahead: its latency is hidden.)
       unsigned pv = prio_it++ + prio_slot;
       if (K1_PRIO_ROT == 4) { pv = prio_time + prio_slot; prio_time = (unsigned)(__builtin_amdgcn_s_memtime() >> K1_PRIO_SHIFT); }
-#ifdef K1_PRIO_BIAS   // (tuning variant: every K1_PRIO_BIAS-th slice the YOUNGER slots of a SIMD take the top priorities, whatever the rotation says)
-      if ((prio_it % K1_PRIO_BIAS) == 0) pv = prio_slot;
-#endif
       asm volatile("s_bitcmp1_b32 %0, 1\n\ts_cbranch_scc1 2f\n\ts_bitcmp1_b32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_setprio 0\n\ts_branch 4f\n"
                    "1:\n\ts_setprio 1\n\ts_branch 4f\n"
                    "2:\n\ts_bitcmp1_b32 %0, 0\n\ts_cbranch_scc1 3f\n\ts_setprio 2\n\ts_branch 4f\n"
@@ -1210,7 +953,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       v16i acc_hh = {0}, acc_mid = {0}, acc_ll = {0};
       if (!CU8) acc_ll = cinit;
       KOps ops;
-      if (K1_PRIO_ROT == 2) asm volatile("s_setprio 3");   // (tuning variants: the matrix phase first / last)
+      if (K1_PRIO_ROT == 2) asm volatile("s_setprio 3");
       if (K1_PRIO_ROT == 3) asm volatile("s_setprio 0");
       stageK_begin(cb, ops);
       stageK(cb, ops, acc_hh, acc_mid, acc_ll);
@@ -1249,58 +992,10 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #endif
       u = nu; c = nc; g = ng; tile = ntile; tend = ntend; srcb = nsrcb; outb = noutb;
     };
-    // (PAIR) one step = the unit's next TWO tiles (the last step of a unit with an odd tile count: one; its second window
-    // then holds stale samples and its results are dropped). Buffers 2 PAR, 2 PAR + 1 hold this step's windows, the other
-    // two receive the next step's.
-    auto slice2 = [&](auto par_) __attribute__((always_inline)) {
-      constexpr int PAR = decltype(par_)::value;
-      char *cbA = wbase + (2 * PAR) * BUFB, *cbB = cbA + BUFB, *nbA = wbase + (2 * (1 - PAR)) * BUFB, *nbB = nbA + BUFB;
-      const bool hasB = tile + 1 < tend;
-      int nu = u, nc = c, ng = g, ntile = tile + (hasB ? 2 : 1), ntend = tend;
-      const char *nsrcb = srcb;
-      char *noutb = outb;
-      if (ntile >= tend) {
-        next_unit(nu, nc, ng, ntile, ntend);
-        nsrcb = chan_src(nc); noutb = chan_out(nc);
-      }
-      const bool more = nu < a.U, nhasB = more && ntile + 1 < ntend;
-      rotate_priority();
-      if (__builtin_expect(more, 1)) {
-        dma_issue(nsrcb + (long)ntile * tile_in_bytes + lane_byte, nbA);
-        if (nhasB) dma_issue(nsrcb + (long)(ntile + 1) * tile_in_bytes + lane_byte, nbB);
-      }
-      // everything older than the DMA instructions just issued (VMEM retires in order)
-      static_assert(!PAIR || NDMA == 3, "pair variant: three DMA instructions per window");
-      if (nhasB) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else if (more) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stageP(cbA);
-      if (hasB) stageP(cbB);
-      asm volatile("" ::: "memory");
-      v16i hhA = {0}, midA = {0}, llA = cinit, hhB = {0}, midB = {0}, llB = cinit;
-      stageK2(cbA, cbB, hhA, midA, llA, hhB, midB, llB);
-      {
-        const int2 sum = stageE(std::false_type{}, hhA, midA, llA, cnt0 + (uint32_t)tile * tile_cnt, cbA, 0);
-        stageF(sum, outb + (long)tile * tile_out_bytes, GLW0);
-      }
-      if (hasB) {
-        const int2 sum = stageE(std::false_type{}, hhB, midB, llB, cnt0 + (uint32_t)(tile + 1) * tile_cnt, cbB, 0);
-        stageF(sum, outb + (long)(tile + 1) * tile_out_bytes, GLW0);
-      }
-      u = nu; c = nc; g = ng; tile = ntile; tend = ntend; srcb = nsrcb; outb = noutb;
-    };
-    if (PAIR) {
-      while (u < a.U) {
-        slice2(std::integral_constant<int, 0>{});
-        if (!(u < a.U)) break;
-        slice2(std::integral_constant<int, 1>{});
-      }
-    } else {
-      while (u < a.U) {
-        slice(std::integral_constant<int, 0>{});
-        if (!(u < a.U)) break;
-        slice(std::integral_constant<int, 1>{});
-      }
+    while (u < a.U) {
+      slice(std::integral_constant<int, 0>{});
+      if (!(u < a.U)) break;
+      slice(std::integral_constant<int, 1>{});
     }
   }
 
@@ -1308,7 +1003,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // stream's D+1 first window, the open last group and the demodulator's angle for the next call, FMDemod's first two
   // outputs of a buffer (group_finish is the decimation-8 form of the same rules). sid: the slice's number 4 * tile + wv.
   auto cold_finish_gen = [&](int2 sum, int cc, int sid) __attribute__((always_inline)) {
-    const int lsh = ac.lpg_sh, k = l >> lsh, q = sid * GS + k;   // q: the group's output index within the call
+    const int lsh = a.lpg_sh, k = l >> lsh, q = sid * GS + k;   // q: the group's output index within the call
     const bool lead = (l & ((1 << lsh) - 1)) == 0 && k < GS && q < b.n_groups;
     if (lead && q == 0) {
       const int2 carry = b.acc_old[cc];
@@ -1331,15 +1026,15 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
     int yr = div_d(sum.x), yi = div_d(sum.y);
     if (CS8) { yr = (signed char)yr; yi = (signed char)yi; }   // (the int8 node's output type)
     if (EPI == SDRHIP_EPI_NONE && CS8) {
-      if (emits) reinterpret_cast<uint16_t *>(ac.out)[(long)cc * ac.out_stride + q] = (uint16_t)((yr & 0xff) | ((yi & 0xff) << 8));
+      if (emits) reinterpret_cast<uint16_t *>(a.out)[(long)cc * a.out_stride + q] = (uint16_t)((yr & 0xff) | ((yi & 0xff) << 8));
     } else if (EPI == SDRHIP_EPI_NONE) {
-      if (emits) reinterpret_cast<uint32_t *>(ac.out)[(long)cc * ac.out_stride + q] = ((uint32_t)(uint16_t)yr) | ((uint32_t)(uint16_t)yi << 16);
+      if (emits) reinterpret_cast<uint32_t *>(a.out)[(long)cc * a.out_stride + q] = ((uint32_t)(uint16_t)yr) | ((uint32_t)(uint16_t)yi << 16);
     } else if (EPI == SDRHIP_EPI_AM) {
       const short o = am_i16(yr, yi);
-      if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
+      if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
     } else if (EPI == SDRHIP_EPI_USB) {
       const short o = usb_i16(yr, yi);
-      if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
+      if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
     } else {
       const int phi = fm_phi(yr, yi);
       const int prev = __builtin_amdgcn_ds_bpermute(4 * (((k - 1) << lsh) & 63), phi);   // the leader of team k - 1
@@ -1348,33 +1043,24 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
                           : (short)yr;                             // index 0 is never written by FMDemod (in place)
       else if (q == 1) o = (short)((int)b.fm_old[cc] - phi);       // y[0] is never looked at: the previous call's last angle
       else o = (short)((k > 0 ? prev : 0) - phi);                  // (a slice's first group: the fix-up launch adds philast)
-      if (HS_ON(ac)) {   // (kernel-uniform)
-        const bool hfirst = emits && k == 0 && q >= 2;   // (outputs 0 and 1 have their own rules above)
-        if (emits && !hfirst) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
-        hs_exchange(ac, hfirst, emits && k == GS - 1, cc, sid, phi);
-      } else {
-        if (emits) reinterpret_cast<short *>(ac.out)[(long)cc * ac.out_stride + q] = o;
-        if (emits && k == GS - 1) ac.philast[(long)cc * ac.philast_stride + sid] = (short)phi;
-      }
+      if (emits) reinterpret_cast<short *>(a.out)[(long)cc * a.out_stride + q] = o;
+      if (emits && k == GS - 1) a.philast[(long)cc * a.philast_stride + sid] = (short)phi;
       if (emits && q == b.n_out - 1 && b.n_out >= 2) b.fm_new[cc] = (short)phi;
     }
   };
 
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (LATE_B || LATE_A) {
-    // the blocks' places in the kernarg segment: the explicit arguments of every kernel that calls this body
+  if (DG) {
+    // the block's place in the kernarg segment: the explicit arguments of every kernel that calls this body
     // (`(const HotArgs a, const IqbbArgs b)`), laid out in declaration order at their natural alignment
     typedef const uint32_t __attribute__((address_space(4))) *KernargP;   // (the kernarg segment is constant memory: scalar loads)
     constexpr size_t B_OFF = (sizeof(HotArgs) + alignof(IqbbArgs) - 1) / alignof(IqbbArgs) * alignof(IqbbArgs);
     const char __attribute__((address_space(4))) *kp = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kp) :: "memory");
-    static_assert(sizeof(IqbbArgs) % 4 == 0 && sizeof(HotArgs) % 4 == 0, "copied by dwords");
+    static_assert(sizeof(IqbbArgs) % 4 == 0, "copied by dwords");
     uint32_t *dst = reinterpret_cast<uint32_t *>(&b_late);
 #pragma unroll
-    for (int i = 0; i < (LATE_B ? (int)(sizeof(IqbbArgs) / 4) : 0); i++) dst[i] = ((KernargP)(kp + B_OFF))[i];
-    uint32_t *dsta = reinterpret_cast<uint32_t *>(&a_late);
-#pragma unroll
-    for (int i = 0; i < (LATE_A ? (int)(sizeof(HotArgs) / 4) : 0); i++) dsta[i] = ((KernargP)kp)[i];
+    for (int i = 0; i < (int)(sizeof(IqbbArgs) / 4); i++) dst[i] = ((KernargP)(kp + B_OFF))[i];
   }
 #endif
   // ---- the call's COLD slices --------------------------------------------------------------------------------
@@ -1382,28 +1068,24 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // groups, the end of the input — are a few per channel (2 of 130 on the headline workload).
   {
     char *cb = wbase;
-#ifdef K1_ABL_NOCOLD   // tuning ablation (results wrong): no cold phase
-    for (int cc = ac.C; cc < ac.C; cc += gx) {
-#else
-    for (int cc = bx; cc < ac.C; cc += gx) {
-#endif
+    for (int cc = bx; cc < a.C; cc += gx) {
       // (DG: every tile of the call in turn; the wave's own hot tiles [hl, hh) and the slices behind the call's last group are skipped)
-      for (int t = 0; t < (DG ? ac.tiles_h : b.tiles); t = DG ? t + 1 : (t == 0 ? max(b.bt_hi, 1) : t + 1)) {
-        const int q0 = t * ac.OG - ac.ovl, groups_here = DG ? 0 : min(b.CG, b.n_groups - q0);
+      for (int t = 0; t < (DG ? a.tiles_h : b.tiles); t = DG ? t + 1 : (t == 0 ? max(b.bt_hi, 1) : t + 1)) {
+        const int q0 = t * a.OG - a.ovl, groups_here = DG ? 0 : min(b.CG, b.n_groups - q0);
         if (DG) { if ((t >= hl && t < hh) || (q0 + gw) >= b.n_groups) continue; }
-        else if (slice_is_hot(HALO, WIN, ac.base0_rel, ac.OG, ac.ovl, ac.N, ac.n_out, t, wv) || gw + ac.ovl >= groups_here) continue;
+        else if (slice_is_hot(HALO, WIN, a.base0_rel, a.OG, a.ovl, a.N, a.n_out, t, wv) || gw + a.ovl >= groups_here) continue;
         // the wave's window by ordinary loads: history / input / zeros per sample, every load issued from a clamped
         // address and masked afterwards (all in flight together)
-        const int first = ac.base0_rel + (q0 + gw) * DD - HALO;
+        const int first = a.base0_rel + (q0 + gw) * DD - HALO;
         const uint32_t *hrow = b.hist_old + (long)cc * b.HH;
         if (REAL) {   // 8 real samples per piece: input int16, or the low half of a history dword
-          const uint16_t *row = reinterpret_cast<const uint16_t *>(ac.in) + (long)cc * ac.in_stride;
+          const uint16_t *row = reinterpret_cast<const uint16_t *>(a.in) + (long)cc * a.in_stride;
           uint32_t v[NDMA][8];
 #pragma unroll
           for (int k = 0; k < NDMA; k++) {
             const int pp = min(l + 64 * k, NPIECE - 1);
 #pragma unroll
-            for (int j = 0; j < 8; j++) v[k][j] = row[max(min(first + 8 * pp + j, ac.N - 1), 0)];
+            for (int j = 0; j < 8; j++) v[k][j] = row[max(min(first + 8 * pp + j, a.N - 1), 0)];
           }
 #pragma unroll
           for (int k = 0; k < NDMA; k++) {
@@ -1411,7 +1093,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #pragma unroll
             for (int j = 0; j < 8; j++) {
               const int rel = first + 8 * pp + j;
-              if (rel >= ac.N) v[k][j] = 0u;
+              if (rel >= a.N) v[k][j] = 0u;
               if (first < 0) {   // (wave-uniform: only the call's first slices reach into the history)
                 const uint32_t xh = hrow[max(b.HH + rel, 0)];
                 if (rel < 0) v[k][j] = (b.HH + rel >= 0) ? (xh & 0xffffu) : 0u;
@@ -1429,13 +1111,13 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
             }
           }
         } else if (CU8) {
-          const uint16_t *row = reinterpret_cast<const uint16_t *>(ac.in) + (long)cc * ac.in_stride;
+          const uint16_t *row = reinterpret_cast<const uint16_t *>(a.in) + (long)cc * a.in_stride;
           uint32_t v[NDMA][8];
 #pragma unroll
           for (int k = 0; k < NDMA; k++) {
             const int pp = min(l + 64 * k, NPIECE - 1);
 #pragma unroll
-            for (int j = 0; j < 8; j++) v[k][j] = row[max(min(first + 8 * pp + j, ac.N - 1), 0)];
+            for (int j = 0; j < 8; j++) v[k][j] = row[max(min(first + 8 * pp + j, a.N - 1), 0)];
           }
 #pragma unroll
           for (int k = 0; k < NDMA; k++) {
@@ -1446,7 +1128,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
               // the sample's two high-plane bytes: AutoCast of the input bytes, or bytes 1 and 3 of a history dword
               // (int8 chain: the input bytes themselves, or bytes 0 and 2 of a history dword — the sign-extended pair)
               uint32_t hb = CS8 ? v[k][j] : ((v[k][j] + 0x81u) & 0xffu) | ((v[k][j] + 0x8100u) & 0xff00u);
-              if (rel >= ac.N) hb = 0u;
+              if (rel >= a.N) hb = 0u;
               if (first < 0) {   // (wave-uniform: only the call's first slices reach into the history)
                 const uint32_t xh = hrow[max(b.HH + rel, 0)];
                 if (rel < 0) hb = (b.HH + rel >= 0) ? (CS8 ? ((xh & 0xffu) | ((xh >> 8) & 0xff00u)) : (((xh >> 8) & 0xffu) | ((xh >> 16) & 0xff00u))) : 0u;
@@ -1459,7 +1141,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
                                                                     rotb(v[k][4] | (v[k][5] << 16)), rotb(v[k][6] | (v[k][7] << 16)));
           }
         } else {
-          const uint32_t *row = reinterpret_cast<const uint32_t *>(ac.in) + (long)cc * ac.in_stride;
+          const uint32_t *row = reinterpret_cast<const uint32_t *>(a.in) + (long)cc * a.in_stride;
           uint32_t v[NDMA][4];
 #pragma unroll
           for (int k = 0; k < NDMA; k++) {
@@ -1467,7 +1149,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #pragma unroll
             for (int j = 0; j < 4; j++) {
               const int rel = first + 4 * pp + j, hh = b.HH + rel;
-              const uint32_t *src = rel >= 0 ? row + min(rel, ac.N - 1) : hrow + max(hh, 0);
+              const uint32_t *src = rel >= 0 ? row + min(rel, a.N - 1) : hrow + max(hh, 0);
               v[k][j] = *src;
             }
           }
@@ -1477,7 +1159,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #pragma unroll
             for (int j = 0; j < 4; j++) {
               const int rel = first + 4 * pp + j;
-              if (rel >= ac.N || b.HH + rel < 0) v[k][j] = 0u;
+              if (rel >= a.N || b.HH + rel < 0) v[k][j] = 0u;
             }
             if (k < NDMA - 1 || l < LASTL) {
               uint2 l2, h2;
@@ -1494,7 +1176,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
         v16i acc_hh = {0}, acc_mid = {0}, acc_ll = {0};
         if (!CU8) {
 #pragma unroll
-          for (int r = 0; r < 16; r++) acc_ll[r] = (r & 1) ? ac.cim : ac.cre;
+          for (int r = 0; r < 16; r++) acc_ll[r] = (r & 1) ? a.cim : a.cre;
         }
         const char *pl = cb + coff, *ph = cb + (CU8 ? 0 : PLB) + coff;
 #pragma unroll
@@ -1515,26 +1197,26 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
           }
         }
         if (DG) {
-          const int s0 = ac.base0_rel + (q0 + gw) * DD;   // the slice's first sample, call-relative
+          const int s0 = a.base0_rel + (q0 + gw) * DD;   // the slice's first sample, call-relative
           int2 *pdst = nullptr;
           int ob0 = 0;
           if (PART) {
-            const int t0 = s0 - ac.base_real;
-            ob0 = t0 < 0 ? ac.Dreal - t0 : ac.Dreal - (int)((unsigned)t0 % (unsigned)ac.Dreal);
-            pdst = ac.part + (long)cc * ac.part_stride + 3 * (4 * t + wv);
+            const int t0 = s0 - a.base_real;
+            ob0 = t0 < 0 ? a.Dreal - t0 : a.Dreal - (int)((unsigned)t0 % (unsigned)a.Dreal);
+            pdst = a.part + (long)cc * a.part_stride + 3 * (4 * t + wv);
           }
-          const int2 sum = stageE(std::true_type{}, acc_hh, acc_mid, acc_ll, (ac.n0_lo + (uint32_t)s0) * ac.inc, cb, s0 + MF_BLK * n + 8 * h, pdst, ob0);
+          const int2 sum = stageE(std::true_type{}, acc_hh, acc_mid, acc_ll, (a.n0_lo + (uint32_t)s0) * a.inc, cb, s0 + MF_BLK * n + 8 * h, pdst, ob0);
           if (SD) sd_finish_cold(cb, cc, 4 * t + wv);
           else if (!PART) cold_finish_gen(sum, cc, 4 * t + wv);
         } else {
-          const int tb = ac.base0_rel + q0 * 8, rel0 = tb + 8 * gw + MF_BLK * n + 8 * h;
+          const int tb = a.base0_rel + q0 * 8, rel0 = tb + 8 * gw + MF_BLK * n + 8 * h;
           const int2 sum = group_sum<ROT, CU8, true, WIDE ? 2 : 1, FSH, CS8>(b, acc_hh, acc_mid, acc_ll, rel0);
           group_finish(b, b.lut, cc, n, h, gw, q0, groups_here, sum);   // (its one table user, the stream's first sample, reads global memory)
         }
         asm volatile("" ::: "memory");
       }
       for (int k = tid & 255; k < b.HH; k += 256) {   // the FIR history for the next call (this virtual workgroup's channel)
-        const long qq = (long)ac.N + k;   // index into concat(hist_old, in)
+        const long qq = (long)a.N + k;   // index into concat(hist_old, in)
         b.hist_new[(long)cc * b.HH + k] = qq < b.HH ? b.hist_old[(long)cc * b.HH + qq] : raw_x(b, cc, qq - b.HH);
       }
     }
@@ -1550,9 +1232,9 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
       // pair orders their stores and loads; a device-scope fence here writes the XCD's whole L2 back, once per workgroup:
       // measured +110 us per launch)
       __syncthreads();
-      for (int cc = bx; cc < ac.C; cc += gx) {
-        short *row = reinterpret_cast<short *>(ac.out) + (long)cc * ac.out_stride;
-        short *pl = ac.philast + (long)cc * ac.philast_stride;
+      for (int cc = bx; cc < a.C; cc += gx) {
+        short *row = reinterpret_cast<short *>(a.out) + (long)cc * a.out_stride;
+        short *pl = a.philast + (long)cc * a.philast_stride;
         for (int sl = b.fix_lo + (tid & 255); sl < b.fix_hi; sl += 256) {
           short *o = row + (long)sl * GS;
           *o = (short)(*o + pl[sl - 1]);
@@ -1563,14 +1245,14 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
   // (PART, whole channels as units) likewise the groups of the large-decimation form: every slice's partial sums of this
   // workgroup's channels are its own waves' — the finishing launch's work, one lane per group, behind the same barrier
   if (PART) {
-    if (ac.fin_groups > 0) {   // (kernel-uniform)
+    if (a.fin_groups > 0) {   // (kernel-uniform)
       __syncthreads();
       BigdArgs f;
-      f.part = ac.part; f.part_stride = ac.part_stride;
-      f.D = ac.Dreal; f.base0_rel = ac.base_real; f.N = ac.N; f.n_groups = ac.fin_groups; f.n_out = ac.fin_out; f.epi = ac.fin_epi; f.C = ac.C;
+      f.part = a.part; f.part_stride = a.part_stride;
+      f.D = a.Dreal; f.base0_rel = a.base_real; f.N = a.N; f.n_groups = a.fin_groups; f.n_out = a.fin_out; f.epi = a.fin_epi; f.C = a.C;
       f.acc_old = b.acc_old; f.acc_new = b.acc_new; f.fm_old = b.fm_old; f.fm_new = b.fm_new;
-      f.out = ac.out; f.out_stride = ac.out_stride;
-      for (int cc = bx; cc < ac.C; cc += gx)
+      f.out = a.out; f.out_stride = a.out_stride;
+      for (int cc = bx; cc < a.C; cc += gx)
         for (int q = tid & 255; q < f.n_groups; q += 256) bigd_finish_group(f, cc, q);
     }
   }
@@ -1584,9 +1266,7 @@ __device__ __forceinline__ void iqbb_hot_body(const HotArgs &a, const IqbbArgs &
 #endif
 }
 
-#ifndef K1_MINWAVES
-#define K1_MINWAVES 4
-#endif
+constexpr int K1_MINWAVES = 4;   // waves per SIMD the kernels are compiled for (128 vector registers each)
 // One launch per call: the hot grid, then each virtual workgroup's share of the cold slices.
 template <int S, int S0, int NH, bool ROT, int EPI, int IN, int NW, int L0 = 0, int NL = S>
 __global__ __launch_bounds__(64 * NW, K1_MINWAVES) void iqbb_hot_kernel(const HotArgs a, const IqbbArgs b) {
@@ -1639,13 +1319,12 @@ void hot_launch_form(bool rot, int epi, const HotLaunch &hl, const HotArgs &ha, 
     constexpr bool ROT = decltype(rot_c)::value;
     constexpr int NWL = FORM == HOT_SD ? hot_sd_range_waves(S, HotRange{S0, NH, NW}, IN, ROT) : NW;
     if constexpr (NWL > 0) {
-      constexpr bool PAIR = FORM == HOT_D8 && hot_pair(IN, NW, false);
       constexpr int extra = FORM == HOT_ANYD ? hot_anyd_extra(S, IN, ROT, NW) : FORM == HOT_SD ? hot_sd_extra(S, IN, ROT, NWL) : 0;
-      constexpr size_t lds = FORM == HOT_D8 ? hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, 0, PAIR), PAIR)
+      constexpr size_t lds = FORM == HOT_D8 ? hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW))
                            : FORM == HOT_ANYD ? hot_lds_bytes(S, NH, IN, NW, hot_wide(S, NH, IN, NW, extra)) + extra
                                               : hot_lds_bytes(S, NH, IN, NWL, false) + extra;
       static_assert(FORM != HOT_ANYD || hot_lds_bytes(S, NH, IN, NW, false) + hot_anyd_extra(S, IN, false, NW) <= 163840, "any-D form: a workgroup's LDS");
-      constexpr int anyd_cap = hot_lds_cap(NW, false, S) + hot_anyd_extra(S, IN, false, NW);
+      constexpr int anyd_cap = hot_lds_cap(NW, S) + hot_anyd_extra(S, IN, false, NW);
       constexpr int attr = FORM == HOT_ANYD ? (anyd_cap > 163840 ? 163840 : anyd_cap) : (int)lds;
       if constexpr (IN != HOT_CS8) if (FORM == HOT_ANYD ? NW > 4 : lds > 64 * 1024) {
         static std::atomic<uint64_t> attr_set{0};

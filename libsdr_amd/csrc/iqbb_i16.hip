@@ -46,10 +46,6 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
   struct __attribute__((packed, aligned(4))) Quad { uint32_t v[4]; };   // 16-byte load from a 4-byte aligned address
   Quad px[NQ];
   auto fetch = [&](int tile_) {
-#ifdef K1_ABL_NOFETCH   // tuning ablation (results wrong): no global loads
-    for (int k = 0; k < NQ; k++) for (int j = 0; j < 4; j++) px[k].v[j] = tile_ + k + j;
-    return;
-#endif
     const int q0_ = tile_ * a.OG - a.ovl;
     const int first = a.base0_rel + q0_ * 8 - (a.OP - 1);
     const int quads = (min(a.CG, a.n_groups - q0_) * 8 + a.OP + 4) / 4;
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
     // The next tile's samples are only pulled towards L2 here — one dword per 64-byte line into a scratch
     // register — and loaded into registers after the K loop, so that 12 VGPRs of prefetch are not live across it.
     // The compiler does not know the asm is a load: `touch` stays tied to it until the explicit wait below.
-    // The touch runs K1_TOUCH_AHEAD tiles ahead (default 2): a tile period is longer than an HBM round trip under
+    // The touch runs TOUCH_AHEAD tiles ahead: a tile period is longer than an HBM round trip under
     // load, so the register loads after the K loop find their lines in L2 — with one tile of lead they still waited
     // on HBM, and a workgroup has only that one tile of loads in flight (measured: the kernel without any arithmetic
     // took 104 of the 160 us).
@@ -138,26 +134,19 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
       const int q0_ = tile_ * a.OG - a.ovl;
       constexpr int LINE = CU8 ? 32 : 16;   // samples per 64-byte line
       const long first = (long)a.base0_rel + (long)q0_ * 8 - (a.OP - 1) + (long)LINE * tid;   // one line per lane
-#ifndef K1_ABL_NOFETCH
-      if ((CU8 || !a.in_cu8) && first >= 0 && first < (long)a.N && LINE * tid < TI + a.OP + LINE)
-#else
-      if (false)
-#endif
-      {
+      if ((CU8 || !a.in_cu8) && first >= 0 && first < (long)a.N && LINE * tid < TI + a.OP + LINE) {
         const void *pa = CU8 ? (const void *)((reinterpret_cast<const uint16_t *>(a.in) + (long)c * a.in_stride + first))
                              : (const void *)(a.in + (long)c * a.in_stride + first);
         pa = (const void *)((uintptr_t)pa & ~(uintptr_t)3);
         asm volatile("global_load_dword %0, %1, off" : "+v"(touch) : "v"(pa) : "memory");
       }
     };
-#ifndef K1_TOUCH_AHEAD
-#define K1_TOUCH_AHEAD 2
-#endif
+    constexpr int TOUCH_AHEAD = 2;
     if (it == 0) {
 #pragma unroll
-      for (int d = 1; d < K1_TOUCH_AHEAD; d++) touch_tile(tile + d);
+      for (int d = 1; d < TOUCH_AHEAD; d++) touch_tile(tile + d);
     }
-    touch_tile(tile + K1_TOUCH_AHEAD);
+    touch_tile(tile + TOUCH_AHEAD);
     const bool wave_has_work = (w * OGw + a.ovl < groups_here);
     if (!wave_has_work) {   // (a wave without groups in a ragged last tile)
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch) : : "memory");
@@ -175,9 +164,6 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
       const int coff = ((gw + h) & 1) * (2 * PLW) + 16 * (((gw + h) >> 1) + n);
       const char *pl = reinterpret_cast<const char *>(lo) + coff;
       const char *ph = reinterpret_cast<const char *>(hi) + coff;
-#ifdef K1_ABL_NOKLOOP   // tuning ablation (results wrong): no LDS operand reads, no MFMAs
-      acc_mid[0] = *reinterpret_cast<const int *>(ph); acc_ll[1] = *reinterpret_cast<const int *>(pl);
-#else
 #pragma unroll
       for (int s = 0; s < S; s++) {
         // the outer taps of a windowed sinc are small: where every tap a K step touches has a zero high byte, its
@@ -186,12 +172,6 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
         const bool has_ah = (a.ah_mask >> s) & 1;
         const v4i uh = *reinterpret_cast<const v4i *>(ph + 16 * s);
         const v4i Al = taps_s[(2 * s + 1) * 64 + l];
-#ifdef K1_ABL_NOMFMA    // tuning ablation (results wrong): the LDS operand reads stay, the matrix instructions go
-        acc_mid[s] += uh.x ^ uh.y ^ uh.z ^ uh.w ^ Al.x ^ Al.y ^ Al.z ^ Al.w;
-        { const v4i ul = *reinterpret_cast<const v4i *>(pl + 16 * s); acc_ll[s] += ul.x ^ ul.y ^ ul.z ^ ul.w; }
-        if (has_ah) { const v4i Ah = taps_s[(2 * s) * 64 + l]; acc_hh[s] += Ah.x ^ Ah.y ^ Ah.z ^ Ah.w; }
-        continue;
-#endif
         // (the unconditional low-plane products come first: step 0 writes acc_mid with C = 0, so that only acc_hh
         // needs an explicit zero — a conditional first write makes the compiler materialise zeros on the other path)
         acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(Al, uh, acc_mid, 0, 0, 0);
@@ -207,7 +187,6 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
           }
         }
       }
-#endif
       // ---- epilogue, all in this lane: the tap fragments' rows are permuted at create time so that lane (n, h)
       // holds the WHOLE decimation group glw = 2n + h of the wave — sample j = 0..7 of it in accumulator registers
       // 2j (re) and 2j+1 (im): recombine -> >>14 -> rotate -> the box sum takes the products' high halves ----
@@ -216,14 +195,8 @@ __global__ __launch_bounds__(TPB, CU8 ? 5 : 4) void iqbb_i16_mfma_kernel(const I
       int2 sum;
       // (two copies of the sample loop behind a scalar branch: written as one loop with `if (edge)` inside, the
       // compiler if-converts the border test into 8 compares + selects per sample on every tile)
-#ifdef K1_ABL_NOEPI   // tuning ablation (results wrong): no recombination / rotation / window sum
-      sum = make_int2(0, 0);
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) { sum.x += acc_hh[r] ^ acc_mid[r] ^ acc_ll[r]; sum.y += acc_hh[r + 1] ^ acc_mid[r + 1] ^ acc_ll[r + 1]; }
-#else
       if (edge) sum = group_sum<ROT, CU8, true>(a, acc_hh, acc_mid, acc_ll, rel0);
       else sum = group_sum<ROT, CU8, false>(a, acc_hh, acc_mid, acc_ll, rel0);
-#endif
       // the accumulators are dead now: the loads ride through the rest of the epilogue (the touch landed long ago)
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch) : : "memory");
       if (tile + 1 < tile_end) fetch(tile + 1);
@@ -287,7 +260,6 @@ __device__ __forceinline__ void iqbb_i16_mfma_dma_body(const IqbbArgs &a, const 
     const int first = a.base0_rel + q0_ * 8 - (a.OP - 1);
     const bool interior = first >= 0 && first + 4 * QUADS <= a.N;   // no history, no end of call (scalar)
     if (interior) {
-#ifndef K1_ABL_NOFETCH
 #pragma unroll
       for (int k = 0; k < NQ; k++) {
         const int p = tid + k * TPB;
@@ -295,7 +267,6 @@ __device__ __forceinline__ void iqbb_i16_mfma_dma_body(const IqbbArgs &a, const 
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(row + first + 4 * p),
                                            (__attribute__((address_space(3))) void *)(raw + (p - l)), 16, 0, 0);
       }
-#endif
     } else {
       // border tile: history / input / zeros per sample, branch-free — every load is issued unconditionally from a
       // clamped address and masked afterwards, so that all of a lane's 12 loads are in flight together (per-sample
@@ -363,9 +334,6 @@ __device__ __forceinline__ void iqbb_i16_mfma_dma_body(const IqbbArgs &a, const 
       const int coff = ((gw + h) & 1) * (2 * PLW) + 16 * (((gw + h) >> 1) + n);
       const char *pl = reinterpret_cast<const char *>(lo) + coff;
       const char *ph = reinterpret_cast<const char *>(hi) + coff;
-#ifdef K1_ABL_NOKLOOP   // tuning ablation (results wrong): no LDS operand reads, no MFMAs
-      acc_mid[0] = *reinterpret_cast<const int *>(ph); acc_ll[1] = *reinterpret_cast<const int *>(pl);
-#else
 #pragma unroll
       for (int s = 0; s < S; s++) {
         // the outer taps of a windowed sinc are small: where every tap a K step touches has a zero high byte, its
@@ -385,20 +353,12 @@ __device__ __forceinline__ void iqbb_i16_mfma_dma_body(const IqbbArgs &a, const 
           acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(Ah, ul, acc_mid, 0, 0, 0);
         }
       }
-#endif
       // ---- epilogue, all in this lane (see iqbb_i16_mfma_kernel): lane (n, h) holds the whole group 2n + h ----
       const int rel0 = tb + 8 * gw + MF_BLK * n + 8 * h;   // call-relative index of the lane's first sample
       const bool edge = (tb < 0) || (tb + groups_here * 8 > a.N);   // tile touches the call's borders (scalar)
       int2 sum;
-#ifdef K1_ABL_NOEPI   // tuning ablation (results wrong): no recombination / rotation / window sum
-      sum = make_int2(0, 0);
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) { sum.x += acc_hh[r] ^ acc_mid[r] ^ acc_ll[r]; sum.y += acc_hh[r + 1] ^ acc_mid[r + 1] ^ acc_ll[r + 1]; }
-      (void)rel0; (void)edge;
-#else
       if (edge) sum = group_sum<ROT, false, true>(a, acc_hh, acc_mid, acc_ll, rel0);
       else sum = group_sum<ROT, false, false>(a, acc_hh, acc_mid, acc_ll, rel0);
-#endif
       group_finish(a, lut_s, c, n, h, gw, q0, groups_here, sum);
     }
     // the channel's last tile rolls the FIR history forward
@@ -858,10 +818,6 @@ struct sdrhip_iqbb_i16 {
   DevBuf<unsigned long long> k1_stamps;   // diagnostic builds: per-wave phase totals of the hot kernel
 #endif
   DevBuf<short> philast;   // any-D hot form with FM: the last angle of every slice (HotArgs::philast)
-  DevBuf<long long> hs;    // ... where the units are not whole channels: the neighbouring slices' handshake entries (HotArgs::hs)
-  int hs_stride = 0, hs_seq = 0;
-  int env_fm_handshake = -1;   // SDRHIP_IQBB_FM_HANDSHAKE=0|1: the fix-up launch / the in-kernel handshake for such calls (-1 = 0: the launch — measured
-                               // equal at 1 channel and faster from 16 channels on, profiles/r17_ab_fm_handshake.txt, r17_fm_latency.txt)
   DevBuf<int2> part;       // decimations above 256: three partial box sums per slice of the longest call (HotArgs::part)
   // Decimations 257 ... 512 run either form: the any-D form's one group per slice uses D of a slice's 512 samples (÷257: half
   // of the matrix work is thrown away), the large-decimation form all of them plus a 5 us launch — measured crossover at
@@ -989,7 +945,7 @@ struct sdrhip_iqbb_i16 {
   // ones: units of tpw tiles (at most 4, fewer while the grid would get under 4 units per virtual workgroup; resident: a whole
   // channel), units dealt over the virtual workgroups. Returns the workgroups.
   unsigned hot_grid(HotArgs &ha, int tiles, int NW, bool resident) const {
-    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;   // virtual workgroups = waves per SIMD (SDRHIP_IQBB_WGPCU: tuning hook, builds with -DK1_MINWAVES=5)
+    const int nvwg = wgpcu() * ctx->prop.multiProcessorCount;   // virtual workgroups = waves per SIMD (SDRHIP_IQBB_WGPCU: tuning hook)
     int htpw = 4; while (htpw > 1 && (size_t)ceil_div((size_t)tiles, (size_t)htpw) * C < 4 * (size_t)nvwg) htpw >>= 1;
     if (resident) htpw = tiles;
     else if (env_tpw) htpw = env_tpw;   // tuning hook
@@ -1018,7 +974,7 @@ struct sdrhip_iqbb_i16 {
     // multi-buffer call with FM (launch_multi): the hot slices write the buffers' first two outputs themselves where the boundary
     // group and the one behind it are stored lanes of ONE hot slice; the others stay on the list for the fix-up launch
     ha.mb_p = 0; ha.mb_q1 = 0; ha.mb_qlast = 0; ha.mb_magic = 0;
-    if (!mb_q.empty() && epi == SDRHIP_EPI_FM && !i8 && !hot_pair(kind, hot_nw(), false)) {
+    if (!mb_q.empty() && epi == SDRHIP_EPI_FM && !i8) {
       const int per = 64 - ovl;   // stored groups per slice
       long P = mb_q.size() >= 2 ? (long)mb_q[1] - mb_q[0] : (long)1 << 30;
       bool uniform = P >= 128;
@@ -1133,31 +1089,17 @@ struct sdrhip_iqbb_i16 {
     // FM: the slices whose first output is neither out[0] nor out[1] (their own rules) and is emitted lack the angle of the
     // slice before them. Where whole channels deal evenly over the persistent grid (within 3 %: 1024 or 8192 channels on 1024
     // workgroups) a unit is a channel — one workgroup then finishes every slice of a channel and completes those outputs
-    // itself, behind a barrier at its end; otherwise (few channels: units of 4 tiles keep the grid full) a second launch does.
+    // itself, behind a barrier at its end; otherwise (few channels: units of 4 tiles keep the grid full) a second, tiny launch
+    // does (iqbb_fm_fixup_kernel: nothing that can be measured against one launch, profiles/r17_ab_fm_handshake.txt, r17_fm_latency.txt).
     const int fix_lo = GS == 1 ? 2 : 1, fix_hi = epi == SDRHIP_EPI_FM ? (int)ceil_div((size_t)g.n_out, (size_t)GS) : 0;
     const bool resident = fix_hi > fix_lo && channel_units();
     a.fix_lo = resident ? fix_lo : 0; a.fix_hi = resident ? fix_hi : 0;
-    // ... and where they do not (few channels, or a count that leaves the grid uneven): the owners of neighbouring slices
-    // can complete the first output between them by a handshake through device memory (iqbb_hot.hpp, hs_exchange) — ONE
-    // launch, in builds with -DK1_FM_HANDSHAKE under SDRHIP_IQBB_FM_HANDSHAKE=1. NOT in the shipped build: the write-through stores and the wait in front of the loads
-    // cost each wave two memory round trips per unit, and the second, tiny launch (iqbb_fm_fixup_kernel) it replaces costs
-    // nothing that can be measured — per buffer, host to host, on ONE channel: 42.2 us against 41.4 us (sdr_fm's plan),
-    // device-resident 11.7 against 11.2 us; at 128 channels 27 against 21 us (profiles/r17_*).
-#ifdef K1_FM_HANDSHAKE
-    const bool handshake = fix_hi > fix_lo && !resident && env_fm_handshake == 1 && hs.p != nullptr && 4 * tiles_h + 2 <= hs_stride;
-#else
-    const bool handshake = false;   // (the kernels are built without it: see iqbb_hot.hpp, hs_exchange)
-#endif
-    if (handshake) {
-      if (++hs_seq <= 0) hs_seq = 1;
-      ha.hs = hs.p; ha.hs_stride = hs_stride; ha.hs_seq = hs_seq;
-    }
     // (17 K steps: 8- or 16-wave workgroups = 2 or 4 virtual ones sharing the tap fragments, as the /8 kernel of that class;
     // the small-decimation form picks its own: hot_sd_nw)
     const int NW = D < 8 ? hot_sd_waves(S, kind, hot_range, inc != 0) : hot_nw();
     const HotLaunch hl{hot_grid(ha, tiles_h, NW, resident), ctx->stream};
     hot_launch(D < 8 ? HOT_SD : HOT_ANYD, S, kind, hot_range, -1, inc != 0, epi, hl, ha, a);
-    if (!resident && !handshake && fix_hi > fix_lo)
+    if (!resident && fix_hi > fix_lo)
       hipLaunchKernelGGL(iqbb_fm_fixup_kernel, dim3((unsigned)ceil_div((size_t)(fix_hi - fix_lo), (size_t)256), (unsigned)C), dim3(256), 0, ctx->stream,
                          reinterpret_cast<short *>(out_dev), (long)out_stride, philast.p, 4 * tiles_h, fix_lo, fix_hi, GS, C);
     return true;
@@ -1180,9 +1122,6 @@ struct sdrhip_iqbb_i16 {
     a.CG = CG; a.OG = OG; a.ovl = ovl; a.CGr = (CG + 3) & ~3;
     a.out = out_dev; a.out_stride = (long)out_stride; a.epilogue = epi;
     a.tapfrag = tapfrag.p; a.cre = cre; a.cim = cim; a.ah_mask = (unsigned)ah_mask;   // (the general kernels: at most 17 steps)
-#ifdef SDRHIP_AH_FULL
-    a.ah_mask = ~0u;   // tuning: never skip
-#endif
     const int tiles = (int)ceil_div((size_t)g.n_groups, (size_t)OG);
     // MFMA path: one workgroup walks `tpw` consecutive tiles so that the tap fragments are fetched once;
     // keep >= ~8 workgroups per CU in flight for balance
@@ -1234,7 +1173,7 @@ struct sdrhip_iqbb_i16 {
     if (f.n_long == 0) return general[f.short_form];
     if (f.long_form[0] == LONG_HOT8) return "iqbb_hot_kernel";
     if (f.long_form[0] == LONG_BIGD) return channel_units() ? "iqbb_hot_anyd_kernel" : "iqbb_hot_anyd_kernel,iqbb_bigd_finish_kernel";
-    const bool fixup = epi == SDRHIP_EPI_FM && !channel_units() && (env_fm_handshake != 1 || !hs.p);   // (launch_anyd_call)
+    const bool fixup = epi == SDRHIP_EPI_FM && !channel_units();   // (launch_anyd_call)
     return std::string(D < 8 ? "iqbb_hot_sd_kernel" : "iqbb_hot_anyd_kernel") + (fixup ? ",iqbb_fm_fixup_kernel" : "");
   }
   void launch_short(int form, IqbbArgs &a, int tiles) {
@@ -1390,7 +1329,6 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       { const char *e = getenv("SDRHIP_IQBB_TPW"); if (e) h->env_tpw = std::max(1, atoi(e)); }
       { const char *e = getenv("SDRHIP_IQBB_WGPCU"); if (e) h->env_wgpcu = std::max(1, atoi(e)); }
       { const char *e = getenv("SDRHIP_IQBB_FM_RESIDENT"); if (e) h->env_fm_resident = atoi(e) != 0; }
-      { const char *e = getenv("SDRHIP_IQBB_FM_HANDSHAKE"); if (e) h->env_fm_handshake = atoi(e) != 0; }
       { const char *e = getenv("SDRHIP_IQBB_TRIM"); if (e && e[0] == '0') h->env_trim = false; }   // A/B, tests: the full low-plane range
       const char *force = getenv("SDRHIP_IQBB_PATH");   // "valu": test hook (the VALU kernel for every plan)
       if (force && !strcmp(force, "valu")) mfma_ok = false;
@@ -1458,10 +1396,6 @@ int create_baseband(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32
       if (epilogue == SDRHIP_EPI_FM && (h->path == 3 || h->real_anyd()) && decim >= 1 && decim <= 512) {   // any-D hot forms: one angle per slice of the longest call (launch_anyd_call)
         const size_t GS = 512 / (size_t)decim, tiles_h = ceil_div(max_in / (size_t)decim + 2, 4 * GS);
         h->philast.alloc((size_t)channels * 4 * tiles_h + 1024);
-#ifdef K1_FM_HANDSHAKE
-        h->hs_stride = (int)(4 * tiles_h + 2);
-        h->hs.alloc((size_t)2 * channels * h->hs_stride); h->hs.zero(ctx->stream);   // (call numbers start at 1: a zeroed entry matches none)
-#endif
       }
       { const char *e = getenv("SDRHIP_IQBB_BIGD_MIN"); if (e) { h->bigd_min = std::max(257, atoi(e)); h->bigd_skip_lo = 513; } }   // tuning / test hook
       { const char *e = getenv("SDRHIP_IQBB_BIGD_ALWAYS"); if (e && atoi(e) != 0 && decim >= 257) { h->bigd_always = true; h->bigd_skip_lo = 513; } }   // test hook: short calls too

@@ -176,7 +176,6 @@ def test_iqbb_any_decimation_long_calls_vs_oracle(ctx, orc, order, decim, Fc, cu
     channels get by themselves: SDRHIP_IQBB_FM_RESIDENT forces it on these 3)."""
     monkeypatch.setenv("SDRHIP_IQBB_HOT", "1" if hot else "0")
     monkeypatch.setenv("SDRHIP_IQBB_FM_RESIDENT", "1" if hot == "resident" else "0")
-    monkeypatch.delenv("SDRHIP_IQBB_FM_HANDSHAKE", raising=False)
     monkeypatch.delenv("SDRHIP_IQBB_PATH", raising=False)
     monkeypatch.delenv("SDRHIP_IQBB_BIGD_MIN", raising=False)
     # decimations 257 ... 512 run either of two hot forms (by default the faster one: the large-decimation form below 465):
@@ -299,7 +298,6 @@ def test_iqbb_any_decimation_more_channels_than_workgroups(ctx, orc, epi, reside
     then walk two channels and complete both themselves)."""
     handshake = False
     monkeypatch.setenv("SDRHIP_IQBB_FM_RESIDENT", "1" if resident else "0")
-    monkeypatch.delenv("SDRHIP_IQBB_FM_HANDSHAKE", raising=False)
     C, N, D = 1100, 40001, 62
     FSr = 1e6
     taps, lut, inc = orc.iqbb_design(100e3, 12.5e3, FSr, 16), orc.freqshift_lut_i16(), orc.freqshift_inc(-100e3, FSr)
@@ -325,20 +323,17 @@ def test_iqbb_any_decimation_more_channels_than_workgroups(ctx, orc, epi, reside
 @pytest.mark.parametrize("order,decim,Fc,cu8", [(21, 125, 100e3, True), (16, 20, 0.0, True), (21, 4, 100e3, True), (127, 125, -100e3, False)])
 def test_iqbb_fm_at_any_channel_count(ctx, orc, C, order, decim, Fc, cu8, monkeypatch):
     """The reference's graphs are ONE channel (examples/sdr_fm.cc:40-43: 21 taps, /125; sdr_rec.cc:66-72): FM at a decimation
-    other than 8 on 1, 16, 128 and 1100 channels — the hot kernel + the tiny fix-up launch (or, in a -DK1_FM_HANDSHAKE build under
-    SDRHIP_IQBB_FM_HANDSHAKE=1, ONE launch: the neighbouring slices' handshake) — with ragged calls (a call that ends inside
-    a group, a one-sample call) and the state carried across them, bit-exact against the oracle on every channel. (The
-    handshake measured no faster at any channel count — profiles/r17_ab_fm_handshake.txt — and is not in the shipped build.)"""
+    other than 8 on 1, 16, 128 and 1100 channels — the hot kernel + the tiny fix-up launch — with ragged calls (a call that ends
+    inside a group, a one-sample call) and the state carried across them, bit-exact against the oracle on every channel."""
     for k in ("SDRHIP_IQBB_HOT", "SDRHIP_IQBB_FM_RESIDENT", "SDRHIP_IQBB_PATH"):
         monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("SDRHIP_IQBB_FM_HANDSHAKE", "1")
     FSr = 1e6
     taps, lut, inc = orc.iqbb_design(abs(Fc), 12.5e3, FSr, order), orc.freqshift_lut_i16(), orc.freqshift_inc(Fc, FSr)
     node = sa.IQBaseBandI16(ctx, taps, lut, inc, Fc < 0, decim, channels=C, max_in=65536, epilogue=sa.EPI_FM)
     if cu8:
         node.set_input_format(sa.abi.IN_CU8)
     hot_name = "iqbb_hot_sd_kernel" if decim < 8 else "iqbb_hot_anyd_kernel"
-    assert node.kernel_names in ([hot_name], [hot_name, "iqbb_fm_fixup_kernel"])   # (one launch only in a handshake build)
+    assert node.kernel_names in ([hot_name], [hot_name, "iqbb_fm_fixup_kernel"])   # (one launch where whole channels are the hot kernel's units)
     rng = np.random.default_rng(C * 1000 + decim)
     nb = min(C, 8)
     refs = [(orc.IQBaseBandI16(taps, lut, inc, Fc < 0, decim), orc.FMDemodI16()) for _ in range(nb)]

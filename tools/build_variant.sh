@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds libsdr_amd/libsdrhip_<name>.so = the library with the K1 sources (iqbb_i16.hip, iqbb_hot_*.hip; or the sources
 # named on the command line) compiled under extra flags (tuning A/B: tools/abk1.py times several such builds against each other in one process on one box).
-# usage: tools/build_variant.sh <name> "<flags>" [only-these-sources...]   e.g.  tools/build_variant.sh noepi "-DK1_ABL_NOEPI"
+# usage: tools/build_variant.sh <name> "<flags>" [only-these-sources...]   e.g.  tools/build_variant.sh stamps "-DK1_STAMPS"
 set -e
 cd $(dirname $0)/../libsdr_amd/csrc
 NAME=$1; FLAGS=$2; shift 2
