@@ -1,0 +1,100 @@
+// entry.hpp — the contract of the C entry points around a node handle (create / process_dev / process / reset / destroy),
+// written once. Host only; every helper runs inside the entry point's guarded() and reports through SDRHIP_REQUIRE.
+// A handle type H has `sdrhip_ctx *ctx` and, for call_begin, `size_t max_in`.
+#pragma once
+#include "sdrhip_internal.hpp"
+
+namespace sdrhip {
+
+// ---- handle lifetime ---------------------------------------------------------------------------------------------------
+// init(h) holds the node's own argument checks (first: nothing is allocated on the device before them) and fills the
+// handle; a failure anywhere deletes it, so a handle that owns another one releases it in its destructor. `others`: the
+// node's further pointer arguments, non-NULL.
+template <class H, class Init>
+static inline void make_handle(sdrhip_ctx *ctx, H **out, bool others, Init &&init) {
+  SDRHIP_REQUIRE(ctx && out && others, SDRHIP_E_INVALID, "NULL argument");
+  *out = nullptr;
+  ctx->use();
+  H *h = new H;
+  try {
+    h->ctx = ctx;
+    init(h);
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  } catch (...) { delete h; throw; }
+  *out = h;
+}
+
+template <class H>
+static inline void destroy_handle(H *h) {
+  if (!h) return;
+  h->ctx->use();
+  (void)hipStreamSynchronize(h->ctx->stream);   // launches in flight still use the handle's buffers
+  delete h;
+}
+
+// reset / set_*: a live handle on its device
+template <class H>
+static inline void use_handle(H *h) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  h->ctx->use();
+}
+
+// ---- argument rules of create ------------------------------------------------------------------------------------------
+static inline void require_channels(int channels, int cap) {
+  SDRHIP_REQUIRE(channels >= 1 && channels <= cap, SDRHIP_E_INVALID, "channels %d outside [1,%d]", channels, cap);
+}
+static inline void require_max_in(size_t max_in) {
+  SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
+}
+
+// ---- the head of a process / process_dev call ----------------------------------------------------------------------------
+// In this order: handle, n against max_in, the empty call (false: nothing to do, and nothing else is looked at), buffers.
+// n_name: what the header calls the count ("n", "n_in") — it appears in the messages.
+template <class H>
+static inline bool call_begin(const H *h, const char *n_name, size_t n, const void *in, const void *out) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  SDRHIP_REQUIRE(n <= h->max_in, SDRHIP_E_SIZE, "%s %zu > max_in %zu", n_name, n, h->max_in);
+  if (n == 0) return false;
+  SDRHIP_REQUIRE(in && out, SDRHIP_E_INVALID, "NULL buffer");
+  return true;
+}
+
+// Row strides in elements: 0 means packed (in: n, out: the call's output row, which only the node knows). Which checks a
+// node makes here is the call site's to say — the copies differed, and the differences are part of the ABI's behaviour:
+enum : unsigned {
+  STRIDES_TOGETHER = 1,   // one check of both, "stride smaller than <n_name>"
+  STRIDE_IN = 2,          // "in_stride a < <n_name> b"
+  STRIDE_OUT = 4,         // "out_stride a < <out_name> b" (where absent, launch() makes this check)
+};
+struct Strides { size_t in, out; };
+static inline Strides call_strides(const char *n_name, size_t n, size_t in_stride, size_t out_row, size_t out_stride, unsigned checks,
+                            const char *out_name = "outputs") {
+  if (in_stride == 0) in_stride = n;
+  if (out_stride == 0) out_stride = out_row;
+  if (checks & STRIDES_TOGETHER)
+    SDRHIP_REQUIRE(in_stride >= n && out_stride >= out_row, SDRHIP_E_SIZE, "stride smaller than %s", n_name);
+  if (checks & STRIDE_IN) SDRHIP_REQUIRE(in_stride >= n, SDRHIP_E_SIZE, "in_stride %zu < %s %zu", in_stride, n_name, n);
+  if (checks & STRIDE_OUT)
+    SDRHIP_REQUIRE(out_stride >= out_row, SDRHIP_E_SIZE, "out_stride %zu < %s %zu", out_stride, out_name, out_row);
+  return {in_stride, out_stride};
+}
+
+// ---- host-pointer calls: staged through packed device rows -------------------------------------------------------------
+struct Staging { DevBuf<uint8_t> in, out; };   // allocated by the first host-pointer call, for the plan's largest one
+
+struct HostIn { const void *p; size_t pitch_b, row_b, rows; };       // the caller's rows; staged packed (pitch = row_b)
+struct HostOut { void *p; size_t pitch_b, stage_pitch_b, rows; };    // stage_pitch_b: the row pitch launch writes with
+// launch(in_dev, out_dev) runs the node on the staging buffers — with whatever the node needs around its launch — and
+// returns the bytes per output row that go back to the caller.
+template <class Launch>
+static inline void run_staged(sdrhip_ctx *ctx, Staging &st, size_t in_cap_b, size_t out_cap_b, const HostIn &in, const HostOut &out,
+                       Launch &&launch) {
+  ctx->use();
+  if (!st.in.p) { st.in.alloc(in_cap_b); st.out.alloc(out_cap_b); }
+  copy_h2d_rows(ctx, st.in.p, in.row_b, in.p, in.pitch_b, in.row_b, in.rows);
+  const size_t row_b = launch(st.in.p, st.out.p);
+  copy_d2h_rows(ctx, out.p, out.pitch_b, st.out.p, out.stage_pitch_b, row_b, out.rows);
+  SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+}  // namespace sdrhip

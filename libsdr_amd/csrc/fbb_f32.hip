@@ -9,6 +9,7 @@
 // fir_cf32_rt_kernel: closed form per lane and tile, constant float64 rotation in between), so the
 // whole chain is ONE launch with 8 B read + 1 B written per input sample. PARITY UNPINNED for the shift.
 #include "sdrhip_internal.hpp"
+#include "entry.hpp"
 
 using namespace sdrhip;
 
@@ -19,8 +20,9 @@ struct sdrhip_fbb_f32 {
   int C = 1;
   size_t max_in = 0;
   unsigned long long n0 = 0;
-  DevBuf<float2> stage_in, stage_out;
+  Staging stage;
   size_t max_out = 0;
+  ~sdrhip_fbb_f32() { if (fir) sdrhip_fir_destroy(fir); }   // (create's failure path and destroy)
 };
 
 extern "C" {
@@ -28,19 +30,15 @@ extern "C" {
 int sdrhip_fbb_f32_create(sdrhip_ctx *ctx, double Fc, double Fs, const double *alpha, int order, int decim,
                           int channels, size_t max_in, sdrhip_fbb_f32 **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && alpha && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(Fs > 0, SDRHIP_E_INVALID, "sample rate must be positive");
-    ctx->use();
-    sdrhip_fbb_f32 *h = new sdrhip_fbb_f32;
-    try {
-      h->ctx = ctx; h->fc = Fc; h->fs = Fs; h->C = channels; h->max_in = max_in;
+    make_handle(ctx, out, alpha != nullptr, [&](sdrhip_fbb_f32 *h) {
+      SDRHIP_REQUIRE(Fs > 0, SDRHIP_E_INVALID, "sample rate must be positive");
+      h->fc = Fc; h->fs = Fs; h->C = channels; h->max_in = max_in;
+      // (channels, max_in, order and decim are the FIR's to check)
       int rc = fir_create_impl(ctx, SDRHIP_FIR_CF32, alpha, order, decim, channels, max_in, SDRHIP_EPI_NONE, false, &h->fir);   // (the shift rides in the time-domain kernel's staging)
       if (rc != SDRHIP_OK) throw Failure{rc};
       fir_set_shift(h->fir, Fc, Fs);   // the shift rides in the FIR's staging: one kernel, no intermediate buffer
       h->max_out = max_in / decim + 1;
-    } catch (...) { if (h->fir) sdrhip_fir_destroy(h->fir); delete h; throw; }
-    *out = h;
+    });
   });
 }
 
@@ -58,12 +56,8 @@ int sdrhip_fbb_f32_process_dev(sdrhip_fbb_f32 *h, const float *in_dev, size_t n_
                                size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fbb_f32_process_dev");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) { if (n_out) *n_out = 0; return; }
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    if (in_stride == 0) in_stride = n_in;
+    if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) { if (n_out) *n_out = 0; return; }
+    // the strides, the overlap and the launch are the FIR's device entry point's
     int rc = sdrhip_fir_process_dev(h->fir, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
     if (rc != SDRHIP_OK) throw Failure{rc};
     h->n0 += n_in;
@@ -74,25 +68,20 @@ int sdrhip_fbb_f32_process(sdrhip_fbb_f32 *h, const float *in_host, size_t n_in,
                            size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fbb_f32_process");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) { if (n_out) *n_out = 0; return; }
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    if (in_stride == 0) in_stride = n_in;
+    if (!call_begin(h, "n_in", n_in, in_host, out_host)) { if (n_out) *n_out = 0; return; }
     size_t no = 0;
     int rc = sdrhip_fir_out_count(h->fir, n_in, &no);
     if (rc != SDRHIP_OK) throw Failure{rc};
-    if (out_stride == 0) out_stride = no;
-    SDRHIP_REQUIRE(out_stride >= no, SDRHIP_E_SIZE, "out_stride %zu < outputs %zu", out_stride, no);
-    if (!h->stage_in.p) { h->stage_in.alloc((size_t)h->C * h->max_in); h->stage_out.alloc((size_t)h->C * h->max_out); }
-    copy_h2d_rows(h->ctx, h->stage_in.p, n_in * 8, in_host, in_stride * 8, n_in * 8, h->C);
+    // (no in_stride check, as the FIR's host entry point: looks like an oversight, kept)
+    const Strides s = call_strides("n_in", n_in, in_stride, no, out_stride, STRIDE_OUT);
+    const size_t C = (size_t)h->C;
     size_t produced = 0;
-    rc = sdrhip_fbb_f32_process_dev(h, reinterpret_cast<const float *>(h->stage_in.p), n_in, n_in,
-                                    reinterpret_cast<float *>(h->stage_out.p), h->max_out, &produced);
-    if (rc != SDRHIP_OK) throw Failure{rc};
-    copy_d2h_rows(h->ctx, out_host, out_stride * 8, h->stage_out.p, h->max_out * 8, produced * 8, h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    run_staged(h->ctx, h->stage, C * h->max_in * 8, C * h->max_out * 8, {in_host, s.in * 8, n_in * 8, C},
+               {out_host, s.out * 8, h->max_out * 8, C}, [&](void *in, void *out) {
+                 fir_launch(h->fir, in, n_in, n_in, out, h->max_out, &produced);
+                 h->n0 += n_in;
+                 return produced * 8;
+               });
     if (n_out) *n_out = produced;
   });
 }
@@ -123,13 +112,7 @@ int sdrhip_fbb_f32_reset(sdrhip_fbb_f32 *h) {
 }
 
 int sdrhip_fbb_f32_destroy(sdrhip_fbb_f32 *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->fir) sdrhip_fir_destroy(h->fir);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });   // (~sdrhip_fbb_f32 releases the FIR)
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 // digit-reversed order), the kernel spectrum is stored pre-permuted and pre-scaled by 1/L, and
 // the inverse is the mirrored in-place DIT, so no reordering pass is ever executed.
 #include "sdrhip_internal.hpp"
+#include "entry.hpp"
 
 #include <cmath>
 #include <complex>
@@ -773,6 +774,15 @@ void allow_big_lds(K kernel, size_t bytes) { allow_lds_max(kernel, bytes); }   /
 // The general plan (fftgen.hpp) behind the same handle: any FFT size made of the factors 2 ... 13 in complex<float>, and
 // every size in complex<double> (FilterNode<double>, FFTPlan<double>). Same overlap-save evaluation, same state rules.
 // what the handle holds for every plan other than the tuned power-of-two complex<float> one
+// a filter bank's host-pointer call, the same for every plan type: C rows go up, B x C rows of n_in elements come back
+template <class Launch>
+void run_conv_staged(sdrhip_ctx *ctx, Staging &st, size_t eb, int C, int B, size_t max_in, const void *in_host, size_t n_in,
+                     const Strides &s, void *out_host, Launch &&launch) {
+  const size_t rows = (size_t)C, out_rows = (size_t)B * C;
+  run_staged(ctx, st, rows * max_in * eb, out_rows * max_in * eb, {in_host, s.in * eb, n_in * eb, rows},
+             {out_host, s.out * eb, n_in * eb, out_rows}, [&](void *in, void *out) { launch(in, out); return n_in * eb; });
+}
+
 struct ConvAny {
   bool f64 = false;
   virtual ~ConvAny() {}
@@ -790,7 +800,8 @@ struct GenConv : ConvAny {
   int mode = 0, C = 1, B = 1, hop = 0, HH = 0, par = 0, n_taps = 0;
   size_t max_in = 0;
   fftgen::GenPlan<T2> plan;
-  DevBuf<T2> Kp, hist[2], stage_in, stage_out;
+  DevBuf<T2> Kp, hist[2];
+  Staging stage;
   static constexpr size_t kMaxLds = 160 * 1024;
 
   void create(sdrhip_ctx *ctx_, int mode_, int L, const R *kernels, int n_taps_, int n_bands, int channels, size_t max_in_) {
@@ -842,29 +853,17 @@ struct GenConv : ConvAny {
     if (HH > 0) par ^= 1;
   }
   void process_dev(const R *in_dev, size_t n_in, size_t in_stride, R *out_dev, size_t out_stride) {
-    SDRHIP_REQUIRE(n_in <= max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    require_disjoint(in_dev, in_stride, n_in, sizeof(T2), out_dev, out_stride, n_in, sizeof(T2), (size_t)C, (size_t)C * B);
-    launch(reinterpret_cast<const T2 *>(in_dev), n_in, in_stride, reinterpret_cast<T2 *>(out_dev), out_stride, (size_t)C * out_stride);
+    if (!call_begin(this, "n_in", n_in, in_dev, out_dev)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    require_disjoint(in_dev, s.in, n_in, sizeof(T2), out_dev, s.out, n_in, sizeof(T2), (size_t)C, (size_t)C * B);
+    launch(reinterpret_cast<const T2 *>(in_dev), n_in, s.in, reinterpret_cast<T2 *>(out_dev), s.out, (size_t)C * s.out);
   }
   void process(const R *in_host, size_t n_in, size_t in_stride, R *out_host, size_t out_stride) {
-    SDRHIP_REQUIRE(n_in <= max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    ctx->use();
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    if (!stage_in.p) { stage_in.alloc((size_t)C * max_in); stage_out.alloc((size_t)B * C * max_in); }
-    const size_t eb = sizeof(T2);
-    copy_h2d_rows(ctx, stage_in.p, n_in * eb, in_host, in_stride * eb, n_in * eb, C);
-    launch(stage_in.p, n_in, n_in, stage_out.p, n_in, (size_t)C * n_in);
-    copy_d2h_rows(ctx, out_host, out_stride * eb, stage_out.p, n_in * eb, n_in * eb, (size_t)B * C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!call_begin(this, "n_in", n_in, in_host, out_host)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    run_conv_staged(ctx, stage, sizeof(T2), C, B, max_in, in_host, n_in, s, out_host, [&](void *in, void *out) {
+      launch(static_cast<const T2 *>(in), n_in, n_in, static_cast<T2 *>(out), n_in, (size_t)C * n_in);
+    });
   }
   void reset() override { ctx->use(); for (int p = 0; p < 2; p++) hist[p].zero(ctx->stream); }
   void load_kernel(int band, const void *kernel) override { load_kernel(band, static_cast<const R *>(kernel)); }
@@ -926,7 +925,8 @@ struct BigConv : ConvAny {
   long L = 0;
   size_t max_in = 0;
   fftany::AnyFft<T2> fft;
-  DevBuf<T2> Kp, hist[2], X, Y, stage_in, stage_out;
+  DevBuf<T2> Kp, hist[2], X, Y;
+  Staging stage;
   int group = 1;   // channels per pass
   static constexpr size_t kScratchBytes = (size_t)1 << 30;
 
@@ -1018,29 +1018,17 @@ struct BigConv : ConvAny {
     SDRHIP_CHECK_HIP(hipGetLastError());
   }
   void process_dev(const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride) override {
-    SDRHIP_REQUIRE(n_in <= max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    require_disjoint(in_dev, in_stride, n_in, sizeof(T2), out_dev, out_stride, n_in, sizeof(T2), (size_t)C, (size_t)C * B);
-    launch(static_cast<const T2 *>(in_dev), n_in, in_stride, static_cast<T2 *>(out_dev), out_stride, (size_t)C * out_stride);
+    if (!call_begin(this, "n_in", n_in, in_dev, out_dev)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    require_disjoint(in_dev, s.in, n_in, sizeof(T2), out_dev, s.out, n_in, sizeof(T2), (size_t)C, (size_t)C * B);
+    launch(static_cast<const T2 *>(in_dev), n_in, s.in, static_cast<T2 *>(out_dev), s.out, (size_t)C * s.out);
   }
   void process(const void *in_host, size_t n_in, size_t in_stride, void *out_host, size_t out_stride) override {
-    SDRHIP_REQUIRE(n_in <= max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    ctx->use();
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    if (!stage_in.p) { stage_in.alloc((size_t)C * max_in); stage_out.alloc((size_t)B * C * max_in); }
-    const size_t eb = sizeof(T2);
-    copy_h2d_rows(ctx, stage_in.p, n_in * eb, in_host, in_stride * eb, n_in * eb, C);
-    launch(stage_in.p, n_in, n_in, stage_out.p, n_in, (size_t)C * n_in);
-    copy_d2h_rows(ctx, out_host, out_stride * eb, stage_out.p, n_in * eb, n_in * eb, (size_t)B * C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!call_begin(this, "n_in", n_in, in_host, out_host)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    run_conv_staged(ctx, stage, sizeof(T2), C, B, max_in, in_host, n_in, s, out_host, [&](void *in, void *out) {
+      launch(static_cast<const T2 *>(in), n_in, n_in, static_cast<T2 *>(out), n_in, (size_t)C * n_in);
+    });
   }
   void reset() override { ctx->use(); for (int p = 0; p < 2; p++) hist[p].zero(ctx->stream); }
   const char *kernel_names() const override { return fft.fuses() ? "fourstep_tile_kernel x4 (gather, product, scatter fused)" : "big_gather_kernel,fft passes,big_mul_kernel,big_scatter_kernel"; }
@@ -1065,7 +1053,7 @@ struct sdrhip_fftconv {
   FftPlan plan;
   DevBuf<float2> Kp;
   DevBuf<float2> hist[2];
-  DevBuf<float2> stage_in, stage_out;
+  Staging stage;
   int stamps_grid = 0;   // (diagnostic builds)
   DevBuf<float2> dump;   // (the pipelined 16384-point form) 128 bytes per wave of its grid for the stores of masked lanes
 
@@ -1339,16 +1327,12 @@ extern "C" {
 int sdrhip_fftconv_create_bank(sdrhip_ctx *ctx, int mode, int fft_size, const float *kernels, int n_taps, int n_bands,
                                int channels, size_t max_in, sdrhip_fftconv **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && kernels && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(mode == SDRHIP_FFTCONV_OLA || mode == SDRHIP_FFTCONV_OLS, SDRHIP_E_INVALID, "bad mode %d", mode);
-    SDRHIP_REQUIRE(channels >= 1 && channels <= 65535, SDRHIP_E_INVALID, "channels %d outside [1,65535]", channels);
-    SDRHIP_REQUIRE(n_bands >= 1 && n_bands <= 256, SDRHIP_E_INVALID, "n_bands %d outside [1,256]", n_bands);
-    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
-    ctx->use();
-    sdrhip_fftconv *h = new sdrhip_fftconv;
-    try {
-      h->ctx = ctx; h->mode = mode; h->C = channels; h->max_in = max_in; h->B = n_bands;
+    make_handle(ctx, out, kernels != nullptr, [&](sdrhip_fftconv *h) {
+      SDRHIP_REQUIRE(mode == SDRHIP_FFTCONV_OLA || mode == SDRHIP_FFTCONV_OLS, SDRHIP_E_INVALID, "bad mode %d", mode);
+      require_channels(channels, 65535);
+      SDRHIP_REQUIRE(n_bands >= 1 && n_bands <= 256, SDRHIP_E_INVALID, "n_bands %d outside [1,256]", n_bands);
+      require_max_in(max_in);
+      h->mode = mode; h->C = channels; h->max_in = max_in; h->B = n_bands;
       std::vector<float> taps_all;
       // (a single band on a power of two as well: half of every 2N-point block is overlap, a longer block keeps up to 7/8 —
       // N = 256: 13.9 -> 50.4 % of the roofline, 512: 28 -> 43 %, 2048: 29.5 -> 33 %, 4096: 21.6 -> 28 % at 256 channels. Not the
@@ -1380,7 +1364,6 @@ int sdrhip_fftconv_create_bank(sdrhip_ctx *ctx, int mode, int fft_size, const fl
       }
       if (!is_pow2(fft_size) || fft_size < 4 || fft_size > 16384) {   // (FilterNode(size_t block_size) takes any block size: src/filternode.hh:235-245)
         h->any.reset(make_any_conv<float2, float>(ctx, mode, fft_size, kernels, n_taps, n_bands, channels, max_in));
-        *out = h;
         return;
       }
       h->plan.build(ctx, fft_size);
@@ -1403,9 +1386,7 @@ int sdrhip_fftconv_create_bank(sdrhip_ctx *ctx, int mode, int fft_size, const fl
       const size_t per_band = mode == SDRHIP_FFTCONV_OLA ? (size_t)2 * L : (size_t)2 * n_taps;   // floats per band in `kernels`
       for (int b = 0; b < n_bands; b++) h->load_kernel(b, kernels + (size_t)b * per_band);
       for (int p = 0; p < 2; p++) { h->hist[p].alloc((size_t)channels * std::max(1, h->HL)); h->hist[p].zero(ctx->stream); }
-      SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) { delete h; throw; }
-    *out = h;
+    });
   });
 }
 
@@ -1442,15 +1423,10 @@ int sdrhip_fftconv_process_dev(sdrhip_fftconv *h, const float *in_dev, size_t n_
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(!(h->any && h->any->f64), SDRHIP_E_INVALID, "a complex<double> plan: use sdrhip_fftconv_f64_process_dev");
     if (h->any) { h->any->process_dev(in_dev, n_in, in_stride, out_dev, out_stride); return; }
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    require_disjoint(in_dev, in_stride, n_in, 8, out_dev, out_stride, n_in, 8, (size_t)h->C, (size_t)h->C * h->B);
-    h->launch(reinterpret_cast<const float2 *>(in_dev), n_in, in_stride, reinterpret_cast<float2 *>(out_dev), out_stride,
-              (size_t)h->C * out_stride);
+    if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    require_disjoint(in_dev, s.in, n_in, 8, out_dev, s.out, n_in, 8, (size_t)h->C, (size_t)h->C * h->B);
+    h->launch(reinterpret_cast<const float2 *>(in_dev), n_in, s.in, reinterpret_cast<float2 *>(out_dev), s.out, (size_t)h->C * s.out);
   });
 }
 
@@ -1461,53 +1437,36 @@ int sdrhip_fftconv_process(sdrhip_fftconv *h, const float *in_host, size_t n_in,
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(!(h->any && h->any->f64), SDRHIP_E_INVALID, "a complex<double> plan: use sdrhip_fftconv_f64_process");
     if (h->any) { h->any->process(in_host, n_in, in_stride, out_host, out_stride); return; }
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) return;
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    if (in_stride == 0) in_stride = n_in;
-    if (out_stride == 0) out_stride = n_in;
-    SDRHIP_REQUIRE(in_stride >= n_in && out_stride >= n_in, SDRHIP_E_SIZE, "stride smaller than n_in");
-    if (!h->stage_in.p) { h->stage_in.alloc((size_t)h->C * h->max_in); h->stage_out.alloc((size_t)h->B * h->C * h->max_in); }
-    copy_h2d_rows(h->ctx, h->stage_in.p, n_in * 8, in_host, in_stride * 8, n_in * 8, h->C);
-    h->launch(h->stage_in.p, n_in, n_in, h->stage_out.p, n_in, (size_t)h->C * n_in);
-    copy_d2h_rows(h->ctx, out_host, out_stride * 8, h->stage_out.p, n_in * 8, n_in * 8, (size_t)h->B * h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    if (!call_begin(h, "n_in", n_in, in_host, out_host)) return;
+    const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
+    run_conv_staged(h->ctx, h->stage, 8, h->C, h->B, h->max_in, in_host, n_in, s, out_host, [&](void *in, void *out) {
+      h->launch(static_cast<const float2 *>(in), n_in, n_in, static_cast<float2 *>(out), n_in, (size_t)h->C * n_in);
+    });
   });
 }
 
 int sdrhip_fftconv_reset(sdrhip_fftconv *h) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    h->ctx->use();
+    use_handle(h);
     if (h->any) { h->any->reset(); return; }
     for (int p = 0; p < 2; p++) h->hist[p].zero(h->ctx->stream);
   });
 }
 
 int sdrhip_fftconv_destroy(sdrhip_fftconv *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 // ---- FilterNode<double> (reference src/filternode.hh:230-232: the filter classes are templates over Scalar) ----
 int sdrhip_fftconv_f64_create_bank(sdrhip_ctx *ctx, int mode, int fft_size, const double *kernels, int n_taps, int n_bands,
                                    int channels, size_t max_in, sdrhip_fftconv **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && kernels && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(mode == SDRHIP_FFTCONV_OLA || mode == SDRHIP_FFTCONV_OLS, SDRHIP_E_INVALID, "bad mode %d", mode);
-    SDRHIP_REQUIRE(channels >= 1 && channels <= 65535, SDRHIP_E_INVALID, "channels %d outside [1,65535]", channels);
-    SDRHIP_REQUIRE(n_bands >= 1 && n_bands <= 256, SDRHIP_E_INVALID, "n_bands %d outside [1,256]", n_bands);
-    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
-    ctx->use();
-    sdrhip_fftconv *h = new sdrhip_fftconv;
-    try {
-      h->ctx = ctx; h->mode = mode; h->C = channels; h->max_in = max_in; h->B = n_bands;
+    make_handle(ctx, out, kernels != nullptr, [&](sdrhip_fftconv *h) {
+      SDRHIP_REQUIRE(mode == SDRHIP_FFTCONV_OLA || mode == SDRHIP_FFTCONV_OLS, SDRHIP_E_INVALID, "bad mode %d", mode);
+      require_channels(channels, 65535);
+      SDRHIP_REQUIRE(n_bands >= 1 && n_bands <= 256, SDRHIP_E_INVALID, "n_bands %d outside [1,256]", n_bands);
+      require_max_in(max_in);
+      h->mode = mode; h->C = channels; h->max_in = max_in; h->B = n_bands;
       std::vector<double> taps_all;
       if (mode == SDRHIP_FFTCONV_OLA && !(is_pow2(fft_size) && fft_size <= 8192) && fft_size % 2 == 0 && fft_size >= 4 && !getenv("SDRHIP_FFTCONV_LITERAL")) {
         const int N = fft_size / 2, lp = overlap_save_fft_size(N, 8192);   // (as the complex<float> plans: the general in-LDS plan's power-of-two passes)
@@ -1521,8 +1480,7 @@ int sdrhip_fftconv_f64_create_bank(sdrhip_ctx *ctx, int mode, int fft_size, cons
         }
       }
       h->any.reset(make_any_conv<double2, double>(ctx, mode, fft_size, kernels, n_taps, n_bands, channels, max_in));
-    } catch (...) { delete h; throw; }
-    *out = h;
+    });
   });
 }
 

@@ -23,6 +23,7 @@
 //   gather + pad -> forward transforms -> strided copy into the spectrum rows; spectrum product -> inverse transforms ->
 //   overlap-add scatter (one lane per (channel, point) walks the blocks, tail in a register).
 #include "sdrhip_internal.hpp"
+#include "entry.hpp"
 
 #include <cmath>
 #include <memory>
@@ -163,7 +164,7 @@ struct SplitBase {
   DevBuf<int> pos_of;                      // fused: frequency -> position in the digit-reversed image
   sdrhip_fft_plan *plan = nullptr;         // composed: the planned L-point transform
   DevBuf<char> scratch;                    // composed: C x max_blocks x L points
-  DevBuf<char> stage_in, stage_out;        // host entry points
+  Staging stage;                           // host entry points
   int nt = 0;                              // fused: lanes per workgroup (L / 16)
 
   size_t elem() const { return dtype == SDRHIP_T_CF64 ? 16 : 8; }
@@ -322,6 +323,8 @@ struct sdrhip_fftsource : SplitBase {
 
 extern "C" {
 
+// (FilterSink and FilterSource keep their create as it is: its messages — "out is NULL", build()'s "context is NULL" and
+// bare ranges — and its codes differ from make_handle's, and *out is left alone on failure: drifted, kept)
 int sdrhip_fftsink_create(sdrhip_ctx *ctx, int dtype, int N, int channels, size_t max_blocks, sdrhip_fftsink **out) {
   return guarded([&] {
     SDRHIP_REQUIRE(out, SDRHIP_E_INVALID, "out is NULL");
@@ -343,6 +346,7 @@ int sdrhip_fftsink_form(sdrhip_fftsink *h, const char **name) {
   });
 }
 
+// (FilterSink counts in blocks: its head is blocks_of — whole blocks, at most max_blocks — where the other nodes have max_in)
 int sdrhip_fftsink_process_dev(sdrhip_fftsink *h, const void *in_dev, size_t n_in, size_t in_stride, void *spec_dev,
                                size_t spec_stride) {
   return guarded([&] {
@@ -352,11 +356,9 @@ int sdrhip_fftsink_process_dev(sdrhip_fftsink *h, const void *in_dev, size_t n_i
     if (nb == 0) return;
     SDRHIP_REQUIRE(in_dev && spec_dev, SDRHIP_E_INVALID, "NULL buffer");
     const size_t row = nb * (size_t)h->L;
-    if (in_stride == 0) in_stride = n_in;
-    if (spec_stride == 0) spec_stride = row;
-    SDRHIP_REQUIRE(in_stride >= n_in && spec_stride >= row, SDRHIP_E_SIZE, "stride smaller than the row");
-    require_disjoint(in_dev, in_stride, n_in, h->elem(), spec_dev, spec_stride, row, h->elem(), (size_t)h->C);
-    h->launch(in_dev, nb, in_stride, spec_dev, spec_stride);
+    const Strides s = call_strides("the row", n_in, in_stride, row, spec_stride, STRIDES_TOGETHER);
+    require_disjoint(in_dev, s.in, n_in, h->elem(), spec_dev, s.out, row, h->elem(), (size_t)h->C);
+    h->launch(in_dev, nb, s.in, spec_dev, s.out);
   });
 }
 
@@ -368,29 +370,18 @@ int sdrhip_fftsink_process(sdrhip_fftsink *h, const void *in_host, size_t n_in, 
     const size_t nb = h->blocks_of(n_in);
     if (nb == 0) return;
     SDRHIP_REQUIRE(in_host && spec_host, SDRHIP_E_INVALID, "NULL buffer");
-    const size_t row = nb * (size_t)h->L, e = h->elem();
-    if (in_stride == 0) in_stride = n_in;
-    if (spec_stride == 0) spec_stride = row;
-    SDRHIP_REQUIRE(in_stride >= n_in && spec_stride >= row, SDRHIP_E_SIZE, "stride smaller than the row");
-    h->ctx->use();
-    if (!h->stage_in.p) {
-      h->stage_in.alloc((size_t)h->C * h->max_blocks * h->N * e);
-      h->stage_out.alloc((size_t)h->C * h->max_blocks * h->L * e);
-    }
-    copy_h2d_rows(h->ctx, h->stage_in.p, n_in * e, in_host, in_stride * e, n_in * e, (size_t)h->C);
-    h->launch(h->stage_in.p, nb, n_in, h->stage_out.p, row);
-    copy_d2h_rows(h->ctx, spec_host, spec_stride * e, h->stage_out.p, row * e, row * e, (size_t)h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    const size_t row = nb * (size_t)h->L, e = h->elem(), C = (size_t)h->C;
+    const Strides s = call_strides("the row", n_in, in_stride, row, spec_stride, STRIDES_TOGETHER);
+    run_staged(h->ctx, h->stage, C * h->max_blocks * h->N * e, C * h->max_blocks * h->L * e, {in_host, s.in * e, n_in * e, C},
+               {spec_host, s.out * e, row * e, C}, [&](void *in, void *out) {
+                 h->launch(in, nb, n_in, out, row);
+                 return row * e;
+               });
   });
 }
 
 int sdrhip_fftsink_destroy(sdrhip_fftsink *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 int sdrhip_fftsource_create(sdrhip_ctx *ctx, int dtype, int N, const void *kernel_spectrum, int channels, size_t max_blocks,
@@ -426,11 +417,9 @@ int sdrhip_fftsource_process_dev(sdrhip_fftsource *h, const void *spec_dev, size
     if (n_blocks == 0) return;
     SDRHIP_REQUIRE(spec_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
     const size_t row = n_blocks * (size_t)h->L, n = n_blocks * (size_t)h->N;
-    if (spec_stride == 0) spec_stride = row;
-    if (out_stride == 0) out_stride = n;
-    SDRHIP_REQUIRE(spec_stride >= row && out_stride >= n, SDRHIP_E_SIZE, "stride smaller than the row");
-    require_disjoint(spec_dev, spec_stride, row, h->elem(), out_dev, out_stride, n, h->elem(), (size_t)h->C);
-    h->launch(spec_dev, n_blocks, spec_stride, out_dev, out_stride);
+    const Strides s = call_strides("the row", row, spec_stride, n, out_stride, STRIDES_TOGETHER);
+    require_disjoint(spec_dev, s.in, row, h->elem(), out_dev, s.out, n, h->elem(), (size_t)h->C);
+    h->launch(spec_dev, n_blocks, s.in, out_dev, s.out);
   });
 }
 
@@ -442,37 +431,25 @@ int sdrhip_fftsource_process(sdrhip_fftsource *h, const void *spec_host, size_t 
     SDRHIP_REQUIRE(n_blocks <= h->max_blocks, SDRHIP_E_SIZE, "%zu blocks > max_blocks %zu", n_blocks, h->max_blocks);
     if (n_blocks == 0) return;
     SDRHIP_REQUIRE(spec_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    const size_t row = n_blocks * (size_t)h->L, n = n_blocks * (size_t)h->N, e = h->elem();
-    if (spec_stride == 0) spec_stride = row;
-    if (out_stride == 0) out_stride = n;
-    SDRHIP_REQUIRE(spec_stride >= row && out_stride >= n, SDRHIP_E_SIZE, "stride smaller than the row");
-    h->ctx->use();
-    if (!h->stage_in.p) {
-      h->stage_in.alloc((size_t)h->C * h->max_blocks * h->L * e);
-      h->stage_out.alloc((size_t)h->C * h->max_blocks * h->N * e);
-    }
-    copy_h2d_rows(h->ctx, h->stage_in.p, row * e, spec_host, spec_stride * e, row * e, (size_t)h->C);
-    h->launch(h->stage_in.p, n_blocks, row, h->stage_out.p, n);
-    copy_d2h_rows(h->ctx, out_host, out_stride * e, h->stage_out.p, n * e, n * e, (size_t)h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    const size_t row = n_blocks * (size_t)h->L, n = n_blocks * (size_t)h->N, e = h->elem(), C = (size_t)h->C;
+    const Strides s = call_strides("the row", row, spec_stride, n, out_stride, STRIDES_TOGETHER);
+    run_staged(h->ctx, h->stage, C * h->max_blocks * h->L * e, C * h->max_blocks * h->N * e, {spec_host, s.in * e, row * e, C},
+               {out_host, s.out * e, n * e, C}, [&](void *in, void *out) {
+                 h->launch(in, n_blocks, row, out, n);
+                 return n * e;
+               });
   });
 }
 
 int sdrhip_fftsource_reset(sdrhip_fftsource *h) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    h->ctx->use();
+    use_handle(h);
     h->tail.zero(h->ctx->stream);
   });
 }
 
 int sdrhip_fftsource_destroy(sdrhip_fftsource *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 }  // extern "C"

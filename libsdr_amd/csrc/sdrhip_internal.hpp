@@ -181,6 +181,7 @@ static inline void require_disjoint(const void *in, size_t in_stride, size_t in_
 // fir.hip: turn on the frequency shift fused into the cf32 FIR's staging (used by the float baseband, fbb_f32.hip)
 void fir_set_shift(sdrhip_fir *h, double fc, double fs);
 void fir_load_taps(sdrhip_fir *h, const double *alpha);
+void fir_launch(sdrhip_fir *h, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride, size_t *n_out);
 int fir_create_impl(sdrhip_ctx *ctx, int kind, const double *alpha, int order, int decim, int channels, size_t max_in, int epilogue,
                     bool allow_fft, sdrhip_fir **out);
 

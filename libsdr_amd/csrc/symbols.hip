@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "sdrhip_internal.hpp"
+#include "entry.hpp"
 
 using namespace sdrhip;
 
@@ -199,8 +200,7 @@ struct sdrhip_detector {
   size_t max_in = 0;
   DevBuf<float4> lut;
   DevBuf<short> hist[2];
-  DevBuf<short> stage_in;
-  DevBuf<uint8_t> stage_out;
+  Staging stage;
   void launch(const short *in_dev, size_t N, size_t in_stride, uint8_t *out_dev, size_t out_stride) {
     ctx->use();
     if (N == 0) return;
@@ -237,7 +237,7 @@ struct sdrhip_bits {
   DevBuf<uint4> flags;
   DevBuf<float> phase, omega;
   DevBuf<unsigned> lastbits, counts;
-  DevBuf<uint8_t> stage_in, stage_out;
+  Staging stage;
   size_t capacity(size_t n) const { return (size_t)std::ceil((double)n * (double)omax) + 1; }
   void launch(const uint8_t *in_dev, size_t N, size_t in_stride, uint8_t *out_dev, size_t out_stride, unsigned *counts_dev) {
     ctx->use();
@@ -271,32 +271,23 @@ extern "C" {
 int sdrhip_detector_create(sdrhip_ctx *ctx, int kind, const float *mark_lut, const float *space_lut, int corr_len, int invert,
                            int channels, size_t max_in, sdrhip_detector **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(kind == SDRHIP_DET_FSK || kind == SDRHIP_DET_ASK, SDRHIP_E_INVALID, "bad kind %d", kind);
-    SDRHIP_REQUIRE(channels >= 1 && channels <= 65535, SDRHIP_E_INVALID, "channels %d outside [1,65535]", channels);
-    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
-    if (kind == SDRHIP_DET_FSK) {
+    make_handle(ctx, out, true, [&](sdrhip_detector *h) {
+      SDRHIP_REQUIRE(kind == SDRHIP_DET_FSK || kind == SDRHIP_DET_ASK, SDRHIP_E_INVALID, "bad kind %d", kind);
+      require_channels(channels, 65535);
+      require_max_in(max_in);
+      h->kind = kind; h->invert = invert ? 1 : 0; h->C = channels; h->max_in = max_in;
+      if (kind != SDRHIP_DET_FSK) return;
       SDRHIP_REQUIRE(mark_lut && space_lut, SDRHIP_E_INVALID, "FSK needs the mark and the space LUT");
       SDRHIP_REQUIRE(corr_len >= 1, SDRHIP_E_INVALID, "corr_len %d < 1", corr_len);
       SDRHIP_REQUIRE(corr_len <= SY_MAX_L, SDRHIP_E_UNSUPPORTED, "corr_len %d > %d", corr_len, SY_MAX_L);
-    }
-    ctx->use();
-    sdrhip_detector *h = new sdrhip_detector;
-    try {
-      h->ctx = ctx; h->kind = kind; h->invert = invert ? 1 : 0; h->C = channels; h->max_in = max_in;
-      if (kind == SDRHIP_DET_FSK) {
-        h->L = corr_len;
-        std::vector<float4> w((size_t)corr_len);
-        for (int i = 0; i < corr_len; i++) w[i] = make_float4(mark_lut[2 * i], mark_lut[2 * i + 1], space_lut[2 * i], space_lut[2 * i + 1]);
-        h->lut.alloc((size_t)corr_len);
-        h->lut.upload(w.data(), (size_t)corr_len, ctx->stream);
-        for (int p = 0; p < 2; p++) h->hist[p].alloc((size_t)channels * (size_t)std::max(corr_len - 1, 1));
-        h->reset();
-      }
-      SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) { delete h; throw; }
-    *out = h;
+      h->L = corr_len;
+      std::vector<float4> w((size_t)corr_len);
+      for (int i = 0; i < corr_len; i++) w[i] = make_float4(mark_lut[2 * i], mark_lut[2 * i + 1], space_lut[2 * i], space_lut[2 * i + 1]);
+      h->lut.alloc((size_t)corr_len);
+      h->lut.upload(w.data(), (size_t)corr_len, ctx->stream);
+      for (int p = 0; p < 2; p++) h->hist[p].alloc((size_t)channels * (size_t)std::max(corr_len - 1, 1));
+      h->reset();
+    });
   });
 }
 
@@ -304,15 +295,10 @@ int sdrhip_detector_process_dev(sdrhip_detector *h, const int16_t *in_dev, size_
                                 size_t out_stride) {
   return guarded([&] {
     Range roctx_range("sdrhip_detector_process_dev");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n <= h->max_in, SDRHIP_E_SIZE, "n %zu > max_in %zu", n, h->max_in);
-    if (n == 0) return;
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
-    if (in_stride == 0) in_stride = n;
-    if (out_stride == 0) out_stride = n;
-    SDRHIP_REQUIRE(in_stride >= n && out_stride >= n, SDRHIP_E_SIZE, "stride smaller than n");
-    require_disjoint(in_dev, in_stride, n, 2, out_dev, out_stride, n, 1, (size_t)h->C);
-    h->launch(in_dev, n, in_stride, out_dev, out_stride);
+    if (!call_begin(h, "n", n, in_dev, out_dev)) return;
+    const Strides s = call_strides("n", n, in_stride, n, out_stride, STRIDES_TOGETHER);
+    require_disjoint(in_dev, s.in, n, 2, out_dev, s.out, n, 1, (size_t)h->C);
+    h->launch(in_dev, n, s.in, out_dev, s.out);
   });
 }
 
@@ -320,19 +306,14 @@ int sdrhip_detector_process(sdrhip_detector *h, const int16_t *in_host, size_t n
                             size_t out_stride) {
   return guarded([&] {
     Range roctx_range("sdrhip_detector_process");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n <= h->max_in, SDRHIP_E_SIZE, "n %zu > max_in %zu", n, h->max_in);
-    if (n == 0) return;
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    if (in_stride == 0) in_stride = n;
-    if (out_stride == 0) out_stride = n;
-    SDRHIP_REQUIRE(in_stride >= n && out_stride >= n, SDRHIP_E_SIZE, "stride smaller than n");
-    if (!h->stage_in.p) { h->stage_in.alloc((size_t)h->C * h->max_in); h->stage_out.alloc((size_t)h->C * h->max_in); }
-    copy_h2d_rows(h->ctx, h->stage_in.p, n * 2, in_host, in_stride * 2, n * 2, h->C);
-    h->launch(h->stage_in.p, n, n, h->stage_out.p, n);
-    copy_d2h_rows(h->ctx, out_host, out_stride, h->stage_out.p, n, n, h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    if (!call_begin(h, "n", n, in_host, out_host)) return;
+    const Strides s = call_strides("n", n, in_stride, n, out_stride, STRIDES_TOGETHER);
+    const size_t C = (size_t)h->C;
+    run_staged(h->ctx, h->stage, C * h->max_in * 2, C * h->max_in, {in_host, s.in * 2, n * 2, C}, {out_host, s.out, n, C},
+               [&](void *in, void *out) {
+                 h->launch(static_cast<const short *>(in), n, n, static_cast<uint8_t *>(out), n);
+                 return n;
+               });
   });
 }
 
@@ -345,35 +326,26 @@ int sdrhip_detector_kernel_names(sdrhip_detector *h, char *buf, size_t len) {
 
 int sdrhip_detector_reset(sdrhip_detector *h) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    use_handle(h);
     h->reset();
   });
 }
 
 int sdrhip_detector_destroy(sdrhip_detector *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 int sdrhip_bits_create(sdrhip_ctx *ctx, double sample_rate, float baud, int mode, int channels, size_t max_in, sdrhip_bits **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(mode == SDRHIP_BITS_NORMAL || mode == SDRHIP_BITS_TRANSITION, SDRHIP_E_INVALID, "bad mode %d", mode);
-    SDRHIP_REQUIRE(sample_rate > 0 && baud > 0, SDRHIP_E_INVALID, "sample rate and baud rate must be positive");
-    SDRHIP_REQUIRE(channels >= 1 && channels <= 65535, SDRHIP_E_INVALID, "channels %d outside [1,65535]", channels);
-    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
-    const double l = sample_rate / baud;
-    SDRHIP_REQUIRE(l >= 1.0, SDRHIP_E_INVALID, "fewer than one symbol per bit");
-    SDRHIP_REQUIRE(l < SY_MAX_L + 1, SDRHIP_E_UNSUPPORTED, "more than %d symbols per bit", SY_MAX_L);
-    ctx->use();
-    sdrhip_bits *h = new sdrhip_bits;
-    try {
-      h->ctx = ctx; h->mode = mode; h->C = channels; h->max_in = max_in;
+    make_handle(ctx, out, true, [&](sdrhip_bits *h) {
+      SDRHIP_REQUIRE(mode == SDRHIP_BITS_NORMAL || mode == SDRHIP_BITS_TRANSITION, SDRHIP_E_INVALID, "bad mode %d", mode);
+      SDRHIP_REQUIRE(sample_rate > 0 && baud > 0, SDRHIP_E_INVALID, "sample rate and baud rate must be positive");
+      require_channels(channels, 65535);
+      require_max_in(max_in);
+      const double l = sample_rate / baud;
+      SDRHIP_REQUIRE(l >= 1.0, SDRHIP_E_INVALID, "fewer than one symbol per bit");
+      SDRHIP_REQUIRE(l < SY_MAX_L + 1, SDRHIP_E_UNSUPPORTED, "more than %d symbols per bit", SY_MAX_L);
+      h->mode = mode; h->C = channels; h->max_in = max_in;
       h->L = int(l);                                                       // src/fsk.cc:122
       h->omega0 = (float)(baud / sample_rate);                             // :127, float = float / double
       h->omin = (float)((double)h->omega0 - 0.005 * (double)h->omega0);    // :129
@@ -382,9 +354,7 @@ int sdrhip_bits_create(sdrhip_ctx *ctx, double sample_rate, float baud, int mode
       h->flags.alloc((size_t)channels * ceil_div(max_in, (size_t)64));
       h->phase.alloc(channels); h->omega.alloc(channels); h->lastbits.alloc(channels); h->counts.alloc(channels);
       h->reset();
-      SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) { delete h; throw; }
-    *out = h;
+    });
   });
 }
 
@@ -402,21 +372,18 @@ int sdrhip_bits_out_capacity(sdrhip_bits *h, size_t n_in, size_t *cap) {
   });
 }
 
+// (BitStream's head is its own: the counts pointer is checked with the handle, and an empty call still zeroes the counts)
 int sdrhip_bits_process_dev(sdrhip_bits *h, const uint8_t *sym_dev, size_t n, size_t in_stride, uint8_t *bits_dev, size_t out_stride,
                             uint32_t *counts_dev) {
   return guarded([&] {
     Range roctx_range("sdrhip_bits_process_dev");
     SDRHIP_REQUIRE(h && counts_dev, SDRHIP_E_INVALID, "NULL argument");
-    SDRHIP_REQUIRE(n <= h->max_in, SDRHIP_E_SIZE, "n %zu > max_in %zu", n, h->max_in);
-    if (n) {
-      SDRHIP_REQUIRE(sym_dev && bits_dev, SDRHIP_E_INVALID, "NULL buffer");
-      if (in_stride == 0) in_stride = n;
-      if (out_stride == 0) out_stride = h->capacity(n);
-      SDRHIP_REQUIRE(in_stride >= n, SDRHIP_E_SIZE, "in_stride %zu < n %zu", in_stride, n);
-      SDRHIP_REQUIRE(out_stride >= h->capacity(n), SDRHIP_E_SIZE, "out_stride %zu < capacity %zu", out_stride, h->capacity(n));
-      require_disjoint(sym_dev, in_stride, n, 1, bits_dev, out_stride, h->capacity(n), 1, (size_t)h->C);
+    Strides s{in_stride, out_stride};
+    if (call_begin(h, "n", n, sym_dev, bits_dev)) {
+      s = call_strides("n", n, in_stride, h->capacity(n), out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
+      require_disjoint(sym_dev, s.in, n, 1, bits_dev, s.out, h->capacity(n), 1, (size_t)h->C);
     }
-    h->launch(sym_dev, n, in_stride, bits_dev, out_stride, counts_dev);
+    h->launch(sym_dev, n, s.in, bits_dev, s.out, counts_dev);
   });
 }
 
@@ -425,22 +392,16 @@ int sdrhip_bits_process(sdrhip_bits *h, const uint8_t *sym_host, size_t n, size_
   return guarded([&] {
     Range roctx_range("sdrhip_bits_process");
     SDRHIP_REQUIRE(h && counts_host, SDRHIP_E_INVALID, "NULL argument");
-    SDRHIP_REQUIRE(n <= h->max_in, SDRHIP_E_SIZE, "n %zu > max_in %zu", n, h->max_in);
-    if (n == 0) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
-    SDRHIP_REQUIRE(sym_host && bits_host, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    const size_t cap = h->capacity(n), cap_max = h->capacity(h->max_in);
-    if (in_stride == 0) in_stride = n;
-    if (out_stride == 0) out_stride = cap;
-    SDRHIP_REQUIRE(in_stride >= n, SDRHIP_E_SIZE, "in_stride %zu < n %zu", in_stride, n);
-    SDRHIP_REQUIRE(out_stride >= cap, SDRHIP_E_SIZE, "out_stride %zu < capacity %zu", out_stride, cap);
-    if (!h->stage_in.p) { h->stage_in.alloc((size_t)h->C * h->max_in); h->stage_out.alloc((size_t)h->C * cap_max); }
-    copy_h2d_rows(h->ctx, h->stage_in.p, n, sym_host, in_stride, n, h->C);
-    h->stage_out.zero(h->ctx->stream);   // the bytes of a row behind counts[c] reach the caller as zeros
-    h->launch(h->stage_in.p, n, n, h->stage_out.p, cap, h->counts.p);
-    copy_d2h_rows(h->ctx, bits_host, out_stride, h->stage_out.p, cap, cap, h->C);
-    SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, (size_t)h->C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    if (!call_begin(h, "n", n, sym_host, bits_host)) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
+    const size_t cap = h->capacity(n), C = (size_t)h->C;
+    const Strides s = call_strides("n", n, in_stride, cap, out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
+    run_staged(h->ctx, h->stage, C * h->max_in, C * h->capacity(h->max_in), {sym_host, s.in, n, C}, {bits_host, s.out, cap, C},
+               [&](void *in, void *out) {
+                 h->stage.out.zero(h->ctx->stream);   // the bytes of a row behind counts[c] reach the caller as zeros
+                 h->launch(static_cast<const uint8_t *>(in), n, n, static_cast<uint8_t *>(out), cap, h->counts.p);
+                 SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
+                 return cap;
+               });
   });
 }
 
@@ -453,18 +414,13 @@ int sdrhip_bits_kernel_names(sdrhip_bits *h, char *buf, size_t len) {
 
 int sdrhip_bits_reset(sdrhip_bits *h) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    use_handle(h);
     h->reset();
   });
 }
 
 int sdrhip_bits_destroy(sdrhip_bits *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 }  // extern "C"

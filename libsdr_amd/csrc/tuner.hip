@@ -27,6 +27,7 @@
 //                           taps whose high byte plane fits int8, calls of at least HOT_MIN_IN samples.
 #include "iqbb_common.hpp"
 #include "iqbb_host.hpp"
+#include "entry.hpp"
 
 #include <algorithm>
 #include <string>
@@ -310,7 +311,7 @@ struct sdrhip_tuner_i16 {
   DevBuf<uint32_t> hist[2];            // ONE ring of HH samples
   DevBuf<int2> acc[2];
   DevBuf<short> fm[2];
-  DevBuf<uint32_t> stage_in, stage_out;
+  Staging stage;
   std::string last_names;
 
   Geometry geometry(size_t N) const { return call_geometry(n0, N, D, false); }
@@ -447,23 +448,19 @@ extern "C" {
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                             const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
   return guarded([&] {
-    SDRHIP_REQUIRE(ctx && taps && lut && lut_inc && negative && out, SDRHIP_E_INVALID, "NULL argument");
-    *out = nullptr;
-    SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
-    SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
-    SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
-    SDRHIP_REQUIRE(channels >= 1 && channels <= TUNER_MAX_CHANNELS, SDRHIP_E_INVALID, "channels %d outside [1,%d]", channels, TUNER_MAX_CHANNELS);
-    SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
-    SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
-    for (size_t i = 0; i < (size_t)channels * order * 2; i++)
-      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
-                     i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
-    for (int i = 0; i < 256; i++)
-      SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
-    ctx->use();
-    sdrhip_tuner_i16 *h = new sdrhip_tuner_i16;
-    try {
-      h->ctx = ctx; h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
+    make_handle(ctx, out, taps && lut && lut_inc && negative, [&](sdrhip_tuner_i16 *h) {
+      SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
+      SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
+      SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
+      require_channels(channels, TUNER_MAX_CHANNELS);
+      require_max_in(max_in);
+      SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
+      for (size_t i = 0; i < (size_t)channels * order * 2; i++)
+        SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
+                       i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
+      for (int i = 0; i < 256; i++)
+        SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
+      h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
       h->ovl = epilogue == SDRHIP_EPI_FM ? 1 : 0;
       h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;
       h->S = (int)ceil_div((size_t)order, (size_t)16);
@@ -498,9 +495,7 @@ int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, con
       }
       h->max_out = max_in / decim + 2;
       h->last_names = h->kernel_name(h->hot_call(max_in));
-      SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
-    } catch (...) { delete h; throw; }
-    *out = h;
+    });
   });
 }
 
@@ -528,41 +523,31 @@ int sdrhip_tuner_i16_out_count(sdrhip_tuner_i16 *h, size_t n_in, size_t *n_out) 
   });
 }
 
+// (one wideband input row: there is no in_stride, and the overlap check takes the input as one row against C output rows)
 int sdrhip_tuner_i16_process_dev(sdrhip_tuner_i16 *h, const void *in_dev, size_t n_in, void *out_dev, size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_tuner_i16_process_dev");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) { if (n_out) *n_out = 0; return; }
-    SDRHIP_REQUIRE(in_dev && out_dev, SDRHIP_E_INVALID, "NULL buffer");
+    if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) { if (n_out) *n_out = 0; return; }
     const size_t no = (size_t)h->geometry(n_in).n_out;
-    if (out_stride == 0) out_stride = no;
-    require_disjoint(in_dev, n_in, n_in, h->in_elem_bytes(), out_dev, out_stride, no, h->out_elem_bytes(), 1, (size_t)h->C);
-    h->launch(in_dev, n_in, out_dev, out_stride, n_out);
+    const Strides s = call_strides("n_in", n_in, 0, no, out_stride, 0);   // (out_stride: launch checks it, after the overlap)
+    require_disjoint(in_dev, n_in, n_in, h->in_elem_bytes(), out_dev, s.out, no, h->out_elem_bytes(), 1, (size_t)h->C);
+    h->launch(in_dev, n_in, out_dev, s.out, n_out);
   });
 }
 
 int sdrhip_tuner_i16_process(sdrhip_tuner_i16 *h, const void *in_host, size_t n_in, void *out_host, size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_tuner_i16_process");
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(n_in <= h->max_in, SDRHIP_E_SIZE, "n_in %zu > max_in %zu", n_in, h->max_in);
-    if (n_in == 0) { if (n_out) *n_out = 0; return; }
-    SDRHIP_REQUIRE(in_host && out_host, SDRHIP_E_INVALID, "NULL buffer");
-    h->ctx->use();
-    const size_t no = (size_t)h->geometry(n_in).n_out;
-    if (out_stride == 0) out_stride = no;
-    SDRHIP_REQUIRE(out_stride >= no, SDRHIP_E_SIZE, "out_stride %zu < outputs %zu", out_stride, no);
-    if (!h->stage_in.p) {
-      h->stage_in.alloc(h->max_in);
-      h->stage_out.alloc((size_t)h->C * h->max_out);
-    }
-    const size_t ib = h->in_elem_bytes(), eb = h->out_elem_bytes();
-    copy_h2d_rows(h->ctx, h->stage_in.p, n_in * ib, in_host, n_in * ib, n_in * ib, 1);
+    if (!call_begin(h, "n_in", n_in, in_host, out_host)) { if (n_out) *n_out = 0; return; }
+    const Strides s = call_strides("n_in", n_in, 0, (size_t)h->geometry(n_in).n_out, out_stride, STRIDE_OUT);
+    // (the output rows are staged at max_out 4-byte slots whatever the element: a demodulated row uses half of its pitch)
+    const size_t ib = h->in_elem_bytes(), eb = h->out_elem_bytes(), C = (size_t)h->C;
     size_t produced = 0;
-    h->launch(h->stage_in.p, n_in, h->stage_out.p, h->max_out * 4 / eb, &produced);
-    copy_d2h_rows(h->ctx, out_host, out_stride * eb, h->stage_out.p, h->max_out * 4, produced * eb, h->C);
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    run_staged(h->ctx, h->stage, h->max_in * 4, C * h->max_out * 4, {in_host, n_in * ib, n_in * ib, 1},
+               {out_host, s.out * eb, h->max_out * 4, C}, [&](void *in, void *out) {
+                 h->launch(in, n_in, out, h->max_out * 4 / eb, &produced);
+                 return produced * eb;
+               });
     if (n_out) *n_out = produced;
   });
 }
@@ -611,8 +596,7 @@ int sdrhip_tuner_i16_set_input_format(sdrhip_tuner_i16 *h, int format) {
 
 int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    h->ctx->use();
+    use_handle(h);
     hipStream_t st = h->ctx->stream;
     // bit 0: the FIR ring survives, read ROTATED afterwards (reconfigured_ring_row, iqbb_host.hpp); bit 1: so do the fused
     // FMDemod's last angles (sdrhip_iqbb_i16_reset)
@@ -638,12 +622,7 @@ int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history) {
 }
 
 int sdrhip_tuner_i16_destroy(sdrhip_tuner_i16 *h) {
-  return guarded([&] {
-    if (!h) return;
-    h->ctx->use();
-    (void)hipStreamSynchronize(h->ctx->stream);
-    delete h;
-  });
+  return guarded([&] { destroy_handle(h); });
 }
 
 }  // extern "C"
