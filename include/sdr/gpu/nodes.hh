@@ -1558,11 +1558,17 @@ template <class Scalar> class TunerBank;
  * order, sub-sampling and the fused demodulator are the bank's. Per buffer: one H2D copy, one launch for all channels
  * (sdrhip_tuner_i16_*), one D2H copy of all rows into a pinned staging buffer, then one send per channel, in channel
  * order, as views of it. addChannel() after config() rebuilds the device plan: every channel restarts as a freshly
- * configured node (FIR history, decimator and LUT phases at zero). */
+ * configured node (FIR history, decimator and LUT phases at zero).
+ * With epilogue = TunerBank::PerChannel every channel has a demodulator of its own (SDRHIP_EPI_FM | _AM | _USB: the modes of
+ * the reference's receiver, examples/sdr_rec.cc:44-110, on one antenna), still in one launch; setMode() replaces the
+ * demodulator node behind ONE channel's baseband, which goes on as it is (sdrhip_tunermodes_i16_set_mode). Every output's Config
+ * is int16_t at the decimated rate, whatever the modes are. */
 template <>
 class TunerBank<int16_t> : public Sink<cs16> {
 public:
   typedef ChannelBank<int16_t>::Out Out;
+  /** The constructor's `epilogue` of a bank with a demodulator per channel. */
+  enum { PerChannel = -1 };
 
   TunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
     : _order(std::max(size_t(1), order)), _D(std::max(size_t(1), sub_sample)), _epilogue(epilogue), _device(device), _ctx(0), _plan(0),
@@ -1572,14 +1578,32 @@ public:
     for (size_t c = 0; c < _outs.size(); c++) delete _outs[c];
   }
 
-  /** A new channel; returns its index. Before or after config(). */
-  size_t addChannel(double Fc, double Ff, double width) {
+  /** A new channel; returns its index. Before or after config(). Its demodulator is the bank's; FMDemod in a bank with one per
+   * channel. */
+  size_t addChannel(double Fc, double Ff, double width) { return addChannel(Fc, Ff, width, perChannel() ? int(SDRHIP_EPI_FM) : _epilogue); }
+  /** ... with the demodulator `mode`: SDRHIP_EPI_FM | _AM | _USB in a bank with one per channel; in any other bank a mode that
+   * is not the bank's throws ConfigError. */
+  size_t addChannel(double Fc, double Ff, double width, int mode) {
+    _checkMode(mode);
     _tunes.push_back(Tune(Fc, Ff, width));
+    _modes.push_back(mode);
     _outs.push_back(new Out());
     if (_plan) _rebuild();
     return _tunes.size() - 1;
   }
   size_t channels() const { return _tunes.size(); }
+  bool perChannel() const { return _epilogue == PerChannel; }
+  /** The demodulator of channel c (the bank's, where it has one for all). */
+  int mode(size_t c) const { return _modes[c]; }
+  /** A new demodulator node behind channel c's baseband. Before config() the mode is only recorded; afterwards the running plan
+   * changes between two buffers (sdrhip_tunermodes_i16_set_mode): the baseband continues, a new FMDemod starts from angle 0, no other
+   * channel is touched. In a bank with one demodulator for all, a mode that is not the bank's throws ConfigError. */
+  void setMode(size_t c, int mode) {
+    _checkMode(mode);
+    if (!perChannel()) return;
+    if (_plan) detail::configCheck(sdrhip_tunermodes_i16_set_mode(_plan, int(c), mode), "TunerBank");
+    _modes[c] = mode;
+  }
   Source *source(size_t c) { return _outs[c]; }
 
   double centerFrequency(size_t c) const { return _tunes[c].Fc; }
@@ -1626,7 +1650,7 @@ public:
       return;
     for (size_t ch = 0; ch < C; ch++) {
       if (_epilogue == SDRHIP_EPI_NONE) _outs[ch]->emit(_stageOut.sub(ch * _outStride, n), false);
-      else if (!(_epilogue == SDRHIP_EPI_FM && n == 0))
+      else if (!(_modes[ch] == SDRHIP_EPI_FM && n == 0))   // (FMDemod does not send on an empty buffer)
         _outs[ch]->emit(Buffer<int16_t>(_stageOut).sub(ch * _outStride * 2, n), false);
     }
   }
@@ -1639,6 +1663,14 @@ protected:
     double shift;
     Tune(double fc, double ff, double w) : Fc(int32_t(fc)), Ff(int32_t(ff)), width(int32_t(w)), shift(fc) {}
   };
+
+  void _checkMode(int mode) const {
+    if (perChannel() ? (mode == SDRHIP_EPI_FM || mode == SDRHIP_EPI_AM || mode == SDRHIP_EPI_USB) : mode == _epilogue) return;
+    ConfigError err;
+    if (perChannel()) err << "TunerBank: mode " << mode << " is none of SDRHIP_EPI_FM, SDRHIP_EPI_AM, SDRHIP_EPI_USB";
+    else err << "TunerBank: mode " << mode << " in a bank whose channels all have the demodulator " << _epilogue;
+    throw err;
+  }
 
   void _retap(size_t c) {
     if (!_plan) return;
@@ -1671,8 +1703,12 @@ protected:
     }
     design::freqShiftLutI16(lut.data());
     _outStride = (_bs + _D - 1) / _D + 1;
-    detail::configCheck(sdrhip_tuner_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), int(_D), int(C), _bs,
-                                                _epilogue, &_plan), "TunerBank");
+    if (perChannel())
+      detail::configCheck(sdrhip_tunermodes_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), _modes.data(),
+                                                       int(_D), int(C), _bs, &_plan), "TunerBank");
+    else
+      detail::configCheck(sdrhip_tuner_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), int(_D), int(C), _bs,
+                                                  _epilogue, &_plan), "TunerBank");
     detail::configCheck(sdrhip_malloc(_ctx, _bs * sizeof(cs16), &_din), "TunerBank");
     detail::configCheck(sdrhip_malloc(_ctx, C * _outStride * sizeof(cs16), &_dout), "TunerBank");
     _stageOut = Buffer<cs16>(C * _outStride);
@@ -1690,6 +1726,7 @@ protected:
   size_t _bs, _outStride;
   int32_t _Fs;
   std::vector<Tune> _tunes;
+  std::vector<int> _modes;   // per channel: its demodulator (the bank's epilogue, where it has one for all)
   std::vector<Out *> _outs;
   Buffer<cs16> _stageOut;
 };

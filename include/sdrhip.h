@@ -277,6 +277,30 @@ int sdrhip_iqbb_i16_destroy(sdrhip_iqbb_i16 *h);
 typedef struct sdrhip_tuner_i16 sdrhip_tuner_i16;
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                             const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out);
+/* A bank with a demodulator PER CHANNEL — FM, AM and USB channels of one antenna in one launch (the reference's receiver picks
+ * its demodulator per receiver: examples/sdr_rec.cc:44-110).
+ * modes: channels entries, each SDRHIP_EPI_FM | SDRHIP_EPI_AM | SDRHIP_EPI_USB (int16 rows). SDRHIP_EPI_NONE is
+ * SDRHIP_E_INVALID: its rows have another element size. Everything else as sdrhip_tuner_i16_create. ctx = NULL on a machine
+ * without a usable device: SDRHIP_E_NODEVICE.
+ * Such a bank plans every call as an FM bank does (plan_info reports that geometry: one recomputed group per time tile),
+ * whatever its modes are; kernel_names reports the same two forms (in a profile its kernels are tuner_i16_modes_mfma_kernel /
+ * tuner_i16_modes_valu_kernel). set_taps, set_shift, set_input_format, reset (| 2 keeps the FM channels' angles), out_count,
+ * process and process_dev keep their meaning. The handle is a sdrhip_tuner_i16 and every sdrhip_tuner_i16_* call takes it; the
+ * three calls that exist for such a bank only carry the prefix sdrhip_tunermodes_i16_, so that the sdrhip_tuner_i16_* set stays
+ * the one every bank answers. */
+int sdrhip_tunermodes_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                                 const int *negative, const int *modes, int decim, int channels, size_t max_in,
+                                 sdrhip_tuner_i16 **out);
+/* Replaces the demodulator node behind channel `channel`'s baseband, between any two calls. The baseband goes on as it is:
+ * FIR ring, open window and its partial sum, LUT phase and sample index continue, and no other channel is touched. The new
+ * node is a freshly configured one — an FMDemod starts from last angle 0 (src/demod.hh:195-212, _last_value = 0 at :210),
+ * also when the channel was FM already — and the next call's out[0] of an FM channel follows the in-place convention
+ * (src/demod.hh:233-249: index 0 is never written, it keeps the real part of the baseband's first output). AMDemod and
+ * USBDemod have no state (src/demod.hh:65-76,144-161).
+ * A bad channel or mode: SDRHIP_E_INVALID, and nothing changes. A bank made by sdrhip_tuner_i16_create has one demodulator
+ * for all channels: set_mode and get_modes return SDRHIP_E_UNSUPPORTED on it. */
+int sdrhip_tunermodes_i16_set_mode(sdrhip_tuner_i16 *h, int channel, int mode);
+int sdrhip_tunermodes_i16_get_modes(sdrhip_tuner_i16 *h, int *modes, int n);   /* n >= channels */
 int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len);
 /* What a call of n_in samples (1 ... max_in) would launch from the bank's current state, which it does not advance (tests):
  * info[0] = 1 the matrix kernel, 0 the plain one, info[1] = K steps S of 32 plane bytes, info[2] = decimation groups a time

@@ -1,7 +1,7 @@
 // tuner.hip — the tuner bank: C independent IQBaseBand<int16_t> channels (+ fused FM / AM / USB demodulator) over ONE
 // shared input row (sdrhip.h, "tuner bank"). Shared by all channels: the input, ONE FIR history, the absolute sample
 // index, order, decimation, epilogue, the LUT. Per channel: taps, LUT increment, sign and phase origin, the open window's
-// partial sum, the FM angle. Reference arithmetic as iqbb_common.hpp lists it. A channel of the bank is presented to the
+// partial sum, the FM angle — and, in a bank made by sdrhip_tunermodes_i16_create, the demodulator. Reference arithmetic as iqbb_common.hpp lists it. A channel of the bank is presented to the
 // one-tune plan's device helpers as a one-channel IqbbArgs view (channel_view) with channel index 0, and the host rules
 // come from the header the one-tune plan (iqbb_i16.hip) takes them from:
 //   iqbb_common.hpp   load_x, rotate / rotate_i16, finalize_group, epilogue_and_roll (and through them box_div; am_i16,
@@ -9,7 +9,8 @@
 //   iqbb_host.hpp     call_geometry, tap_in_range, tap_fits_planes, pack_valu_taps, split_planes, planes_const, hot_row,
 //                     reconfigured_ring_row
 //
-// Two kernels, both bit-exact:
+// Two kernels, both bit-exact (each a __device__ body behind its entry points: one instance per demodulator and input kind,
+// and tuner_i16_modes_valu_kernel / tuner_i16_modes_mfma_kernel per input kind for a bank with a demodulator per channel):
 //   tuner_i16_valu_kernel   v_dot2 FIR at 8 consecutive samples per lane, one workgroup per (time tile, channel): every
 //                           valid plan (order 1 ... 513, decimation 1 ... 512, any call length). Still a COPY of
 //                           iqbb_i16_kernel<false, false>'s body (iqbb_common.hpp), to be kept equal line for line.
@@ -40,6 +41,9 @@ constexpr int TR_STRIDE = 33;    // row stride (int2) of a wave's [channel][colu
 constexpr int HOT_COLS = 512;     // time columns a hot tile aims at (whole decimation groups)
 constexpr int HOT_MIN_D = 4;      // smaller decimations: (channel, group) sums of a tile would not fit LDS
 constexpr int HOT_MIN_IN = 512;   // shorter calls hold no tile worth the staging: the plain form
+// the EPI template argument of the instances that read the demodulator per channel (TunerArgs::mode); the SDRHIP_EPI_*
+// values are 0 ... 3 and the one-tune plan's HOT_EPI_PARTIAL is 4
+constexpr int EPI_PER_CHANNEL = -1;
 
 struct TunerArgs {
   IqbbArgs a;               // the call as ONE channel sees it; in / hist: the shared row and ring, taps / acc / fm / out: channel 0's
@@ -47,16 +51,22 @@ struct TunerArgs {
   const int *negative;      // ... sign of the shift
   const uint32_t *phase0;   // ... absolute sample index (low 32 bits) at which the LUT phase counter last restarted
   const int2 *cst;          // ... 128 * sum(a) of the interleaved tap vectors (re, im): the byte-plane constant term
+  const int *mode;          // ... SDRHIP_EPI_FM | AM | USB (EPI_PER_CHANNEL instances only; NULL otherwise)
   int C, S, ctiles, ctw;    // channels, K steps of 32 plane bytes, channel tiles, channel tiles walked by one workgroup
   int PLB;                  // bytes of one staged sample plane
 };
 
 // Channel c of the bank as the one-tune helpers see a plan's only channel (they are called with channel index 0).
 // rolls: this workgroup's channel is the one that rolls the shared history in the call's last tile.
+// EPI_PER_CHANNEL: the demodulator is the channel's own — c is uniform over the workgroup wherever a view is made (the plain
+// form runs one channel per workgroup, the matrix form finalises channel after channel), so the branches on b.epilogue in
+// finalize_group and epilogue_and_roll stay uniform. Such a bank has the FM geometry (ovl = 1, the angle cache behind
+// ybuf + CGr): an AM / USB channel leaves the overlap slot's ybuf entry unused (epilogue_and_roll starts at a.ovl), and
+// neither writes the angle cache nor fm_new — the host keeps its fm entries at 0 (sdrhip_tunermodes_i16_set_mode).
 template <int EPI, bool CU8>
 __device__ __forceinline__ IqbbArgs channel_view(const TunerArgs &t, int c, bool rolls) {
   IqbbArgs b = t.a;
-  b.in_cu8 = CU8; b.in_real = 0; b.i8 = 0; b.epilogue = EPI;
+  b.in_cu8 = CU8; b.in_real = 0; b.i8 = 0; b.epilogue = EPI == EPI_PER_CHANNEL ? t.mode[c] : EPI;
   b.taps = t.a.taps + (long)c * t.a.OP;
   b.inc = t.inc[c]; b.negative = t.negative[c];
   b.n0_lo = t.a.n0_lo - t.phase0[c];
@@ -69,7 +79,7 @@ __device__ __forceinline__ IqbbArgs channel_view(const TunerArgs &t, int c, bool
 
 // ---- plain form: iqbb_i16_kernel's general decimation path over the shared row, one channel per blockIdx.y -----------
 template <int EPI, bool CU8>
-__global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) {
+__device__ __forceinline__ void tuner_valu_body(const TunerArgs &t) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const int c = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
   const IqbbArgs a = channel_view<EPI, CU8>(t, c, c == 0);
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) 
 // by the 32x32 C/D map lane (n, h) then holds, in accumulator registers 2j / 2j + 1, (re, im) of channel 8 h + j of the
 // tile at time column n.
 template <int EPI, bool CU8>
-__global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) {
+__device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const IqbbArgs &g = t.a;
   const int tile = blockIdx.x, tid = threadIdx.x, l = tid & 63, w = tid >> 6, n = l & 31, h = l >> 5;
@@ -287,11 +297,28 @@ __global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs 
   }
 }
 
+// ---- entry points: one instance per (demodulator, input kind) of a single-epilogue bank, and per input kind of a bank with a
+// mode per channel. The latter have names of their own: the set of tuner_i16_valu_kernel / tuner_i16_mfma_kernel instances is
+// the single-epilogue one.
+template <int EPI, bool CU8>
+__global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI, CU8>(t); }
+template <int EPI, bool CU8>
+__global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI, CU8>(t); }
+template <bool CU8>
+__global__ __launch_bounds__(TPB) void tuner_i16_modes_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI_PER_CHANNEL, CU8>(t); }
+template <bool CU8>
+__global__ __launch_bounds__(TPB, 2) void tuner_i16_modes_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI_PER_CHANNEL, CU8>(t); }
+
 }  // namespace
 
 struct sdrhip_tuner_i16 {
   sdrhip_ctx *ctx = nullptr;
   int order = 0, OP = 0, S = 0, HH = 0, D = 1, C = 1, epi = 0, in_cu8 = 0, ovl = 0;
+  // a mode per channel (sdrhip_tunermodes_i16_create): epi = SDRHIP_EPI_FM stands for the bank's geometry, element size and
+  // double-buffered angles; the kernels take each channel's demodulator from `mode`
+  bool per_channel = false;
+  std::vector<int> mode_host;
+  DevBuf<int> mode;
   int ctiles = 0;
   size_t max_in = 0, max_out = 0;
   uint64_t n0 = 0;
@@ -398,6 +425,11 @@ struct sdrhip_tuner_i16 {
   }
   template <bool CU8>
   void launch_epi(bool hot, const TunerArgs &t, dim3 grid, size_t lds) {
+    if (per_channel) {
+      if (hot) hipLaunchKernelGGL((tuner_i16_modes_mfma_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+      else hipLaunchKernelGGL((tuner_i16_modes_valu_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+      return;
+    }
     switch (epi) {
       case SDRHIP_EPI_FM: launch_kernels<SDRHIP_EPI_FM, CU8>(hot, t, grid, lds); break;
       case SDRHIP_EPI_AM: launch_kernels<SDRHIP_EPI_AM, CU8>(hot, t, grid, lds); break;
@@ -418,6 +450,7 @@ struct sdrhip_tuner_i16 {
     a.in = reinterpret_cast<const uint32_t *>(in_dev); a.in_stride = 0; a.in_cu8 = in_cu8;
     a.hist_old = hist[par].p; a.hist_new = hist[par ^ 1].p; a.HH = HH;
     a.acc_old = acc[par].p; a.acc_new = acc[par ^ 1].p;
+    // (every FM channel writes its fm_new entry in such a call; the other channels of a per-channel bank have 0 in both)
     const bool fm_flip = epi == SDRHIP_EPI_FM && g.n_out >= 2;
     a.fm_old = fm[par_fm].p; a.fm_new = fm[par_fm ^ 1].p;
     a.taps = taps.p; a.lut = lut.p; a.tapfrag = tapfrag.p;
@@ -427,7 +460,7 @@ struct sdrhip_tuner_i16 {
     a.CG = p.CG; a.OG = p.OG; a.CGr = (a.CG + 3) & ~3;
     a.out = out_dev; a.out_stride = (long)out_stride; a.epilogue = epi;
     a.tiles = p.tiles; a.tpw = 1; a.lpg = 1;
-    t.inc = inc.p; t.negative = negative.p; t.phase0 = phase0.p; t.cst = cst.p;
+    t.inc = inc.p; t.negative = negative.p; t.phase0 = phase0.p; t.cst = cst.p; t.mode = mode.p;
     t.C = C; t.S = S; t.ctiles = ctiles; t.ctw = p.ctw; t.PLB = p.PLB;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.grid_y);
     const size_t lds = p.lds;
@@ -443,59 +476,116 @@ struct sdrhip_tuner_i16 {
   }
 };
 
+static inline bool valid_mode(int m) { return m == SDRHIP_EPI_FM || m == SDRHIP_EPI_AM || m == SDRHIP_EPI_USB; }
+
+// sdrhip_tuner_i16_create (modes = NULL) and sdrhip_tunermodes_i16_create (epilogue = SDRHIP_EPI_FM: the geometry)
+static void tuner_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc, const int *negative,
+                         const int *modes, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
+  make_handle(ctx, out, taps && lut && lut_inc && negative, [&](sdrhip_tuner_i16 *h) {
+    SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
+    SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
+    SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
+    require_channels(channels, TUNER_MAX_CHANNELS);
+    require_max_in(max_in);
+    SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
+    for (int c = 0; modes && c < channels; c++)
+      SDRHIP_REQUIRE(valid_mode(modes[c]), SDRHIP_E_INVALID, "channel %d: mode %d is none of SDRHIP_EPI_FM, _AM, _USB", c, modes[c]);
+    for (size_t i = 0; i < (size_t)channels * order * 2; i++)
+      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
+                     i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
+    for (int i = 0; i < 256; i++)
+      SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
+    h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
+    h->ovl = epilogue == SDRHIP_EPI_FM ? 1 : 0;
+    h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;
+    h->S = (int)ceil_div((size_t)order, (size_t)16);
+    h->HH = 16 * h->S;   // >= OP, and the whole ring (reset with keep_history)
+    h->ctiles = (int)ceil_div((size_t)channels, (size_t)CT);
+    { const char *force = getenv("SDRHIP_TUNER_PATH"); h->force_valu = force && !strcmp(force, "valu"); }
+    if (const char *f = getenv("SDRHIP_TUNER_CTW")) { if (f[0] && !f[1] && strchr("1248", f[0])) h->force_ctw = f[0] - '0'; }
+    h->taps_host.assign(taps, taps + (size_t)channels * order * 2);
+    h->inc_host.assign(lut_inc, lut_inc + channels);
+    h->neg_host.resize(channels);
+    for (int c = 0; c < channels; c++) h->neg_host[c] = negative[c] ? 1 : 0;
+    h->fits.resize(channels);
+    for (int c = 0; c < channels; c++) { const int32_t *k = taps + (size_t)c * order * 2; h->fits[c] = std::all_of(k, k + 2 * order, tap_fits_planes); h->misfits += h->fits[c] ? 0 : 1; }
+    hipStream_t st = ctx->stream;
+    h->taps.alloc((size_t)channels * h->OP);
+    {
+      std::vector<uint2> all((size_t)channels * h->OP);
+      for (int c = 0; c < channels; c++) pack_valu_taps(taps + (size_t)c * order * 2, order, h->OP, false, all.data() + (size_t)c * h->OP);
+      h->taps.upload(all.data(), all.size(), st);
+    }
+    h->tapfrag.alloc((size_t)h->ctiles * h->S * 2 * 64);
+    h->cst.alloc((size_t)h->ctiles * CT);
+    for (int ct = 0; ct < h->ctiles; ct++) h->upload_tile(ct);
+    h->lut.alloc(128); h->lut.upload(reinterpret_cast<const int2 *>(lut), 128, st);
+    h->inc.alloc(channels); h->inc.upload(h->inc_host.data(), channels, st);
+    h->negative.alloc(channels); h->negative.upload(h->neg_host.data(), channels, st);
+    h->phase0.alloc(channels); h->phase0.zero(st);
+    if (modes) {
+      h->per_channel = true;
+      h->mode_host.assign(modes, modes + channels);
+      h->mode.alloc(channels); h->mode.upload(h->mode_host.data(), channels, st);
+    }
+    for (int p = 0; p < 2; p++) {
+      h->hist[p].alloc(h->HH); h->hist[p].zero(st);
+      h->acc[p].alloc(channels); h->acc[p].zero(st);
+      h->fm[p].alloc(channels); h->fm[p].zero(st);
+    }
+    h->max_out = max_in / decim + 2;
+    h->last_names = h->kernel_name(h->hot_call(max_in));
+  });
+}
+
 extern "C" {
 
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                             const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
+  return guarded([&] { tuner_create(ctx, taps, order, lut, lut_inc, negative, nullptr, decim, channels, max_in, epilogue, out); });
+}
+
+int sdrhip_tunermodes_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                                 const int *negative, const int *modes, int decim, int channels, size_t max_in,
+                                 sdrhip_tuner_i16 **out) {
   return guarded([&] {
-    make_handle(ctx, out, taps && lut && lut_inc && negative, [&](sdrhip_tuner_i16 *h) {
-      SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
-      SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
-      SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
-      require_channels(channels, TUNER_MAX_CHANNELS);
-      require_max_in(max_in);
-      SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
-      for (size_t i = 0; i < (size_t)channels * order * 2; i++)
-        SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
-                       i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
-      for (int i = 0; i < 256; i++)
-        SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
-      h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
-      h->ovl = epilogue == SDRHIP_EPI_FM ? 1 : 0;
-      h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;
-      h->S = (int)ceil_div((size_t)order, (size_t)16);
-      h->HH = 16 * h->S;   // >= OP, and the whole ring (reset with keep_history)
-      h->ctiles = (int)ceil_div((size_t)channels, (size_t)CT);
-      { const char *force = getenv("SDRHIP_TUNER_PATH"); h->force_valu = force && !strcmp(force, "valu"); }
-      if (const char *f = getenv("SDRHIP_TUNER_CTW")) { if (f[0] && !f[1] && strchr("1248", f[0])) h->force_ctw = f[0] - '0'; }
-      h->taps_host.assign(taps, taps + (size_t)channels * order * 2);
-      h->inc_host.assign(lut_inc, lut_inc + channels);
-      h->neg_host.resize(channels);
-      for (int c = 0; c < channels; c++) h->neg_host[c] = negative[c] ? 1 : 0;
-      h->fits.resize(channels);
-      for (int c = 0; c < channels; c++) { const int32_t *k = taps + (size_t)c * order * 2; h->fits[c] = std::all_of(k, k + 2 * order, tap_fits_planes); h->misfits += h->fits[c] ? 0 : 1; }
-      hipStream_t st = ctx->stream;
-      h->taps.alloc((size_t)channels * h->OP);
-      {
-        std::vector<uint2> all((size_t)channels * h->OP);
-        for (int c = 0; c < channels; c++) pack_valu_taps(taps + (size_t)c * order * 2, order, h->OP, false, all.data() + (size_t)c * h->OP);
-        h->taps.upload(all.data(), all.size(), st);
+    if (out) *out = nullptr;
+    if (!ctx) {   // where no device exists there is no context to pass: say that, not "NULL argument"
+      int n = 0;
+      if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        SDRHIP_FAIL(SDRHIP_E_NODEVICE, "no HIP device available, hence no context; libsdrhip has no CPU fallback");
       }
-      h->tapfrag.alloc((size_t)h->ctiles * h->S * 2 * 64);
-      h->cst.alloc((size_t)h->ctiles * CT);
-      for (int ct = 0; ct < h->ctiles; ct++) h->upload_tile(ct);
-      h->lut.alloc(128); h->lut.upload(reinterpret_cast<const int2 *>(lut), 128, st);
-      h->inc.alloc(channels); h->inc.upload(h->inc_host.data(), channels, st);
-      h->negative.alloc(channels); h->negative.upload(h->neg_host.data(), channels, st);
-      h->phase0.alloc(channels); h->phase0.zero(st);
-      for (int p = 0; p < 2; p++) {
-        h->hist[p].alloc(h->HH); h->hist[p].zero(st);
-        h->acc[p].alloc(channels); h->acc[p].zero(st);
-        h->fm[p].alloc(channels); h->fm[p].zero(st);
-      }
-      h->max_out = max_in / decim + 2;
-      h->last_names = h->kernel_name(h->hot_call(max_in));
-    });
+    }
+    SDRHIP_REQUIRE(!ctx || modes, SDRHIP_E_INVALID, "modes is NULL");   // (ctx = NULL on a machine with a device: make_handle's message)
+    tuner_create(ctx, taps, order, lut, lut_inc, negative, modes, decim, channels, max_in, SDRHIP_EPI_FM, out);
+  });
+}
+
+// The demodulator node behind channel `channel`'s baseband is replaced (reference: a new node connected in the old one's
+// place; FMDemod::config, src/demod.hh:195-212, starts from _last_value = 0 at :210). Both copies of the channel's angle
+// become 0: a new FMDemod's state, and the defined state of a channel that is not FM (launch flips the copies for all).
+int sdrhip_tunermodes_i16_set_mode(sdrhip_tuner_i16 *h, int channel, int mode) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(h->per_channel, SDRHIP_E_UNSUPPORTED, "the bank has one demodulator for all channels (sdrhip_tunermodes_i16_create makes one per channel)");
+    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    SDRHIP_REQUIRE(valid_mode(mode), SDRHIP_E_INVALID, "mode %d is none of SDRHIP_EPI_FM, _AM, _USB", mode);
+    h->ctx->use();
+    hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued
+    h->mode_host[channel] = mode;
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->mode.p + channel, &h->mode_host[channel], sizeof(int), hipMemcpyHostToDevice, st));
+    for (int p = 0; p < 2; p++) SDRHIP_CHECK_HIP(hipMemsetAsync(h->fm[p].p + channel, 0, sizeof(short), st));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int sdrhip_tunermodes_i16_get_modes(sdrhip_tuner_i16 *h, int *modes, int n) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && modes, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(h->per_channel, SDRHIP_E_UNSUPPORTED, "the bank has one demodulator for all channels (sdrhip_tunermodes_i16_create makes one per channel)");
+    SDRHIP_REQUIRE(n >= h->C, SDRHIP_E_INVALID, "modes holds %d entries, the bank has %d channels", n, h->C);
+    std::copy(h->mode_host.begin(), h->mode_host.end(), modes);
   });
 }
 

@@ -337,10 +337,11 @@ class IQBaseBandI16(_Node):
 
 class TunerBankI16(_Node):
     """Tuner bank — C IQBaseBand<int16_t> channels (+ fused FM/AM/USB) over ONE shared input row, each with its own taps
-    and frequency shift. Mirrors sdr::gpu::TunerBank<int16_t>."""
+    and frequency shift. modes (a sequence of EPI_FM | EPI_AM | EPI_USB, one per channel) makes a bank with a demodulator per
+    channel (sdrhip_tunermodes_i16_create) instead of the one `epilogue`. Mirrors sdr::gpu::TunerBank<int16_t>."""
     _destroy = "sdrhip_tuner_i16_destroy"
 
-    def __init__(self, ctx, taps, lut, lut_inc, negative, decim, max_in=65536, epilogue=EPI_NONE):
+    def __init__(self, ctx, taps, lut, lut_inc, negative, decim, max_in=65536, epilogue=EPI_NONE, modes=None):
         super().__init__()
         taps = np.ascontiguousarray(taps, np.int32)
         assert taps.ndim == 3 and taps.shape[2] == 2, taps.shape
@@ -351,6 +352,15 @@ class TunerBankI16(_Node):
         assert inc.size == channels and neg.size == channels
         self.ctx, self.channels, self.order, self.decim, self.epilogue, self.max_in = ctx, channels, order, decim, epilogue, max_in
         self._cu8 = False
+        if modes is not None:
+            m = np.ascontiguousarray(modes, np.intc).reshape(-1)
+            assert m.size == channels
+            self.epilogue = EPI_FM   # (int16 rows; the bank's geometry is FM's)
+            check(abi.lib().sdrhip_tunermodes_i16_create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
+                                                         lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         neg.ctypes.data_as(C.POINTER(C.c_int)), m.ctypes.data_as(C.POINTER(C.c_int)),
+                                                         decim, channels, max_in, C.byref(self._h)))
+            return
         check(abi.lib().sdrhip_tuner_i16_create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
                                                 lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                 neg.ctypes.data_as(C.POINTER(C.c_int)), decim, channels, max_in, epilogue,
@@ -406,6 +416,17 @@ class TunerBankI16(_Node):
     def set_shift(self, c, lut_inc, negative):
         """setCenterFrequency of channel c: increment, sign, that channel's LUT phase restarts."""
         check(abi.lib().sdrhip_tuner_i16_set_shift(self._h, int(c), lut_inc, int(bool(negative))))
+
+    def set_mode(self, c, mode):
+        """A new demodulator node (EPI_FM | EPI_AM | EPI_USB) behind channel c's baseband, which goes on as it is; banks made
+        with modes= only."""
+        check(abi.lib().sdrhip_tunermodes_i16_set_mode(self._h, int(c), int(mode)))
+
+    def modes(self):
+        """The channels' demodulators; banks made with modes= only."""
+        m = (C.c_int * self.channels)()
+        check(abi.lib().sdrhip_tunermodes_i16_get_modes(self._h, m, self.channels))
+        return list(m)
 
     def set_input_format(self, fmt):
         check(abi.lib().sdrhip_tuner_i16_set_input_format(self._h, fmt))

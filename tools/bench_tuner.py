@@ -8,7 +8,14 @@ warm-up; median and range):
   c  the bank, matrix form          d  the bank, plain form (SDRHIP_TUNER_PATH=valu)
 Before anything is timed one step of c is compared with a's rows bit for bit. Writes profiles/tuner_bench.json, then exits
 non-zero when c was not verified or is not faster than a at some C. c against b is reported (c_over_b), not gated.
-usage: python tools/bench_tuner.py [reps] [rounds] [out.json]"""
+--modes: the bank with a demodulator per channel (TunerBankI16(modes=...)) instead, at 1024 channels of both plans and in both
+kernel forms, interleaved in the same way:
+  fm       the bank with ONE demodulator, FM (c / d above)
+  all_fm   the per-channel bank, every channel FM: the same geometry and the same work, the mode read per channel
+  mixed    the per-channel bank, FM / AM / USB in turn
+Before anything is timed, all_fm is compared with fm on every row and every row of mixed with the row of the single-demodulator
+bank of its mode, bit for bit. Writes profiles/tuner_modes_bench.json; exits non-zero when a comparison failed. No speed gate.
+usage: python tools/bench_tuner.py [--modes] [reps] [rounds] [out.json]"""
 import json
 import os
 import sys
@@ -20,9 +27,11 @@ sys.path.insert(0, ROOT)
 
 import libsdr_amd as sa
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 50
-ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "tuner_bench.json")
+MODES = "--modes" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--modes"]
+REPS = int(ARGS[0]) if len(ARGS) > 0 and ARGS[0].isdigit() else 50
+ROUNDS = int(ARGS[1]) if len(ARGS) > 1 else 5
+OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "tuner_modes_bench.json" if MODES else "tuner_bench.json")
 N = 65536
 CHANNELS = (16, 128, 1024)
 PLANS = {"fm127d8": dict(order=127, D=8, Fs=2.4e6, cu8=False), "sdr_fm": dict(order=21, D=125, Fs=1e6, cu8=True)}
@@ -68,13 +77,13 @@ def measure(ctx, fns):
     return out
 
 
-def bank(ctx, tn, lut, D, cu8, valu):
+def bank(ctx, tn, lut, D, cu8, valu, epilogue=sa.EPI_FM, modes=None):
     old = os.environ.pop("SDRHIP_TUNER_PATH", None)
     if valu:
         os.environ["SDRHIP_TUNER_PATH"] = "valu"
     try:
         b = sa.TunerBankI16(ctx, np.stack([np.asarray(t[0], np.int32).reshape(-1, 2) for t in tn]), lut, [t[1] for t in tn],
-                            [t[2] for t in tn], D, max_in=N, epilogue=sa.EPI_FM)
+                            [t[2] for t in tn], D, max_in=N, epilogue=epilogue, modes=modes)
     finally:
         os.environ.pop("SDRHIP_TUNER_PATH", None)
         if old is not None:
@@ -144,7 +153,73 @@ def run_case(ctx, rng, name, p, C):
             ctx.free(q)
 
 
+def run_modes_case(ctx, rng, p, C):
+    order, D, Fs, cu8 = p["order"], p["D"], p["Fs"], p["cu8"]
+    lut = sa.design_freqshift_lut_i16()
+    tn = tunes(C, order, Fs)
+    x = signal(rng, cu8)
+    M = N // D + 2
+    mixed_modes = [(sa.EPI_FM, sa.EPI_AM, sa.EPI_USB)[c % 3] for c in range(C)]
+    din, dout = ctx.malloc(N * (2 if cu8 else 4)), ctx.malloc(C * M * 2)
+    made = []
+
+    def rows(b):
+        """One step of a fresh bank: its rows."""
+        made.append(b)
+        y = np.full((C, M), 0x5A5A, np.int16)
+        ctx.h2d(dout, y)
+        b.process_dev(din, N, dout, M)
+        ctx.synchronize()
+        ctx.d2h(y, dout)
+        return y
+
+    try:
+        ctx.h2d(din, x)
+        out = {}
+        for form, valu in (("matrix", False), ("plain", True)):
+            cand = {"fm": bank(ctx, tn, lut, D, cu8, valu), "all_fm": bank(ctx, tn, lut, D, cu8, valu, modes=[sa.EPI_FM] * C),
+                    "mixed": bank(ctx, tn, lut, D, cu8, valu, modes=mixed_modes)}
+            y = {k: rows(b) for k, b in cand.items()}
+            single = {sa.EPI_FM: y["fm"], sa.EPI_AM: rows(bank(ctx, tn, lut, D, cu8, valu, epilogue=sa.EPI_AM)),
+                      sa.EPI_USB: rows(bank(ctx, tn, lut, D, cu8, valu, epilogue=sa.EPI_USB))}
+            verified = bool(np.array_equal(y["all_fm"], y["fm"])) and all(np.array_equal(y["mixed"][c], single[m][c]) for c, m in enumerate(mixed_modes))
+            r = measure(ctx, {k: (lambda b=b: b.process_dev(din, N, dout, M)) for k, b in cand.items()})
+            r.update({"verified": verified, "kernels": {k: b.kernel_names for k, b in cand.items()},
+                      "all_fm_over_fm": round(r["all_fm"]["ms"] / r["fm"]["ms"], 4), "mixed_over_fm": round(r["mixed"]["ms"] / r["fm"]["ms"], 4),
+                      # the run-to-run range of the single-demodulator bank, as a fraction of its median
+                      "fm_range": round((r["fm"]["max_ms"] - r["fm"]["min_ms"]) / r["fm"]["ms"], 4)})
+            out[form] = r
+        for b in made:
+            b.close()
+        return out
+    finally:
+        ctx.free(din); ctx.free(dout)
+
+
+def main_modes():
+    ctx = sa.Context(0)
+    rng = np.random.default_rng(7)
+    C = 1024
+    result = {"device": ctx.device_name(), "samples_per_step": N, "channels": C, "reps": REPS, "rounds": ROUNDS,
+              "mixed": "FM / AM / USB in turn (channel c: mode c % 3)", "plans": {}}
+    for name, p in PLANS.items():
+        r = run_modes_case(ctx, rng, p, C)
+        result["plans"][name] = dict(p, forms=r)
+        print(json.dumps({name: r}), flush=True)
+    ctx.close()
+    ok = all(f["verified"] for p in result["plans"].values() for f in p["forms"].values())
+    result["verified_everywhere"] = ok
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("verified:", ok)
+    sys.exit(0 if ok else 1)
+
+
 def main():
+    if MODES:
+        return main_modes()
     ctx = sa.Context(0)
     rng = np.random.default_rng(7)
     result = {"device": ctx.device_name(), "samples_per_step": N, "reps": REPS, "rounds": ROUNDS, "plans": {}}
