@@ -20,6 +20,12 @@
 // when allow_overwrite; views (out.head(n)) are sent, never copies; process() never throws (device
 // errors are logged at LOG_ERROR and the buffer is dropped).
 //
+// What the nodes share is written once, in namespace detail at the head of the file: the type check of config()
+// (checkType), the owners of device plans, device memory and pinned registrations (Handle, DeviceMem, Pinned: a node
+// that has one cannot be copied), the designed tap / LUT vectors, the send rule of a fused demodulator
+// (sendDemodulated), the device hand-off between two gpu nodes (HandoffScope, handoffFor) and, further down, the one
+// state machine of the int16 baseband plans (Bb16: IQBaseBand<int16_t|uint8_t|int8_t> and BaseBand<int16_t>).
+//
 // The header compiles against this repository's core (include/sdr/node.hh) or, when the
 // reference's own node.hh was included first, against the reference core unchanged.
 #ifndef SDR_GPU_NODES_HH
@@ -35,6 +41,8 @@
 #include <cstring>
 #include <list>
 #include <map>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "../../sdrhip.h"
@@ -79,192 +87,327 @@ inline bool processOk(int rc, const char *what) {
   Logger::get().log(msg);
   return false;
 }
+/** The type check of every config(), after the node's own guard for an incomplete Config: ConfigError unless the upstream
+ * type is `want`. The message names `shown` as the expected type (BitStream's differs from the one it compares with). */
+inline void checkType(const Config &cfg, Config::Type want, Config::Type shown, const char *what, const char *noun = "type") {
+  if (want == cfg.type()) return;
+  ConfigError err;
+  err << "Can not configure " << what << ": Invalid " << noun << " " << cfg.type() << ", expected " << shown;
+  throw err;
+}
+template <class T> inline void checkType(const Config &cfg, const char *what, const char *noun = "type") {
+  checkType(cfg, Config::typeId<T>(), Config::typeId<T>(), what, noun);
+}
+
+/** The library's names for a complex sample type. */
 template <class T> struct TypeTag;
 template <> struct TypeTag<cs16> { enum { dtype = SDRHIP_T_CS16, fir = SDRHIP_FIR_CS16_EXACT }; typedef int16_t Real; };
 template <> struct TypeTag<cf32> { enum { dtype = SDRHIP_T_CF32, fir = SDRHIP_FIR_CF32 }; typedef float Real; };
 template <> struct TypeTag< std::complex<int8_t> > { enum { dtype = SDRHIP_T_CS8 }; typedef int8_t Real; };
-template <class S> struct RealTag;
-template <> struct RealTag<int16_t> { enum { dtype = SDRHIP_T_CS16 }; };
-template <> struct RealTag<float> { enum { dtype = SDRHIP_T_CF32 }; };
-}  // namespace detail
+template <> struct TypeTag< std::complex<double> > { enum { dtype = SDRHIP_T_CF64 }; typedef double Real; };
 
-// =================================================================================================
-// IQBaseBand<int16_t>
-// =================================================================================================
-namespace detail {
-/** IQBaseBand on the int16 kernels; SIn = int16_t (complex<int16_t> in) or uint8_t (complex<uint8_t> in, with
- * AutoCast< complex<int16_t> > fused into the load: the cast -> baseband pair of examples/sdr_fm.cc:49-50). */
-/** Sample types per input scalar: int16_t and uint8_t (AutoCast fused) produce complex<int16_t>; int8_t is
- * IQBaseBand<int8_t>, which produces complex<int8_t> (reference src/baseband.hh:22-31, src/sdr.hh:225-240). */
-template <class S> struct BbIo { typedef cs16 COut; enum { int8 = 0, cu8 = 0 }; };
-template <> struct BbIo<uint8_t> { typedef cs16 COut; enum { int8 = 0, cu8 = 1 }; };
-template <> struct BbIo<int8_t> { typedef std::complex<int8_t> COut; enum { int8 = 1, cu8 = 0 }; };
-
-template <class SIn>
-class IQBB16 : public Sink< std::complex<SIn> >, public Source {
+/** Owner of one handle of the C library: destroyed with its owner or when replaced, moved but never copied. */
+template <class T, int (*Destroy)(T *)>
+class Handle {
 public:
-  typedef std::complex<SIn> CIn;
-  typedef typename BbIo<SIn>::COut COut;
-  enum { kInt8 = BbIo<SIn>::int8, kCu8 = BbIo<SIn>::cu8 };
-  IQBB16(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : _Fc(Fc), _Ff(Fc), _shift(Fc), _Fs(0), _width(width), _order(std::max(size_t(1), order)), _sub_sample(sub_sample),
-      _oFs(oFs), _sourceBs(0), _epilogue(SDRHIP_EPI_NONE), _device(device), _plan(0) {}
-  IQBB16(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : _Fc(Fc), _Ff(Ff), _shift(Fc), _Fs(0), _width(width), _order(std::max(size_t(1), order)), _sub_sample(sub_sample),
-      _oFs(oFs), _sourceBs(0), _epilogue(SDRHIP_EPI_NONE), _device(device), _plan(0) {}
-  virtual ~IQBB16() {
-    if (_plan) sdrhip_iqbb_i16_destroy(_plan);
-    _buffer.unref();
-  }
+  Handle() : _h(0) {}
+  Handle(Handle &&o) noexcept : _h(o._h) { o._h = 0; }
+  Handle &operator=(Handle &&o) noexcept { if (this != &o) { reset(); _h = o._h; o._h = 0; } return *this; }
+  ~Handle() { reset(); }
+  T *get() const { return _h; }
+  operator T *() const { return _h; }   // (null while there is no plan: `if (_plan)`)
+  void reset() { if (_h) { Destroy(_h); _h = 0; } }
+  /** Where a create call stores its result; what was held before is destroyed first. */
+  T **out() { reset(); return &_h; }
+private:
+  T *_h;
+};
+/** Owner of device memory; freed on the context it was allocated on. */
+class DeviceMem {
+public:
+  DeviceMem() : _ctx(0), _p(0) {}
+  DeviceMem(DeviceMem &&o) noexcept : _ctx(o._ctx), _p(o._p) { o._p = 0; }
+  DeviceMem &operator=(DeviceMem &&o) noexcept { if (this != &o) { reset(); _ctx = o._ctx; _p = o._p; o._p = 0; } return *this; }
+  ~DeviceMem() { reset(); }
+  void alloc(sdrhip_ctx *c, size_t bytes, const char *what) { reset(); configCheck(sdrhip_malloc(c, bytes, &_p), what); _ctx = c; }
+  void reset() { if (_p) { sdrhip_free(_ctx, _p); _p = 0; } }
+  void *get() const { return _p; }
+  template <class T> T *as() const { return static_cast<T *>(_p); }
+private:
+  sdrhip_ctx *_ctx;
+  void *_p;
+};
+/** The registration of a host buffer as pinned memory (the buffer itself stays its node's). */
+class Pinned {
+public:
+  Pinned() : _p(0) {}
+  Pinned(const Pinned &) = delete;
+  Pinned &operator=(const Pinned &) = delete;
+  ~Pinned() { reset(); }
+  void reset(void *p, size_t bytes, const char *what) { reset(); configCheck(sdrhip_host_register(p, bytes), what); _p = p; }
+  void reset() { if (_p) { sdrhip_host_unregister(_p); _p = 0; } }
+private:
+  void *_p;
+};
 
+/** The designers' results as vectors. */
+inline std::vector<int32_t> iqbbTaps(double Ff, double width, double Fs, size_t order) {
+  std::vector<int32_t> taps(2 * order);
+  design::iqbbTaps(Ff, width, Fs, order, taps.data());
+  return taps;
+}
+inline std::vector<int32_t> freqShiftLut(bool int8 = false) {
+  std::vector<int32_t> lut(2 * design::kLutSize);
+  if (int8) design::freqShiftLutI8(lut.data()); else design::freqShiftLutI16(lut.data());
+  return lut;
+}
+inline std::vector<double> firLowPass(size_t order, double Fu, double Fs) {
+  std::vector<double> alpha(order);
+  design::firLowPass(order, Fu, Fs, alpha.data());
+  return alpha;
+}
+/** sinc_flt_kernel + FilterSource::_updateFilter (src/filternode.hh:18-28,186-203): the 2 x block-point spectrum of a band's kernel. */
+template <class Scalar>
+inline std::vector<Scalar> fftFilterSpectrum(size_t block, double fmin, double fmax, double Fs) {
+  std::vector<Scalar> h(2 * block), K(4 * block);
+  design::fftFilterKernel(int(block), fmin, fmax, Fs, h.data());
+  design::fftFilterSpectrum(int(block), h.data(), K.data());
+  return K;
+}
+
+/** The output of a baseband of complex COut with the demodulator `epilogue` fused into its launch: its sample type, and the
+ * output elements per complex sample (the demodulators' int16 fits sizeof(COut) / 2 times into one). */
+template <class COut> inline Config::Type fusedType(int epilogue) {
+  return epilogue == SDRHIP_EPI_NONE ? Config::typeId<COut>() : Config::typeId<int16_t>();
+}
+template <class COut> inline size_t fusedPer(int epilogue) { return epilogue == SDRHIP_EPI_NONE ? 1 : sizeof(COut) / 2; }
+/** The Config of every output of a bank: rows of `stride` at the decimated rate (int32 by size_t, as src/baseband.hh:192-193). */
+inline Config bankOutConfig(int epilogue, int32_t Fs, size_t D, size_t stride) {
+  return Config(fusedType<cs16>(epilogue), double(size_t(Fs) / D), stride, 1);
+}
+/** What such a baseband sends: the n samples at element `row` of `out`, as the nodes fused into it would have —
+ * no demodulator: the complex view; FMDemod: int16, nothing for an empty buffer (src/demod.hh:231), overwrite not allowed;
+ * AMDemod: int16, overwrite allowed (:80); USBDemod: int16, overwrite not allowed. `own`: the view is a buffer of its own
+ * (a node's output); false for a row of a bank's shared staging buffer, which no receiver may write into. */
+template <class COut>
+inline void sendDemodulated(Source &from, int mode, const Buffer<COut> &out, size_t row, size_t n, bool own) {
+  if (mode == SDRHIP_EPI_NONE) from.send(out.sub(row, n), own);
+  else if (mode != SDRHIP_EPI_FM || n) from.send(Buffer<int16_t>(out).sub(row * (sizeof(COut) / 2), n), own && mode == SDRHIP_EPI_AM);
+}
+
+/** The direct hand-off of a result between two gpu nodes (detector -> BitStream: symbols; FilterSink -> FilterSource:
+ * spectra): just before a direct send the producer records {host buffer data -> device copy, device}; the host buffer
+ * stays unfilled, and a consumer that receives that very buffer reads the device copy. The keys are the addresses of live
+ * host buffers, so one table serves all. Direct delivery is synchronous: the record lives as long as the send. */
+struct Handoff { const void *dev; int device; };
+inline std::map<const void *, Handoff> &handoffs() {
+  static std::map<const void *, Handoff> table;
+  return table;
+}
+class HandoffScope {
+public:
+  HandoffScope(const void *host, const void *dev, int device) : _host(host) { const Handoff rec = {dev, device}; handoffs()[host] = rec; }
+  ~HandoffScope() { handoffs().erase(_host); }
+  HandoffScope(const HandoffScope &) = delete;
+private:
+  const void *_host;
+};
+/** The device copy behind a received host buffer, or 0 when there is none on `device`. */
+inline const void *handoffFor(const void *host, int device) {
+  const std::map<const void *, Handoff>::const_iterator it = handoffs().find(host);
+  return (it != handoffs().end() && it->second.device == device) ? it->second.dev : 0;
+}
+/** true: there are sinks, and every one is connected direct and is a SinkT on `device` (the condition of a hand-off). */
+template <class SinkT>
+inline bool allSinksDirectOn(const std::map<SinkBase *, bool> &sinks, int device) {
+  if (sinks.empty()) return false;
+  for (std::map<SinkBase *, bool>::const_iterator it = sinks.begin(); it != sinks.end(); ++it) {
+    const SinkT *s = dynamic_cast<const SinkT *>(it->first);
+    if (!it->second || !s || s->device() != device) return false;
+  }
+  return true;
+}
+
+// =================================================================================================
+// the int16 baseband plans: IQBaseBand<int16_t|uint8_t|int8_t> and BaseBand<int16_t>
+// =================================================================================================
+/** One sdrhip_iqbb_i16 plan behind a node and what happens to it: made, retuned, reconfigured, run. The node says what
+ * differs (_rate, _taps, _create) and keeps its parameters the way its reference node does. */
+template <class In, class COut>
+class Bb16 : public Sink<In>, public Source {
+public:
+  virtual ~Bb16() { _buffer.unref(); }
   /** Extension: fuse FMDemod / AMDemod / USBDemod<int16_t> (run in place on the node's output, as
    * `baseband.connect(&demod, true)` does in examples/sdr_fm.cc:51) into the same kernel launch.
    * The node then is a source of int16_t. Call before connecting / configuring. */
-  void setDemod(int epilogue) { _epilogue = epilogue; if (_Fs) _reconfigure(); }
-
-  inline size_t order() const { return _order; }
-  /** As the reference (src/baseband.hh:69-79): a new kernel and a NEW ring; the decimator window, the sample counter, the
-   * LUT phase and the Config go on untouched. (The reference's new ring is uninitialised memory until `order` samples
-   * have passed; here it is zeros.) */
-  void setOrder(size_t o) {
-    _order = std::max(size_t(1), o);
-    if (_plan) _newPlan(SDRHIP_KEEP_FM | SDRHIP_KEEP_COUNTERS);
-  }
-  inline double centerFrequency() const { return _Fc; }
-  /** As the reference (src/baseband.hh:84-86 -> src/freqshift.hh:52-54,78-87): new LUT increment and sign, the LUT
-   * phase restarts; filter history, decimator state and the kernel go on unchanged. */
-  void setCenterFrequency(double Fc) {
-    _Fc = int32_t(Fc); _shift = _Fc;
-    if (_plan) configCheck(sdrhip_iqbb_i16_set_shift(_plan, design::freqShiftIncrement(_shift, double(_Fs)), 0 > _shift), "IQBaseBand");
-  }
-  inline double filterFrequency() const { return _Ff; }
-  /** As the reference (:92-104): only the filter kernel is recomputed, all streaming state goes on. */
-  void setFilterFrequency(double Ff) { _Ff = int32_t(Ff); _retap(); }
-  inline double filterWidth() const { return _width; }
-  void setFilterWidth(double width) { _width = int32_t(width); _retap(); }
-  size_t subSample() const { return _sub_sample; }
-  void setSubsample(size_t sub_sample) { _sub_sample = std::max(size_t(1), sub_sample); if (_Fs) _reconfigure(); }
-  void setOutputSampleRate(double Fs) { _oFs = Fs; if (_Fs) _reconfigure(); }
-
-  virtual void config(const Config &src_cfg) {
-    if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<CIn>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure IQBaseBand: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<CIn>();
-      throw err;
-    }
-    _Fs = int32_t(src_cfg.sampleRate());
-    _sourceBs = src_cfg.bufferSize();
-    _reconfigure();
-  }
-
-  virtual void process(const Buffer<CIn> &buffer, bool allow_overwrite) {
-    if (!_plan) return;
-    if (allow_overwrite && sizeof(CIn) == sizeof(COut)) _process(buffer, Buffer<COut>(buffer));   // in place needs equal sample sizes
-    else if (_buffer.isUnused()) _process(buffer, _buffer);
-    // else: output buffer still in use downstream -> the input is dropped (src/baseband.hh:141-150)
-  }
+  void setDemod(int epilogue) { _epilogue = epilogue; if (_rate()) _reconfigure(); }
 
 protected:
+  Bb16(const char *name, double shift, size_t order, size_t sub_sample, int device)
+    : _name(name), _gpuName(std::string("gpu::") + name), _shift(shift), _order(std::max(size_t(1), order)), _sub_sample(sub_sample),
+      _sourceBs(0), _epilogue(SDRHIP_EPI_NONE), _device(device) {}
+
+  virtual double _rate() const = 0;                    // the input sample rate as the node holds it; 0 before config()
+  virtual std::vector<int32_t> _taps() const = 0;      // the filter kernel for the node's present parameters
+  virtual int _create(const int32_t *taps, uint32_t inc, size_t D, sdrhip_iqbb_i16 **out) const = 0;
+  virtual void _reconfigure() = 0;
+
+  uint32_t _inc() const { return design::freqShiftIncrement(_shift, _rate()); }
+  void _setShift() {
+    if (_plan) configCheck(sdrhip_iqbb_i16_set_shift(_plan, _inc(), 0 > _shift), _name);
+  }
+  /** false: the new kernel does not fit the plan's formulation (tap bytes); a new plan has to take the stream over. */
+  bool _setTaps() {
+    const int rc = sdrhip_iqbb_i16_set_taps(_plan, _taps().data());
+    if (rc == SDRHIP_E_UNSUPPORTED) return false;
+    configCheck(rc, _name);
+    return true;
+  }
   /** _update_filter_kernel() on a configured node: swap the kernel, keep every bit of streaming state. */
   void _retap() {
-    if (!_plan) return;
-    std::vector<int32_t> taps(2 * _order);
-    design::iqbbTaps(_Ff, _width, _Fs, _order, taps.data());
-    const int rc = sdrhip_iqbb_i16_set_taps(_plan, taps.data());
-    // the new kernel does not fit the plan's formulation (tap bytes): a new plan that takes the whole stream state over
-    if (rc == SDRHIP_E_UNSUPPORTED) _newPlan(SDRHIP_KEEP_RING | SDRHIP_KEEP_FM | SDRHIP_KEEP_COUNTERS);
-    else configCheck(rc, "IQBaseBand");
+    if (_plan && !_setTaps()) _newPlan(SDRHIP_KEEP_RING | SDRHIP_KEEP_FM | SDRHIP_KEEP_COUNTERS);
   }
 
   /** A device plan for the node's present parameters; `carry` (SDRHIP_KEEP_*) names the streaming state it takes over
    * from the plan it replaces (sdrhip_iqbb_i16_adopt_state), so that a new plan is not an event of its own. */
   void _newPlan(int carry) {
     const size_t D = std::max(size_t(1), _sub_sample);
-    std::vector<int32_t> taps(2 * _order), lut(2 * design::kLutSize);
-    design::iqbbTaps(_Ff, _width, _Fs, _order, taps.data());
-    if (kInt8) design::freqShiftLutI8(lut.data()); else design::freqShiftLutI16(lut.data());
-    const uint32_t inc = design::freqShiftIncrement(_shift, double(_Fs));
-    sdrhip_iqbb_i16 *neu = 0;
-    if (kInt8) configCheck(sdrhip_iqbb_i8_create(Device::get(_device), taps.data(), int(_order), lut.data(), inc, 0 > _shift,
-                                                 int(D), 1, _sourceBs, _epilogue, &neu), "IQBaseBand");
-    else configCheck(sdrhip_iqbb_i16_create(Device::get(_device), taps.data(), int(_order), lut.data(), inc, 0 > _shift,
-                                            int(D), 1, _sourceBs, _epilogue, &neu), "IQBaseBand");
-    int rc = kCu8 ? sdrhip_iqbb_i16_set_input_format(neu, SDRHIP_IN_CU8) : SDRHIP_OK;
-    if (rc == SDRHIP_OK && _plan) {
+    Handle<sdrhip_iqbb_i16, sdrhip_iqbb_i16_destroy> neu;
+    configCheck(_create(_taps().data(), _inc(), D, neu.out()), _name);
+    if (_plan) {
       if (_planOrder != _order) carry &= ~SDRHIP_KEEP_RING;   // (a new order is a new ring, src/baseband.hh:75-76)
       if (_planEpi != SDRHIP_EPI_FM || _epilogue != SDRHIP_EPI_FM) carry &= ~SDRHIP_KEEP_FM;
-      rc = sdrhip_iqbb_i16_adopt_state(neu, _plan, carry);
+      configCheck(sdrhip_iqbb_i16_adopt_state(neu, _plan, carry), _name);
     }
-    if (rc != SDRHIP_OK) { sdrhip_iqbb_i16_destroy(neu); configCheck(rc, "IQBaseBand"); }
-    if (_plan) sdrhip_iqbb_i16_destroy(_plan);
-    _plan = neu;
+    _plan = std::move(neu);
     _planOrder = _order; _planD = D; _planBs = _sourceBs; _planEpi = _epilogue;
   }
 
-  /** IQBaseBand::_reconfigure (src/baseband.hh:156-194): kernel and LUT increment recomputed, counters and phases reset,
-   * the FIR ring's CONTENTS kept where they lie (read rotated afterwards) — on the plan in place
-   * (sdrhip_iqbb_i16_reset(keep_history = 1)) or, when the geometry changed (decimation, buffer size, demodulator),
-   * carried into the new device plan. */
-  void _reconfigure() {
-    const size_t D = design::iqbbDecimation(_Fs, _sub_sample, _oFs);
-    _sub_sample = D;
+  /** IQBaseBand::_reconfigure (src/baseband.hh:156-194) and BaseBand::config (:357-395): kernel and LUT increment
+   * recomputed, counters and phases reset, the FIR ring's CONTENTS kept where they lie (read rotated afterwards) — on the
+   * plan in place (sdrhip_iqbb_i16_reset(keep_history = 1)) or, when the geometry changed (order, decimation, buffer size,
+   * demodulator), carried into the new device plan. Returns the Config to propagate, over a new output buffer. */
+  Config _configure(size_t D, double oRate) {
     size_t buffer_size = _sourceBs / D;
     if (_sourceBs % D) buffer_size += 1;
-    const double oRate = double(size_t(_Fs) / D);   // the reference divides int32 by size_t (src/baseband.hh:192-193)
-    const Config out_cfg(_epilogue == SDRHIP_EPI_NONE ? Config::typeId<COut>() : Config::typeId<int16_t>(), oRate, buffer_size, 1);
+    const Config out_cfg(fusedType<COut>(_epilogue), oRate, buffer_size, 1);
     // (a fused demodulator is reconfigured — FM's last angle zeroed — only if the Config we propagate changes,
     // src/node.cc:98-105, src/demod.hh:210)
     const bool same_cfg = (out_cfg == this->_config);
-    bool reuse = _plan && _planOrder == _order && _planD == D && _planBs == _sourceBs && _planEpi == _epilogue;
-    if (reuse) {
-      std::vector<int32_t> taps(2 * _order);
-      design::iqbbTaps(_Ff, _width, _Fs, _order, taps.data());
-      const int rc = sdrhip_iqbb_i16_set_taps(_plan, taps.data());
-      if (rc == SDRHIP_E_UNSUPPORTED) reuse = false;
-      else {
-        configCheck(rc, "IQBaseBand");
-        configCheck(sdrhip_iqbb_i16_set_shift(_plan, design::freqShiftIncrement(_shift, double(_Fs)), 0 > _shift), "IQBaseBand");
-        configCheck(sdrhip_iqbb_i16_reset(_plan, same_cfg ? 3 : 1), "IQBaseBand");
-      }
-    }
-    if (!reuse) _newPlan(SDRHIP_KEEP_RING | (same_cfg ? SDRHIP_KEEP_FM : 0));
+    if (_plan && _planOrder == _order && _planD == D && _planBs == _sourceBs && _planEpi == _epilogue && _setTaps()) {
+      _setShift();
+      configCheck(sdrhip_iqbb_i16_reset(_plan, same_cfg ? 3 : 1), _name);
+    } else _newPlan(SDRHIP_KEEP_RING | (same_cfg ? SDRHIP_KEEP_FM : 0));
     _buffer.unref();
     _buffer = Buffer<COut>(buffer_size);
+    return out_cfg;
+  }
+
+  void _run(const Buffer<In> &in, const Buffer<COut> &out) {
+    size_t n = 0;
+    // (out_stride in output elements)
+    if (!processOk(sdrhip_iqbb_i16_process(_plan, reinterpret_cast<const int16_t *>(in.data()), in.size(), 0, out.data(),
+                                           out.size() * fusedPer<COut>(_epilogue), &n), _gpuName.c_str()))
+      return;
+    sendDemodulated(*this, _epilogue, out, 0, n, true);
+  }
+
+  const char *_name;
+  std::string _gpuName;
+  double _shift;
+  size_t _order, _sub_sample, _sourceBs;
+  int _epilogue, _device;
+  Handle<sdrhip_iqbb_i16, sdrhip_iqbb_i16_destroy> _plan;
+  size_t _planOrder = 0, _planD = 0, _planBs = 0;   // geometry the device plan was made for
+  int _planEpi = 0;
+  Buffer<COut> _buffer;
+};
+
+/** Sample types per input scalar: int16_t and uint8_t (AutoCast fused) produce complex<int16_t>; int8_t is
+ * IQBaseBand<int8_t>, which produces complex<int8_t> (reference src/baseband.hh:22-31, src/sdr.hh:225-240). */
+template <class S> struct BbIo { typedef cs16 COut; enum { int8 = 0, cu8 = 0 }; };
+template <> struct BbIo<uint8_t> { typedef cs16 COut; enum { int8 = 0, cu8 = 1 }; };
+template <> struct BbIo<int8_t> { typedef std::complex<int8_t> COut; enum { int8 = 1, cu8 = 0 }; };
+
+/** IQBaseBand on the int16 kernels; SIn = int16_t (complex<int16_t> in) or uint8_t (complex<uint8_t> in, with
+ * AutoCast< complex<int16_t> > fused into the load: the cast -> baseband pair of examples/sdr_fm.cc:49-50). */
+template <class SIn>
+class IQBB16 : public Bb16< std::complex<SIn>, typename BbIo<SIn>::COut > {
+public:
+  typedef std::complex<SIn> CIn;
+  typedef typename BbIo<SIn>::COut COut;
+  enum { kInt8 = BbIo<SIn>::int8, kCu8 = BbIo<SIn>::cu8 };
+  IQBB16(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
+    : IQBB16(Fc, Fc, width, order, sub_sample, oFs, device) {}
+  IQBB16(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
+    : Bb16<CIn, COut>("IQBaseBand", Fc, order, sub_sample, device), _Fc(Fc), _Ff(Ff), _Fs(0), _width(width), _oFs(oFs) {}
+
+  inline size_t order() const { return this->_order; }
+  /** As the reference (src/baseband.hh:69-79): a new kernel and a NEW ring; the decimator window, the sample counter, the
+   * LUT phase and the Config go on untouched. (The reference's new ring is uninitialised memory until `order` samples
+   * have passed; here it is zeros.) */
+  void setOrder(size_t o) {
+    this->_order = std::max(size_t(1), o);
+    if (this->_plan) this->_newPlan(SDRHIP_KEEP_FM | SDRHIP_KEEP_COUNTERS);
+  }
+  inline double centerFrequency() const { return _Fc; }
+  /** As the reference (src/baseband.hh:84-86 -> src/freqshift.hh:52-54,78-87): new LUT increment and sign, the LUT
+   * phase restarts; filter history, decimator state and the kernel go on unchanged. */
+  void setCenterFrequency(double Fc) { _Fc = int32_t(Fc); this->_shift = _Fc; this->_setShift(); }
+  inline double filterFrequency() const { return _Ff; }
+  /** As the reference (:92-104): only the filter kernel is recomputed, all streaming state goes on. */
+  void setFilterFrequency(double Ff) { _Ff = int32_t(Ff); this->_retap(); }
+  inline double filterWidth() const { return _width; }
+  void setFilterWidth(double width) { _width = int32_t(width); this->_retap(); }
+  size_t subSample() const { return this->_sub_sample; }
+  void setSubsample(size_t sub_sample) { this->_sub_sample = std::max(size_t(1), sub_sample); if (_Fs) _reconfigure(); }
+  void setOutputSampleRate(double Fs) { _oFs = Fs; if (_Fs) _reconfigure(); }
+
+  virtual void config(const Config &src_cfg) {
+    if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
+    checkType<CIn>(src_cfg, "IQBaseBand");
+    _Fs = int32_t(src_cfg.sampleRate());
+    this->_sourceBs = src_cfg.bufferSize();
+    _reconfigure();
+  }
+
+  virtual void process(const Buffer<CIn> &buffer, bool allow_overwrite) {
+    if (!this->_plan) return;
+    if (allow_overwrite && sizeof(CIn) == sizeof(COut)) this->_run(buffer, Buffer<COut>(buffer));   // in place needs equal sample sizes
+    else if (this->_buffer.isUnused()) this->_run(buffer, this->_buffer);
+    // else: output buffer still in use downstream -> the input is dropped (src/baseband.hh:141-150)
+  }
+
+protected:
+  virtual double _rate() const { return double(_Fs); }
+  virtual std::vector<int32_t> _taps() const { return iqbbTaps(_Ff, _width, _Fs, this->_order); }
+  virtual int _create(const int32_t *taps, uint32_t inc, size_t D, sdrhip_iqbb_i16 **out) const {
+    int rc = (kInt8 ? sdrhip_iqbb_i8_create : sdrhip_iqbb_i16_create)(Device::get(this->_device), taps, int(this->_order),
+                 freqShiftLut(kInt8).data(), inc, 0 > this->_shift, int(D), 1, this->_sourceBs, this->_epilogue, out);
+    if (rc == SDRHIP_OK && kCu8) rc = sdrhip_iqbb_i16_set_input_format(*out, SDRHIP_IN_CU8);
+    return rc;
+  }
+  /** The decimation follows the output rate, where one is given, and is written back (src/baseband.hh:159-162). */
+  virtual void _reconfigure() {
+    const size_t D = design::iqbbDecimation(_Fs, this->_sub_sample, _oFs);
+    this->_sub_sample = D;
+    // the reference divides int32 by size_t (src/baseband.hh:192-193)
+    const Config out_cfg = this->_configure(D, double(size_t(_Fs) / D));
 
     LogMessage msg(LOG_DEBUG);
     msg << "Configured gpu::IQBaseBand node:" << std::endl << " sample-rate " << _Fs << "Hz" << std::endl
         << " center freq " << _Fc << "Hz" << std::endl << " width " << _width << "Hz" << std::endl
-        << " in buffer size " << _sourceBs << std::endl << " sub-sample by " << D << std::endl
-        << " out buffer size " << buffer_size;
+        << " in buffer size " << this->_sourceBs << std::endl << " sub-sample by " << D << std::endl
+        << " out buffer size " << out_cfg.bufferSize();
     Logger::get().log(msg);
 
     this->setConfig(out_cfg);
   }
 
-  void _process(const Buffer<CIn> &in, const Buffer<COut> &out) {
-    size_t n = 0;
-    // (out_stride in output elements: the demodulators' int16 fits sizeof(COut) / 2 times into a complex output sample)
-    if (!processOk(sdrhip_iqbb_i16_process(_plan, reinterpret_cast<const int16_t *>(in.data()), in.size(), 0,
-                                                   out.data(), out.size() * (_epilogue == SDRHIP_EPI_NONE ? 1 : sizeof(COut) / 2), &n),
-                           "gpu::IQBaseBand"))
-      return;
-    if (_epilogue == SDRHIP_EPI_NONE) this->send(out.head(n), true);
-    else if (_epilogue == SDRHIP_EPI_FM) { if (n) this->send(Buffer<int16_t>(out).head(n), false); }   // FMDemod: no send when empty
-    else this->send(Buffer<int16_t>(out).head(n), _epilogue == SDRHIP_EPI_AM);
-  }
-
-  int32_t _Fc, _Ff;
-  double _shift;
-  int32_t _Fs, _width;
-  size_t _order, _sub_sample;
+  // as the reference node keeps them (src/baseband.hh:266-272): int32 members, truncated; only the frequency shift
+  // (Bb16::_shift) starts as the constructor's untruncated double
+  int32_t _Fc, _Ff, _Fs, _width;
   double _oFs;
-  size_t _sourceBs;
-  int _epilogue, _device;
-  sdrhip_iqbb_i16 *_plan;
-  size_t _planOrder = 0, _planD = 0, _planBs = 0;   // geometry the device plan was made for
-  int _planEpi = 0;
-  Buffer<COut> _buffer;
 };
 }  // namespace detail
 
@@ -273,29 +416,20 @@ template <class Scalar> class IQBaseBand;
 template <>
 class IQBaseBand<int16_t> : public detail::IQBB16<int16_t> {
 public:
-  IQBaseBand(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<int16_t>(Fc, width, order, sub_sample, oFs, device) {}
-  IQBaseBand(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<int16_t>(Fc, Ff, width, order, sub_sample, oFs, device) {}
+  using detail::IQBB16<int16_t>::IQBB16;
 };
 /** Drop-in for sdr::IQBaseBand<int8_t>, the baseband of the reference's documentation example (src/sdr.hh:225-240):
  * sinks and sources complex<int8_t>. */
 template <>
 class IQBaseBand<int8_t> : public detail::IQBB16<int8_t> {
 public:
-  IQBaseBand(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<int8_t>(Fc, width, order, sub_sample, oFs, device) {}
-  IQBaseBand(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<int8_t>(Fc, Ff, width, order, sub_sample, oFs, device) {}
+  using detail::IQBB16<int8_t>::IQBB16;
 };
 /** AutoCast< complex<int16_t> > + IQBaseBand<int16_t> in one node: sinks complex<uint8_t> (RTL-SDR bytes). */
 template <>
 class IQBaseBand<uint8_t> : public detail::IQBB16<uint8_t> {
 public:
-  IQBaseBand(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<uint8_t>(Fc, width, order, sub_sample, oFs, device) {}
-  IQBaseBand(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : detail::IQBB16<uint8_t>(Fc, Ff, width, order, sub_sample, oFs, device) {}
+  using detail::IQBB16<uint8_t>::IQBB16;
 };
 
 /** IQBaseBand<float> — BASELINE config 2's node. The reference has NO working float baseband (IQBaseBand<float> does not
@@ -314,15 +448,11 @@ template <>
 class IQBaseBand<float> : public Sink<cf32>, public Source {
 public:
   IQBaseBand(double Fc, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
-    : _Fc(Fc), _Ff(Fc), _width(width), _Fs(0), _order(std::max(size_t(1), order)), _sub_sample(std::max(size_t(1), sub_sample)),
-      _oFs(oFs), _sourceBs(0), _device(device), _plan(0) {}
+    : IQBaseBand(Fc, Fc, width, order, sub_sample, oFs, device) {}
   IQBaseBand(double Fc, double Ff, double width, size_t order, size_t sub_sample, double oFs = 0.0, int device = 0)
     : _Fc(Fc), _Ff(Ff), _width(width), _Fs(0), _order(std::max(size_t(1), order)), _sub_sample(std::max(size_t(1), sub_sample)),
-      _oFs(oFs), _sourceBs(0), _device(device), _plan(0) {}
-  virtual ~IQBaseBand() {
-    if (_plan) sdrhip_fbb_f32_destroy(_plan);
-    _buffer.unref();
-  }
+      _oFs(oFs), _sourceBs(0), _device(device) {}
+  virtual ~IQBaseBand() { _buffer.unref(); }
   inline size_t order() const { return _order; }
   /** A new order is a new plan (filter history, decimator and phasor restart: the reference's setOrder reallocates its ring
    * too, src/baseband.hh:69-79); the same order changes nothing. */
@@ -354,11 +484,8 @@ public:
   /** New coefficients on the SAME plan (src/baseband.hh:95-101: setFilterWidth only recomputes the kernel; the ring stays). */
   void setFilterWidth(double width) {
     _width = width;
-    if (_plan) {
-      std::vector<double> alpha(_order);
-      design::firLowPass(_order, _width / 2, _Fs, alpha.data());
-      detail::configCheck(sdrhip_fbb_f32_set_taps(_plan, alpha.data()), "IQBaseBand<float>");
-    } else if (_Fs) _reconfigure();
+    if (_plan) detail::configCheck(sdrhip_fbb_f32_set_taps(_plan, detail::firLowPass(_order, _width / 2, _Fs).data()), "IQBaseBand<float>");
+    else if (_Fs) _reconfigure();
   }
   size_t subSample() const { return _sub_sample; }
   /** A decimation that does not change keeps plan and state; a new one is a new plan (the reference runs _reconfigure:
@@ -377,11 +504,7 @@ public:
 
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<cf32>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure IQBaseBand: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<cf32>();
-      throw err;
-    }
+    detail::checkType<cf32>(src_cfg, "IQBaseBand");
     _Fs = src_cfg.sampleRate();
     _sourceBs = src_cfg.bufferSize();
     _reconfigure();
@@ -408,10 +531,8 @@ protected:
     }
     const size_t D = design::iqbbDecimation(_Fs, _sub_sample, _oFs);
     _sub_sample = D;
-    std::vector<double> alpha(_order);
-    design::firLowPass(_order, _width / 2, _Fs, alpha.data());
-    if (_plan) { sdrhip_fbb_f32_destroy(_plan); _plan = 0; }
-    detail::configCheck(sdrhip_fbb_f32_create(Device::get(_device), _Fc, _Fs, alpha.data(), int(_order), int(D), 1, _sourceBs, &_plan),
+    const std::vector<double> alpha = detail::firLowPass(_order, _width / 2, _Fs);
+    detail::configCheck(sdrhip_fbb_f32_create(Device::get(_device), _Fc, _Fs, alpha.data(), int(_order), int(D), 1, _sourceBs, _plan.out()),
                         "IQBaseBand<float>");
     size_t buffer_size = _sourceBs / D + 1;   // (a call may emit one output more than Bs / D: the decimator's phase carries over)
     _buffer.unref();
@@ -430,7 +551,7 @@ protected:
   double _oFs;
   size_t _sourceBs;
   int _device;
-  sdrhip_fbb_f32 *_plan;
+  detail::Handle<sdrhip_fbb_f32, sdrhip_fbb_f32_destroy> _plan;
   Buffer<cf32> _buffer;
 };
 
@@ -442,48 +563,23 @@ template <class Scalar> class BaseBand;
  * place (the reference's process() ignores allow_overwrite, :408-419); drops the input while the output buffer is
  * still in use downstream. */
 template <>
-class BaseBand<int16_t> : public Sink<int16_t>, public Source {
+class BaseBand<int16_t> : public detail::Bb16<int16_t, cs16> {
 public:
-  BaseBand(double Fc, double width, size_t order, size_t sub_sample)
-    : _shift(Fc), _Ff(Fc), _width(width), _Fs(0), _order(std::max(size_t(1), order)), _sub_sample(sub_sample), _sourceBs(0),
-      _epilogue(SDRHIP_EPI_NONE), _device(0), _plan(0) {}
+  BaseBand(double Fc, double width, size_t order, size_t sub_sample) : BaseBand(Fc, Fc, width, order, sub_sample, 0) {}
   BaseBand(double Fc, double Ff, double width, size_t order, size_t sub_sample, int device = 0)
-    : _shift(Fc), _Ff(Ff), _width(width), _Fs(0), _order(std::max(size_t(1), order)), _sub_sample(sub_sample), _sourceBs(0),
-      _epilogue(SDRHIP_EPI_NONE), _device(device), _plan(0) {}
-  virtual ~BaseBand() {
-    if (_plan) sdrhip_iqbb_i16_destroy(_plan);
-    _buffer.unref();
-  }
-  /** Extension, as IQBaseBand::setDemod: fuse FM / AM / USB<int16_t> into the launch. */
-  void setDemod(int epilogue) { _epilogue = epilogue; if (_Fs) _reconfigure(); }
+    : detail::Bb16<int16_t, cs16>("BaseBand", Fc, order, sub_sample, device), _Ff(Ff), _width(width), _Fs(0) {}
   inline double sampleRate() const { return _Fs; }
   inline double frequencyShift() const { return _shift; }
   /** FreqShiftBase::setFrequencyShift (src/freqshift.hh:52-54,78-87): new increment and sign, the LUT phase restarts;
    * ring, decimator and kernel go on. */
-  void setFrequencyShift(double F) {
-    _shift = F;
-    if (_plan) detail::configCheck(sdrhip_iqbb_i16_set_shift(_plan, design::freqShiftIncrement(_shift, _Fs), 0 > _shift), "BaseBand");
-  }
+  void setFrequencyShift(double F) { _shift = F; _setShift(); }
   /** BaseBand::setSampleRate (src/baseband.hh:397-401): the LUT increment and the kernel are recomputed, nothing is
    * propagated (the reference marks that as a bug of its own, :400). */
-  void setSampleRate(double Fs) {
-    _Fs = Fs;
-    if (!_plan) return;
-    detail::configCheck(sdrhip_iqbb_i16_set_shift(_plan, design::freqShiftIncrement(_shift, _Fs), 0 > _shift), "BaseBand");
-    std::vector<int32_t> taps(2 * _order);
-    design::bbTaps(_Ff, _width, _Fs, _order, taps.data());
-    const int rc = sdrhip_iqbb_i16_set_taps(_plan, taps.data());
-    if (rc == SDRHIP_E_UNSUPPORTED) _newPlan(SDRHIP_KEEP_RING | SDRHIP_KEEP_FM | SDRHIP_KEEP_COUNTERS);
-    else detail::configCheck(rc, "BaseBand");
-  }
+  void setSampleRate(double Fs) { _Fs = Fs; _setShift(); _retap(); }
 
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<int16_t>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure BaseBand: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
-      throw err;
-    }
+    detail::checkType<int16_t>(src_cfg, "BaseBand");
     _Fs = src_cfg.sampleRate();
     _sourceBs = src_cfg.bufferSize();
     _reconfigure();
@@ -491,65 +587,24 @@ public:
 
   virtual void process(const Buffer<int16_t> &buffer, bool allow_overwrite) {
     (void)allow_overwrite;
-    if (!_plan || !_buffer.isUnused()) return;
-    size_t n = 0;
-    if (!detail::processOk(sdrhip_iqbb_i16_process(_plan, reinterpret_cast<const int16_t *>(buffer.data()), buffer.size(), 0, _buffer.data(),
-                                                   _buffer.size() * (_epilogue == SDRHIP_EPI_NONE ? 1 : 2), &n), "gpu::BaseBand"))
-      return;
-    if (_epilogue == SDRHIP_EPI_NONE) this->send(_buffer.head(n), true);
-    else if (_epilogue == SDRHIP_EPI_FM) { if (n) this->send(Buffer<int16_t>(_buffer).head(n), false); }
-    else this->send(Buffer<int16_t>(_buffer).head(n), _epilogue == SDRHIP_EPI_AM);
+    if (_plan && _buffer.isUnused()) _run(buffer, _buffer);
   }
 
 protected:
-  void _newPlan(int carry) {
-    std::vector<int32_t> taps(2 * _order), lut(2 * design::kLutSize);
+  virtual double _rate() const { return _Fs; }
+  virtual std::vector<int32_t> _taps() const {
+    std::vector<int32_t> taps(2 * _order);
     design::bbTaps(_Ff, _width, _Fs, _order, taps.data());
-    design::freqShiftLutI16(lut.data());
-    sdrhip_iqbb_i16 *neu = 0;
-    detail::configCheck(sdrhip_bb_i16_create(Device::get(_device), taps.data(), int(_order), lut.data(), design::freqShiftIncrement(_shift, _Fs),
-                                             0 > _shift, int(_sub_sample), 1, _sourceBs, _epilogue, &neu), "BaseBand");
-    if (_plan) {
-      if (_planEpi != SDRHIP_EPI_FM || _epilogue != SDRHIP_EPI_FM) carry &= ~SDRHIP_KEEP_FM;
-      const int rc = sdrhip_iqbb_i16_adopt_state(neu, _plan, carry);
-      if (rc != SDRHIP_OK) { sdrhip_iqbb_i16_destroy(neu); detail::configCheck(rc, "BaseBand"); }
-      sdrhip_iqbb_i16_destroy(_plan);
-    }
-    _plan = neu; _planBs = _sourceBs; _planEpi = _epilogue;
+    return taps;
   }
-
-  /** BaseBand::config (src/baseband.hh:357-395): sample rate (LUT increment, kernel), output buffer, counters reset —
-   * the ring's contents stay where they lie, as in IQBaseBand::_reconfigure. */
-  void _reconfigure() {
-    size_t buffer_size = _sourceBs / _sub_sample;
-    if (_sourceBs % _sub_sample) buffer_size += 1;
-    const Config out_cfg(_epilogue == SDRHIP_EPI_NONE ? Config::typeId<cs16>() : Config::typeId<int16_t>(), _Fs / _sub_sample, buffer_size, 1);
-    const bool same_cfg = (out_cfg == this->_config);
-    bool reuse = _plan && _planBs == _sourceBs && _planEpi == _epilogue;
-    if (reuse) {
-      std::vector<int32_t> taps(2 * _order);
-      design::bbTaps(_Ff, _width, _Fs, _order, taps.data());
-      const int rc = sdrhip_iqbb_i16_set_taps(_plan, taps.data());
-      if (rc == SDRHIP_E_UNSUPPORTED) reuse = false;
-      else {
-        detail::configCheck(rc, "BaseBand");
-        detail::configCheck(sdrhip_iqbb_i16_set_shift(_plan, design::freqShiftIncrement(_shift, _Fs), 0 > _shift), "BaseBand");
-        detail::configCheck(sdrhip_iqbb_i16_reset(_plan, same_cfg ? 3 : 1), "BaseBand");
-      }
-    }
-    if (!reuse) _newPlan(SDRHIP_KEEP_RING | (same_cfg ? SDRHIP_KEEP_FM : 0));
-    _buffer.unref();
-    _buffer = Buffer<cs16>(buffer_size);
-    this->setConfig(out_cfg);
+  virtual int _create(const int32_t *taps, uint32_t inc, size_t D, sdrhip_iqbb_i16 **out) const {
+    return sdrhip_bb_i16_create(Device::get(_device), taps, int(_order), detail::freqShiftLut().data(), inc, 0 > _shift, int(D), 1,
+                                _sourceBs, _epilogue, out);
   }
+  /** The decimation is the constructor's; the output rate is the double quotient (src/baseband.hh:357-395). */
+  virtual void _reconfigure() { this->setConfig(_configure(_sub_sample, _Fs / _sub_sample)); }
 
-  size_t _planBs = 0;
-  int _planEpi = 0;
-  double _shift, _Ff, _width, _Fs;
-  size_t _order, _sub_sample, _sourceBs;
-  int _epilogue, _device;
-  sdrhip_iqbb_i16 *_plan;
-  Buffer<cs16> _buffer;
+  double _Ff, _width, _Fs;
 };
 
 // =================================================================================================
@@ -559,11 +614,8 @@ template <class Scalar>
 class FIRLowPass : public Sink<Scalar>, public Source {
 public:
   FIRLowPass(size_t order, double Fc, int device = 0)
-    : _enabled(true), _order(std::max(size_t(1), order)), _Fu(Fc), _Fs(0), _bs(0), _device(device), _plan(0) {}
-  virtual ~FIRLowPass() {
-    if (_plan) sdrhip_fir_destroy(_plan);
-    _buffer.unref();
-  }
+    : _enabled(true), _order(std::max(size_t(1), order)), _Fu(Fc), _Fs(0), _bs(0), _device(device) {}
+  virtual ~FIRLowPass() { _buffer.unref(); }
   inline bool enabled() const { return _enabled; }
   inline void enable(bool enable) { _enabled = enable; }
   inline size_t order() const { return _order; }
@@ -574,18 +626,12 @@ public:
     _Fu = freq;
     if (!_Fs) return;
     if (!_plan) { _plan_(); return; }
-    std::vector<double> alpha(_order);
-    design::firLowPass(_order, _Fu, _Fs, alpha.data());
-    detail::configCheck(sdrhip_fir_set_taps(_plan, alpha.data()), "FIRLowPass");
+    detail::configCheck(sdrhip_fir_set_taps(_plan, detail::firLowPass(_order, _Fu, _Fs).data()), "FIRLowPass");
   }
 
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<Scalar>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure FIRLowPass: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<Scalar>();
-      throw err;
-    }
+    detail::checkType<Scalar>(src_cfg, "FIRLowPass");
     _Fs = src_cfg.sampleRate();
     _bs = src_cfg.bufferSize();
     _plan_();   // a fresh plan = zeroed ring, as FIRFilter::config does (src/firfilter.hh:193-195)
@@ -603,11 +649,9 @@ public:
 
 protected:
   void _plan_() {
-    std::vector<double> alpha(_order);
-    design::firLowPass(_order, _Fu, _Fs, alpha.data());
-    if (_plan) { sdrhip_fir_destroy(_plan); _plan = 0; }
+    const std::vector<double> alpha = detail::firLowPass(_order, _Fu, _Fs);
     detail::configCheck(sdrhip_fir_create(Device::get(_device), detail::TypeTag<Scalar>::fir, alpha.data(), int(_order), 1, 1,
-                                          _bs, SDRHIP_EPI_NONE, &_plan), "FIRLowPass");
+                                          _bs, SDRHIP_EPI_NONE, _plan.out()), "FIRLowPass");
   }
   void _process(const Buffer<Scalar> &in, const Buffer<Scalar> &out) {
     size_t n = 0;
@@ -619,7 +663,7 @@ protected:
   double _Fu, _Fs;
   size_t _bs;
   int _device;
-  sdrhip_fir *_plan;
+  detail::Handle<sdrhip_fir, sdrhip_fir_destroy> _plan;
   Buffer<Scalar> _buffer;
 };
 
@@ -630,20 +674,12 @@ namespace detail {
 template <class InC, class OutR>
 class DemodBase : public Sink<InC>, public Source {
 public:
-  DemodBase(int kind, const char *name, int device) : _kind(kind), _name(name), _device(device), _plan(0), _can_overwrite(true) {}
-  virtual ~DemodBase() {
-    if (_plan) sdrhip_demod_destroy(_plan);
-    _buffer.unref();
-  }
+  DemodBase(int kind, const char *name, int device) : _kind(kind), _name(name), _device(device), _can_overwrite(true) {}
+  virtual ~DemodBase() { _buffer.unref(); }
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<InC>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure " << _name << ": Invalid type " << src_cfg.type() << ", expected " << Config::typeId<InC>();
-      throw err;
-    }
-    if (_plan) { sdrhip_demod_destroy(_plan); _plan = 0; }
-    configCheck(sdrhip_demod_create(Device::get(_device), _kind, TypeTag<InC>::dtype, 1, src_cfg.bufferSize(), 0, &_plan), _name);
+    checkType<InC>(src_cfg, _name);
+    configCheck(sdrhip_demod_create(Device::get(_device), _kind, TypeTag<InC>::dtype, 1, src_cfg.bufferSize(), 0, _plan.out()), _name);
     if (!_buffer.isEmpty()) _buffer.unref();
     _buffer = Buffer<OutR>(src_cfg.bufferSize());
     this->setConfig(Config(Config::typeId<OutR>(), src_cfg.sampleRate(), src_cfg.bufferSize(),
@@ -662,7 +698,7 @@ protected:
   int _kind;
   const char *_name;
   int _device;
-  sdrhip_demod *_plan;
+  Handle<sdrhip_demod, sdrhip_demod_destroy> _plan;
   bool _can_overwrite;
   Buffer<OutR> _buffer;
 };
@@ -697,23 +733,16 @@ template <class Scalar> class FMDeemph;
 template <>
 class FMDeemph<int16_t> : public Sink<int16_t>, public Source {
 public:
-  explicit FMDeemph(bool enabled = true, int device = 0) : _enabled(enabled), _device(device), _plan(0) {}
-  virtual ~FMDeemph() {
-    if (_plan) sdrhip_deemph_i16_destroy(_plan);
-    _buffer.unref();
-  }
+  explicit FMDeemph(bool enabled = true, int device = 0) : _enabled(enabled), _device(device) {}
+  virtual ~FMDeemph() { _buffer.unref(); }
   inline bool isEnabled() const { return _enabled; }
   inline void enable(bool enabled) { _enabled = enabled; }
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<int16_t>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure FMDeemph: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
-      throw err;
-    }
-    if (_plan) { sdrhip_deemph_i16_destroy(_plan); _plan = 0; }   // a fresh plan: average reset to 0 (:308)
+    detail::checkType<int16_t>(src_cfg, "FMDeemph");
+    _plan.reset();   // a fresh plan: average reset to 0 (:308)
     detail::configCheck(sdrhip_deemph_i16_create(Device::get(_device), design::fmDeemphAlpha(src_cfg.sampleRate()), 1,
-                                                 src_cfg.bufferSize(), &_plan), "FMDeemph");
+                                                 src_cfg.bufferSize(), _plan.out()), "FMDeemph");
     _buffer.unref();
     _buffer = Buffer<int16_t>(src_cfg.bufferSize());
     this->setConfig(Config(src_cfg.type(), src_cfg.sampleRate(), src_cfg.bufferSize(), 1));
@@ -731,29 +760,13 @@ public:
 protected:
   bool _enabled;
   int _device;
-  sdrhip_deemph *_plan;
+  detail::Handle<sdrhip_deemph, sdrhip_deemph_i16_destroy> _plan;
   Buffer<int16_t> _buffer;
 };
 
 // =================================================================================================
 // audio to bits: FSKDetector, ASKDetector<int16_t>, BitStream (reference src/fsk.hh, src/fsk.cc)
 // =================================================================================================
-namespace detail {
-/** The direct hand-off of symbols between a gpu detector and a gpu::BitStream, as SpectrumHandoff below: just before a
- * direct send the detector records {host buffer data -> device symbols}; the host buffer stays unfilled and a BitStream
- * that receives that very buffer reads the device copy. */
-struct SymbolHandoff { const uint8_t *dev; int device; };
-inline std::map<const void *, SymbolHandoff> &symbolHandoffs() {
-  static std::map<const void *, SymbolHandoff> table;
-  return table;
-}
-inline void *symAlloc(sdrhip_ctx *c, size_t bytes, const char *what) {
-  void *p = 0;
-  configCheck(sdrhip_malloc(c, bytes, &p), what);
-  return p;
-}
-}  // namespace detail
-
 /** Drop-in for sdr::BitStream (reference src/fsk.hh:124-171, src/fsk.cc:102-202): symbols in, bits out, sent only when a
  * buffer produced at least one (:201). The output buffer holds ceil(bufferSize * omegaMax) + 1 bits (the reference's
  * 1 + bufferSize / corrLen can be exceeded by its own PLL); the Config forwarded says so. */
@@ -761,24 +774,21 @@ class BitStream : public Sink<uint8_t>, public Source {
 public:
   typedef enum { NORMAL, TRANSITION } Mode;
   explicit BitStream(float baud, Mode mode = TRANSITION, int device = 0)
-    : _baud(baud), _mode(mode), _device(device), _plan(0), _in(0), _out(0), _counts(0), _cap(0), _onDevice(false) {}
-  virtual ~BitStream() { _release(); _buffer.unref(); }
+    : _baud(baud), _mode(mode), _device(device), _cap(0), _onDevice(false) {}
+  virtual ~BitStream() { _buffer.unref(); }
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
-    if (Config::typeId<uint8_t>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure BitStream: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
-      throw err;
-    }
-    _release();   // a fresh plan: ring, PLL and bit history start over (:125-140)
+    // (the type named as expected is the reference's, src/fsk.cc:116)
+    detail::checkType(src_cfg, Config::typeId<uint8_t>(), Config::typeId<int16_t>(), "BitStream");
+    _plan.reset();   // a fresh plan: ring, PLL and bit history start over (:125-140)
     sdrhip_ctx *c = Device::get(_device);
     const size_t bs = std::max(size_t(1), src_cfg.bufferSize());
     detail::configCheck(sdrhip_bits_create(c, src_cfg.sampleRate(), _baud, _mode == TRANSITION ? SDRHIP_BITS_TRANSITION : SDRHIP_BITS_NORMAL,
-                                           1, bs, &_plan), "BitStream");
+                                           1, bs, _plan.out()), "BitStream");
     detail::configCheck(sdrhip_bits_out_capacity(_plan, bs, &_cap), "BitStream");
-    _in = detail::symAlloc(c, bs, "BitStream");
-    _out = detail::symAlloc(c, _cap, "BitStream");
-    _counts = detail::symAlloc(c, sizeof(uint32_t), "BitStream");
+    _in.alloc(c, bs, "BitStream");
+    _out.alloc(c, _cap, "BitStream");
+    _counts.alloc(c, sizeof(uint32_t), "BitStream");
     _buffer.unref();
     _buffer = Buffer<uint8_t>(_cap);
     LogMessage msg(LOG_DEBUG);
@@ -793,19 +803,18 @@ public:
   virtual void process(const Buffer<uint8_t> &buffer, bool) {
     if (!_plan) return;
     sdrhip_ctx *c = Device::get(_device);
-    const std::map<const void *, detail::SymbolHandoff> &t = detail::symbolHandoffs();
-    std::map<const void *, detail::SymbolHandoff>::const_iterator it = t.find(buffer.data());
-    _onDevice = it != t.end() && it->second.device == _device;
-    const uint8_t *sym = _onDevice ? it->second.dev : reinterpret_cast<const uint8_t *>(_in);
+    const void *handed = detail::handoffFor(buffer.data(), _device);
+    _onDevice = handed != 0;
+    const uint8_t *sym = _onDevice ? static_cast<const uint8_t *>(handed) : _in.as<uint8_t>();
     if (!_onDevice && buffer.size() &&
-        !detail::processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), buffer.size()), "gpu::BitStream")) return;
-    if (!detail::processOk(sdrhip_bits_process_dev(_plan, sym, buffer.size(), 0, reinterpret_cast<uint8_t *>(_out), _cap,
-                                                   reinterpret_cast<uint32_t *>(_counts)), "gpu::BitStream")) return;
+        !detail::processOk(sdrhip_memcpy_h2d(c, _in.get(), buffer.data(), buffer.size()), "gpu::BitStream")) return;
+    if (!detail::processOk(sdrhip_bits_process_dev(_plan, sym, buffer.size(), 0, _out.as<uint8_t>(), _cap, _counts.as<uint32_t>()),
+                           "gpu::BitStream")) return;
     uint32_t o = 0;
-    if (!detail::processOk(sdrhip_memcpy_d2h(c, &o, _counts, sizeof(o)), "gpu::BitStream")) return;
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, &o, _counts.get(), sizeof(o)), "gpu::BitStream")) return;
     if (0 == o) return;                                                              // :201
     if (!_buffer.isUnused()) return;   // still referenced downstream: the bits of this buffer are dropped
-    if (!detail::processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _out, o), "gpu::BitStream")) return;
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _out.get(), o), "gpu::BitStream")) return;
     this->send(_buffer.head(o));
   }
   /** true: the last buffer's symbols were read from a gpu detector's device memory (no host copy in between). */
@@ -813,18 +822,11 @@ public:
   int device() const { return _device; }
 
 protected:
-  void _release() {
-    if (_plan) { sdrhip_bits_destroy(_plan); _plan = 0; }
-    sdrhip_ctx *c = (_in || _out || _counts) ? Device::get(_device) : 0;
-    if (_in) { sdrhip_free(c, _in); _in = 0; }
-    if (_out) { sdrhip_free(c, _out); _out = 0; }
-    if (_counts) { sdrhip_free(c, _counts); _counts = 0; }
-  }
   float _baud;
   Mode _mode;
   int _device;
-  sdrhip_bits *_plan;
-  void *_in, *_out, *_counts;
+  detail::Handle<sdrhip_bits, sdrhip_bits_destroy> _plan;
+  detail::DeviceMem _in, _out, _counts;
   size_t _cap;
   bool _onDevice;
   Buffer<uint8_t> _buffer;
@@ -836,58 +838,40 @@ namespace detail {
  * same device, the symbols stay on the device and the buffer sent is left unfilled; otherwise they are copied into it. */
 class DetectorBase : public Sink<int16_t>, public Source {
 public:
-  DetectorBase(const char *name, int device) : _name(name), _device(device), _plan(0), _in(0), _sym(0), _onDevice(false) {}
-  virtual ~DetectorBase() { _release(); _buffer.unref(); }
+  DetectorBase(const char *name, int device) : _name(name), _device(device), _onDevice(false) {}
+  virtual ~DetectorBase() { _buffer.unref(); }
   virtual void process(const Buffer<int16_t> &buffer, bool) {
     if (!_plan) return;
     sdrhip_ctx *c = Device::get(_device);
     const size_t n = buffer.size();
-    if (n && (!processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), n * sizeof(int16_t)), _name) ||
-              !processOk(sdrhip_detector_process_dev(_plan, reinterpret_cast<const int16_t *>(_in), n, 0,
-                                                     reinterpret_cast<uint8_t *>(_sym), 0), _name))) return;
-    _onDevice = _deviceHandoff();
+    if (n && (!processOk(sdrhip_memcpy_h2d(c, _in.get(), buffer.data(), n * sizeof(int16_t)), _name) ||
+              !processOk(sdrhip_detector_process_dev(_plan, _in.as<int16_t>(), n, 0, _sym.as<uint8_t>(), 0), _name))) return;
+    _onDevice = allSinksDirectOn<gpu::BitStream>(_sinks, _device);
     if (!_onDevice) {
-      if (n && !processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _sym, n), _name)) return;
+      if (n && !processOk(sdrhip_memcpy_d2h(c, _buffer.data(), _sym.get(), n), _name)) return;
       this->send(_buffer.head(n), false);
       return;
     }
-    const SymbolHandoff rec = {reinterpret_cast<const uint8_t *>(_sym), _device};
-    symbolHandoffs()[_buffer.data()] = rec;
+    const HandoffScope handoff(_buffer.data(), _sym.get(), _device);
     this->send(_buffer.head(n), false);
-    symbolHandoffs().erase(_buffer.data());
   }
   /** true: the last buffer's symbols went to the BitStream nodes on the device (no host copy). */
   bool lastBufferOnDevice() const { return _onDevice; }
 
 protected:
   void _plan_(int kind, const float *mark, const float *space, int corrLen, bool invert, size_t bufferSize) {
-    _release();
     sdrhip_ctx *c = Device::get(_device);
     const size_t bs = std::max(size_t(1), bufferSize);
-    configCheck(sdrhip_detector_create(c, kind, mark, space, corrLen, invert ? 1 : 0, 1, bs, &_plan), _name);
-    _in = symAlloc(c, bs * sizeof(int16_t), _name);
-    _sym = symAlloc(c, bs, _name);
+    configCheck(sdrhip_detector_create(c, kind, mark, space, corrLen, invert ? 1 : 0, 1, bs, _plan.out()), _name);
+    _in.alloc(c, bs * sizeof(int16_t), _name);
+    _sym.alloc(c, bs, _name);
     _buffer.unref();
     _buffer = Buffer<uint8_t>(bs);
   }
-  bool _deviceHandoff() const {
-    if (_sinks.empty()) return false;
-    for (std::map<SinkBase *, bool>::const_iterator it = _sinks.begin(); it != _sinks.end(); ++it) {
-      const gpu::BitStream *s = dynamic_cast<const gpu::BitStream *>(it->first);
-      if (!it->second || !s || s->device() != _device) return false;
-    }
-    return true;
-  }
-  void _release() {
-    if (_plan) { sdrhip_detector_destroy(_plan); _plan = 0; }
-    sdrhip_ctx *c = (_in || _sym) ? Device::get(_device) : 0;
-    if (_in) { sdrhip_free(c, _in); _in = 0; }
-    if (_sym) { sdrhip_free(c, _sym); _sym = 0; }
-  }
   const char *_name;
   int _device;
-  sdrhip_detector *_plan;
-  void *_in, *_sym;
+  Handle<sdrhip_detector, sdrhip_detector_destroy> _plan;
+  DeviceMem _in, _sym;
   bool _onDevice;
   Buffer<uint8_t> _buffer;
 };
@@ -900,11 +884,7 @@ public:
     : detail::DetectorBase("FSKDetector", device), _baud(baud), _corrLen(0), _Fmark(Fmark), _Fspace(Fspace) {}
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
-    if (Config::typeId<int16_t>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure FSKBase: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
-      throw err;
-    }
+    detail::checkType<int16_t>(src_cfg, "FSKBase");
     _corrLen = size_t(design::fskCorrLen(src_cfg.sampleRate(), _baud));
     std::vector<float> mark(2 * _corrLen), space(2 * _corrLen);
     design::fskLut(src_cfg.sampleRate(), _Fmark, int(_corrLen), mark.data());
@@ -933,11 +913,7 @@ public:
   explicit ASKDetector(bool invert = false, int device = 0) : detail::DetectorBase("ASKDetector", device), _invert(invert) {}
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasSampleRate()) return;
-    if (Config::typeId<int16_t>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure ASKDetector: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<int16_t>();
-      throw err;
-    }
+    detail::checkType<int16_t>(src_cfg, "ASKDetector");
     _plan_(SDRHIP_DET_ASK, 0, 0, 0, _invert, src_cfg.bufferSize());
     LogMessage msg(LOG_DEBUG);
     msg << "Config ASKDetector node: " << std::endl
@@ -958,24 +934,16 @@ protected:
 template <class Scalar>
 class SubSample : public Sink<Scalar>, public Source {
 public:
-  explicit SubSample(size_t n, int device = 0) : _n(n), _oFs(0), _device(device), _plan(0) {}
-  explicit SubSample(double Fs, int device = 0) : _n(1), _oFs(Fs), _device(device), _plan(0) {}
-  virtual ~SubSample() {
-    if (_plan) sdrhip_subsample_destroy(_plan);
-    _buffer.unref();
-  }
+  explicit SubSample(size_t n, int device = 0) : _n(n), _oFs(0), _device(device) {}
+  explicit SubSample(double Fs, int device = 0) : _n(1), _oFs(Fs), _device(device) {}
+  virtual ~SubSample() { _buffer.unref(); }
   virtual void config(const Config &src_cfg) {
     if (!src_cfg.hasType() || !src_cfg.hasBufferSize()) return;
-    if (Config::typeId<Scalar>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure SubSample node: Invalid buffer type " << src_cfg.type() << ", expected " << Config::typeId<Scalar>();
-      throw err;
-    }
+    detail::checkType<Scalar>(src_cfg, "SubSample node", "buffer type");
     if (_oFs > 0) _n = size_t(std::max(1.0, src_cfg.sampleRate() / _oFs));
     size_t out_size = src_cfg.bufferSize() / _n;
     if (src_cfg.bufferSize() % _n) out_size += 1;
-    if (_plan) { sdrhip_subsample_destroy(_plan); _plan = 0; }
-    detail::configCheck(sdrhip_subsample_create(Device::get(_device), detail::TypeTag<Scalar>::dtype, _n, 1, src_cfg.bufferSize(), &_plan),
+    detail::configCheck(sdrhip_subsample_create(Device::get(_device), detail::TypeTag<Scalar>::dtype, _n, 1, src_cfg.bufferSize(), _plan.out()),
                         "SubSample");
     _buffer.unref();
     _buffer = Buffer<Scalar>(out_size);
@@ -996,7 +964,7 @@ protected:
   size_t _n;
   double _oFs;
   int _device;
-  sdrhip_subsample *_plan;
+  detail::Handle<sdrhip_subsample, sdrhip_subsample_destroy> _plan;
   Buffer<Scalar> _buffer;
 };
 
@@ -1025,25 +993,6 @@ template <> struct FftConvApi<double> {
 // =================================================================================================
 template <class Scalar> class FilterSource;
 
-namespace detail {
-template <class Scalar> struct SplitTag;
-template <> struct SplitTag<float> { enum { dtype = SDRHIP_T_CF32 }; };
-template <> struct SplitTag<double> { enum { dtype = SDRHIP_T_CF64 }; };
-/** The direct hand-off of a spectrum between a gpu::FilterSink and its gpu::FilterSources: just before a direct send the
- * sink records {host buffer data -> device spectrum, device}; the host buffer stays unfilled, and a source that receives
- * that very buffer reads the device copy. Direct delivery is synchronous, so the sink erases the entry after send. */
-struct SpectrumHandoff { const void *dev; int device; };
-inline std::map<const void *, SpectrumHandoff> &spectrumHandoffs() {
-  static std::map<const void *, SpectrumHandoff> table;
-  return table;
-}
-inline void *deviceAlloc(sdrhip_ctx *c, size_t bytes, const char *what) {
-  void *p = 0;
-  configCheck(sdrhip_malloc(c, bytes, &p), what);
-  return p;
-}
-}  // namespace detail
-
 /** Drop-in for sdr::FilterSink<Scalar>, Scalar = float or double (reference src/filternode.hh:32-99): every buffer of
  * block_size samples becomes one 2 x block_size-point spectrum (zero-padded block, forward DFT, natural order), sent as
  * complex<Scalar>. The config it propagates says bufferSize = block_size, as the reference's does (:76-77), although its
@@ -1055,16 +1004,12 @@ class FilterSink : public Sink< std::complex<Scalar> >, public Source {
 public:
   typedef std::complex<Scalar> CScalar;
   FilterSink(size_t block_size, int device = 0)
-    : _block(block_size), _device(device), _plan(0), _in(0), _spec(0), _out(2 * block_size), _onDevice(false) {}
-  virtual ~FilterSink() { _release(); _out.unref(); }
+    : _block(block_size), _device(device), _out(2 * block_size), _onDevice(false) {}
+  virtual ~FilterSink() { _out.unref(); }
 
   virtual void config(const Config &src_cfg) {
     if ((Config::Type_UNDEFINED == src_cfg.type()) || (0 == src_cfg.sampleRate()) || (0 == src_cfg.bufferSize())) return;
-    if (Config::typeId<CScalar>() != src_cfg.type()) {
-      ConfigError err;
-      err << "Can not configure filter-sink: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<CScalar>();
-      throw err;
-    }
+    detail::checkType<CScalar>(src_cfg, "filter-sink");
     if (_block != src_cfg.bufferSize()) {
       ConfigError err;
       err << "Can not configure filter-sink: Invalid buffer size " << src_cfg.bufferSize() << ", expected " << _block;
@@ -1072,16 +1017,16 @@ public:
     }
     if (!_plan) {
       sdrhip_ctx *c = Device::get(_device);
-      detail::configCheck(sdrhip_fftsink_create(c, detail::SplitTag<Scalar>::dtype, int(_block), 1, 1, &_plan), "gpu::FilterSink");
-      _in = detail::deviceAlloc(c, _block * sizeof(CScalar), "gpu::FilterSink");
-      _spec = detail::deviceAlloc(c, 2 * _block * sizeof(CScalar), "gpu::FilterSink");
+      detail::configCheck(sdrhip_fftsink_create(c, detail::TypeTag<CScalar>::dtype, int(_block), 1, 1, _plan.out()), "gpu::FilterSink");
+      _in.alloc(c, _block * sizeof(CScalar), "gpu::FilterSink");
+      _spec.alloc(c, 2 * _block * sizeof(CScalar), "gpu::FilterSink");
     }
     setConfig(Config(Config::typeId<CScalar>(), src_cfg.sampleRate(), src_cfg.bufferSize(), src_cfg.numBuffers()));
   }
 
   virtual void process(const Buffer<CScalar> &buffer, bool) {
     if (!_plan || buffer.size() != _block) return;
-    _onDevice = _deviceHandoff();
+    _onDevice = detail::allSinksDirectOn< gpu::FilterSource<Scalar> >(this->_sinks, _device);
     if (!_onDevice) {
       // the repo's drop rule: a buffer still referenced downstream is not overwritten
       if (!_out.isUnused()) return;
@@ -1090,12 +1035,10 @@ public:
       return;
     }
     sdrhip_ctx *c = Device::get(_device);
-    if (!detail::processOk(sdrhip_memcpy_h2d(c, _in, buffer.data(), _block * sizeof(CScalar)), "gpu::FilterSink") ||
-        !detail::processOk(sdrhip_fftsink_process_dev(_plan, _in, _block, 0, _spec, 0), "gpu::FilterSink")) return;
-    const detail::SpectrumHandoff rec = {_spec, _device};
-    detail::spectrumHandoffs()[_out.data()] = rec;
+    if (!detail::processOk(sdrhip_memcpy_h2d(c, _in.get(), buffer.data(), _block * sizeof(CScalar)), "gpu::FilterSink") ||
+        !detail::processOk(sdrhip_fftsink_process_dev(_plan, _in.get(), _block, 0, _spec.get(), 0), "gpu::FilterSink")) return;
+    const detail::HandoffScope handoff(_out.data(), _spec.get(), _device);
     send(_out);
-    detail::spectrumHandoffs().erase(_out.data());
   }
 
   /** true: the last block's spectrum went to the sources on the device (no host copy). */
@@ -1104,16 +1047,10 @@ public:
   int device() const { return _device; }
 
 protected:
-  bool _deviceHandoff() const;
-  void _release() {
-    if (_plan) { sdrhip_fftsink_destroy(_plan); _plan = 0; }
-    if (_in) { sdrhip_free(Device::get(_device), _in); _in = 0; }
-    if (_spec) { sdrhip_free(Device::get(_device), _spec); _spec = 0; }
-  }
   size_t _block;
   int _device;
-  sdrhip_fftsink *_plan;
-  void *_in, *_spec;
+  detail::Handle<sdrhip_fftsink, sdrhip_fftsink_destroy> _plan;
+  detail::DeviceMem _in, _spec;
   Buffer<CScalar> _out;
   bool _onDevice;
 };
@@ -1130,23 +1067,13 @@ class FilterSource : public Sink< std::complex<Scalar> >, public Source {
 public:
   typedef std::complex<Scalar> CScalar;
   FilterSource(size_t block_size, double fmin, double fmax, int device = 0)
-    : _block(block_size), _fmin(fmin), _fmax(fmax), _device(device), _Fs(0), _plan(0), _spec(0), _outDev(0),
-      _onDevice(false), _inert(false) {}
-  virtual ~FilterSource() {
-    if (_plan) sdrhip_fftsource_destroy(_plan);
-    if (_spec) sdrhip_free(Device::get(_device), _spec);
-    if (_outDev) sdrhip_free(Device::get(_device), _outDev);
-    _buffer.unref();
-  }
+    : FilterSource(Inert(), block_size, fmin, fmax, device) { _inert = false; }
+  virtual ~FilterSource() { _buffer.unref(); }
 
   /** FilterSource::setFreq (:128-130): the kernel is recomputed (once configured) and applies from the next block. */
   virtual void setFreq(double fmin, double fmax) {
     _fmin = fmin; _fmax = fmax;
-    if (_plan) {
-      std::vector<Scalar> K(4 * _block);
-      _kernel(K.data());
-      detail::configCheck(sdrhip_fftsource_set_kernel(_plan, K.data()), "FilterSource");
-    }
+    if (_plan) detail::configCheck(sdrhip_fftsource_set_kernel(_plan, _kernel().data()), "FilterSource");
   }
   virtual double fmin() const { return _fmin; }
   virtual double fmax() const { return _fmax; }
@@ -1163,14 +1090,13 @@ public:
       throw err;
     }
     _Fs = src_cfg.sampleRate();
-    std::vector<Scalar> K(4 * _block);
-    _kernel(K.data());
+    const std::vector<Scalar> K = _kernel();
     if (!_plan) {
       sdrhip_ctx *c = Device::get(_device);
-      detail::configCheck(sdrhip_fftsource_create(c, detail::SplitTag<Scalar>::dtype, int(_block), K.data(), 1, 1, &_plan),
+      detail::configCheck(sdrhip_fftsource_create(c, detail::TypeTag<CScalar>::dtype, int(_block), K.data(), 1, 1, _plan.out()),
                           "FilterSource");
-      _spec = detail::deviceAlloc(c, 2 * _block * sizeof(CScalar), "FilterSource");
-      _outDev = detail::deviceAlloc(c, _block * sizeof(CScalar), "FilterSource");
+      _spec.alloc(c, 2 * _block * sizeof(CScalar), "FilterSource");
+      _outDev.alloc(c, _block * sizeof(CScalar), "FilterSource");
       _buffer = Buffer<CScalar>(_block);
       _scratch.resize(_block);
     } else {
@@ -1183,15 +1109,14 @@ public:
     if (_inert || !_plan || buffer.size() < 2 * _block) return;
     sdrhip_ctx *c = Device::get(_device);
     const bool keep = _buffer.isUnused();
-    const std::map<const void *, detail::SpectrumHandoff> &t = detail::spectrumHandoffs();
-    const std::map<const void *, detail::SpectrumHandoff>::const_iterator it = t.find(buffer.data());
-    _onDevice = it != t.end() && it->second.device == _device;
-    const void *spec = _onDevice ? it->second.dev : _spec;
-    if (!_onDevice && !detail::processOk(sdrhip_memcpy_h2d(c, _spec, buffer.data(), 2 * _block * sizeof(CScalar)), "FilterSource"))
+    const void *handed = detail::handoffFor(buffer.data(), _device);
+    _onDevice = handed != 0;
+    const void *spec = _onDevice ? handed : _spec.get();
+    if (!_onDevice && !detail::processOk(sdrhip_memcpy_h2d(c, _spec.get(), buffer.data(), 2 * _block * sizeof(CScalar)), "FilterSource"))
       return;
-    if (!detail::processOk(sdrhip_fftsource_process_dev(_plan, spec, 1, 0, _outDev, 0), "FilterSource")) return;
+    if (!detail::processOk(sdrhip_fftsource_process_dev(_plan, spec, 1, 0, _outDev.get(), 0), "FilterSource")) return;
     CScalar *dst = keep ? reinterpret_cast<CScalar *>(_buffer.data()) : _scratch.data();
-    if (!detail::processOk(sdrhip_memcpy_d2h(c, dst, _outDev, _block * sizeof(CScalar)), "FilterSource") || !keep) return;
+    if (!detail::processOk(sdrhip_memcpy_d2h(c, dst, _outDev.get(), _block * sizeof(CScalar)), "FilterSource") || !keep) return;
     send(_buffer);
   }
 
@@ -1199,33 +1124,18 @@ protected:
   /** Band of gpu::FilterNode: no device state, its sink side does nothing (the bank runs it). */
   struct Inert {};
   FilterSource(Inert, size_t block_size, double fmin, double fmax, int device)
-    : _block(block_size), _fmin(fmin), _fmax(fmax), _device(device), _Fs(0), _plan(0), _spec(0), _outDev(0),
-      _onDevice(false), _inert(true) {}
-  void _kernel(Scalar *K) const {   // sinc_flt_kernel + FilterSource::_updateFilter (:18-28,186-203)
-    std::vector<Scalar> h(2 * _block);
-    design::fftFilterKernel(int(_block), _fmin, _fmax, _Fs, h.data());
-    design::fftFilterSpectrum(int(_block), h.data(), K);
-  }
+    : _block(block_size), _fmin(fmin), _fmax(fmax), _device(device), _Fs(0), _onDevice(false), _inert(true) {}
+  std::vector<Scalar> _kernel() const { return detail::fftFilterSpectrum<Scalar>(_block, _fmin, _fmax, _Fs); }
   size_t _block;
   double _fmin, _fmax;
   int _device;
   double _Fs;
-  sdrhip_fftsource *_plan;
-  void *_spec, *_outDev;
+  detail::Handle<sdrhip_fftsource, sdrhip_fftsource_destroy> _plan;
+  detail::DeviceMem _spec, _outDev;
   bool _onDevice, _inert;
   Buffer<CScalar> _buffer;
   std::vector<CScalar> _scratch;
 };
-
-template <class Scalar>
-bool FilterSink<Scalar>::_deviceHandoff() const {
-  if (_sinks.empty()) return false;
-  for (std::map<SinkBase *, bool>::const_iterator it = _sinks.begin(); it != _sinks.end(); ++it) {
-    const gpu::FilterSource<Scalar> *s = dynamic_cast<const gpu::FilterSource<Scalar> *>(it->first);
-    if (!it->second || !s || s->device() != _device) return false;
-  }
-  return true;
-}
 
 /** Drop-in for sdr::FilterNode<Scalar>, Scalar = float or double (reference src/filternode.hh:230-284), ANY block size
  * (:235: `FilterNode(size_t block_size=1024)`; FFTW plans any 2 x block_size): one launch per buffer where the transform
@@ -1254,9 +1164,8 @@ public:
     size_t _index;
   };
 
-  explicit FilterNode(size_t block_size = 1024, int device = 0) : _block(block_size), _device(device), _plan(0), _sink(this) {}
+  explicit FilterNode(size_t block_size = 1024, int device = 0) : _block(block_size), _device(device), _sink(this) {}
   virtual ~FilterNode() {
-    if (_plan) sdrhip_fftconv_destroy(_plan);
     for (size_t b = 0; b < _bands.size(); b++) delete _bands[b];
   }
 
@@ -1272,21 +1181,17 @@ public:
   }
 
 protected:
-  void _kernelOf(const Band *b, Scalar *K) const {   // sinc_flt_kernel + FilterSource::_updateFilter (:18-28,186-203)
-    std::vector<Scalar> h(2 * _block);
-    design::fftFilterKernel(int(_block), b->_fmin, b->_fmax, _cfg.sampleRate(), h.data());
-    design::fftFilterSpectrum(int(_block), h.data(), K);
-  }
+  std::vector<Scalar> _kernelOf(const Band *b) const { return detail::fftFilterSpectrum<Scalar>(_block, b->_fmin, b->_fmax, _cfg.sampleRate()); }
   /** ONE device plan for all bands: one upload and one forward FFT per input block feed every band
    * (FilterSink -> FilterSource fan-out, src/filternode.hh:81-88,257-270). */
   void _configure(const Config &cfg) {
     _cfg = cfg;
-    if (_plan) { sdrhip_fftconv_destroy(_plan); _plan = 0; }
+    _plan.reset();
     if (_bands.empty()) return;
-    std::vector<Scalar> K(4 * _block * _bands.size());
-    for (size_t b = 0; b < _bands.size(); b++) _kernelOf(_bands[b], K.data() + b * 4 * _block);
+    std::vector<Scalar> K;
+    for (size_t b = 0; b < _bands.size(); b++) { const std::vector<Scalar> k = _kernelOf(_bands[b]); K.insert(K.end(), k.begin(), k.end()); }
     detail::configCheck(detail::FftConvApi<Scalar>::create(Device::get(_device), int(2 * _block), K.data(), int(_bands.size()),
-                                                           cfg.bufferSize(), &_plan), "FFT filter");
+                                                           cfg.bufferSize(), _plan.out()), "FFT filter");
     _stage.resize(2 * cfg.bufferSize() * _bands.size());
     for (size_t b = 0; b < _bands.size(); b++) {
       _bands[b]->_buffer.unref();
@@ -1296,9 +1201,7 @@ protected:
   }
   void _bandChanged(size_t index) {
     if (!_plan) return;
-    std::vector<Scalar> K(4 * _block);
-    _kernelOf(_bands[index], K.data());
-    detail::configCheck(detail::FftConvApi<Scalar>::setKernel(_plan, int(index), K.data()), "FFT filter");
+    detail::configCheck(detail::FftConvApi<Scalar>::setKernel(_plan, int(index), _kernelOf(_bands[index]).data()), "FFT filter");
   }
   void _run(const Buffer<CScalar> &in) {
     if (!_plan || in.size() * 2 * _bands.size() > _stage.size()) return;
@@ -1319,11 +1222,7 @@ protected:
     explicit In(FilterNode *p) : _p(p) {}
     virtual void config(const Config &src_cfg) {
       if (Config::Type_UNDEFINED == src_cfg.type() || 0 == src_cfg.sampleRate() || 0 == src_cfg.bufferSize()) return;
-      if (Config::typeId<CScalar>() != src_cfg.type()) {
-        ConfigError err;
-        err << "Can not configure filter-sink: Invalid type " << src_cfg.type() << ", expected " << Config::typeId<CScalar>();
-        throw err;
-      }
+      detail::checkType<CScalar>(src_cfg, "filter-sink");
       _p->_configure(src_cfg);
     }
     virtual void process(const Buffer<CScalar> &buffer, bool) { _p->_run(buffer); }
@@ -1333,7 +1232,7 @@ protected:
   size_t _block;
   int _device;
   Config _cfg;
-  sdrhip_fftconv *_plan;
+  detail::Handle<sdrhip_fftconv, sdrhip_fftconv_destroy> _plan;
   In _sink;
   std::vector<Band *> _bands;
   std::vector<Scalar> _stage;
@@ -1363,15 +1262,12 @@ public:
   /** All channels share the band-select parameters (taps / LUT are read-only data, designed once on the host). */
   ChannelBank(size_t channels, double Fc, double Ff, double width, size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE,
               int device = 0)
-    : _C(channels), _Fc(Fc), _Ff(Ff), _width(width), _order(std::max(size_t(1), order)), _D(sub_sample), _epilogue(epilogue),
-      _devices(1, device), _comm(0), _gather(0), _bs(0), _have(0), _ins(channels, In(this)), _outs(channels), _pending(channels, false) {
-    for (size_t c = 0; c < _C; c++) _ins[c]._index = c;
-  }
+    : ChannelBank(channels, Fc, Ff, width, order, sub_sample, epilogue, std::vector<int>(1, device)) {}
   /** The same bank over several devices: rank r (device devices[r]) owns the r-th contiguous block of channels. */
   ChannelBank(size_t channels, double Fc, double Ff, double width, size_t order, size_t sub_sample, int epilogue,
               const std::vector<int> &devices)
     : _C(channels), _Fc(Fc), _Ff(Ff), _width(width), _order(std::max(size_t(1), order)), _D(sub_sample), _epilogue(epilogue),
-      _devices(devices.empty() ? std::vector<int>(1, 0) : devices), _comm(0), _gather(0), _bs(0), _have(0), _ins(channels, In(this)),
+      _devices(devices.empty() ? std::vector<int>(1, 0) : devices), _bs(0), _have(0), _ins(channels, In(this)),
       _outs(channels), _pending(channels, false) {
     for (size_t c = 0; c < _C; c++) _ins[c]._index = c;
   }
@@ -1397,67 +1293,55 @@ protected:
     size_t _index;
   };
   struct Rank {
-    sdrhip_ctx *ctx; sdrhip_iqbb_i16 *plan; size_t c0, c1; void *din, *dout;
-    Rank() : ctx(0), plan(0), c0(0), c1(0), din(0), dout(0) {}
+    sdrhip_ctx *ctx; detail::Handle<sdrhip_iqbb_i16, sdrhip_iqbb_i16_destroy> plan; size_t c0, c1; detail::DeviceMem din, dout;
+    Rank() : ctx(0), c0(0), c1(0) {}
   };
 
+  /** In this order: the ranks' contexts belong to the comm, which therefore goes last, after all work on them has ended. */
   void _release() {
     if (_comm) sdrhip_comm_synchronize(_comm);
-    for (size_t r = 0; r < _ranks.size(); r++) {
-      if (_ranks[r].plan) sdrhip_iqbb_i16_destroy(_ranks[r].plan);
-      if (_ranks[r].din) sdrhip_free(_ranks[r].ctx, _ranks[r].din);
-      if (_ranks[r].dout) sdrhip_free(_ranks[r].ctx, _ranks[r].dout);
-    }
-    if (_gather) sdrhip_free(_ranks[0].ctx, _gather);
-    _gather = 0;
+    for (size_t r = 0; r < _ranks.size(); r++) { _ranks[r].plan.reset(); _ranks[r].din.reset(); _ranks[r].dout.reset(); }
+    _gather.reset();
     _ranks.clear();
-    if (!_stageIn.isEmpty()) sdrhip_host_unregister(_stageIn.data());
-    if (!_stageOut.isEmpty()) sdrhip_host_unregister(_stageOut.data());
-    if (_comm) { sdrhip_comm_destroy(_comm); _comm = 0; }
+    _pinIn.reset();
+    _pinOut.reset();
+    _comm.reset();
   }
 
   void _config(const Config &cfg) {
     if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
-    if (Config::typeId<cs16>() != cfg.type()) {
-      ConfigError err;
-      err << "Can not configure ChannelBank: Invalid type " << cfg.type() << ", expected " << Config::typeId<cs16>();
-      throw err;
-    }
+    detail::checkType<cs16>(cfg, "ChannelBank");
     if (_comm && cfg == _cfg) return;   // every channel's source pushes the same Config
     _cfg = cfg;
     _bs = cfg.bufferSize();
     const int32_t Fs = int32_t(cfg.sampleRate());
-    std::vector<int32_t> taps(2 * _order), lut(2 * design::kLutSize);
-    design::iqbbTaps(_Ff, _width, Fs, _order, taps.data());
-    design::freqShiftLutI16(lut.data());
+    const std::vector<int32_t> taps = detail::iqbbTaps(_Ff, _width, Fs, _order), lut = detail::freqShiftLut();
     _release();
     _stageIn.unref(); _stageOut.unref();
     _outStride = _bs / _D + 2;
     _stageIn = Buffer<cs16>(_C * _bs);
     _stageOut = Buffer<cs16>(_C * _outStride);
-    detail::configCheck(sdrhip_host_register(_stageIn.data(), _C * _bs * sizeof(cs16)), "ChannelBank");
-    detail::configCheck(sdrhip_host_register(_stageOut.data(), _C * _outStride * sizeof(cs16)), "ChannelBank");
+    _pinIn.reset(_stageIn.data(), _C * _bs * sizeof(cs16), "ChannelBank");
+    _pinOut.reset(_stageOut.data(), _C * _outStride * sizeof(cs16), "ChannelBank");
     const size_t R = std::min(_devices.size(), _C);
-    detail::configCheck(sdrhip_comm_create(_devices.data(), int(R), &_comm), "ChannelBank");
-    _ranks.assign(R, Rank());
+    detail::configCheck(sdrhip_comm_create(_devices.data(), int(R), _comm.out()), "ChannelBank");
+    _ranks.resize(R);
     for (size_t r = 0; r < R; r++) {   // contiguous blocks, sizes differ by at most one
       Rank &k = _ranks[r];
       k.c0 = r * (_C / R) + std::min(r, _C % R);
       k.c1 = k.c0 + _C / R + (r < _C % R ? 1 : 0);
       detail::configCheck(sdrhip_comm_ctx(_comm, int(r), &k.ctx), "ChannelBank");
       detail::configCheck(sdrhip_iqbb_i16_create(k.ctx, taps.data(), int(_order), lut.data(), design::freqShiftIncrement(_Fc, double(Fs)),
-                                                 0 > _Fc, int(_D), int(k.c1 - k.c0), _bs, _epilogue, &k.plan), "ChannelBank");
-      detail::configCheck(sdrhip_malloc(k.ctx, (k.c1 - k.c0) * _bs * sizeof(cs16), &k.din), "ChannelBank");
-      detail::configCheck(sdrhip_malloc(k.ctx, (k.c1 - k.c0) * _outStride * sizeof(cs16), &k.dout), "ChannelBank");
+                                                 0 > _Fc, int(_D), int(k.c1 - k.c0), _bs, _epilogue, k.plan.out()), "ChannelBank");
+      k.din.alloc(k.ctx, (k.c1 - k.c0) * _bs * sizeof(cs16), "ChannelBank");
+      k.dout.alloc(k.ctx, (k.c1 - k.c0) * _outStride * sizeof(cs16), "ChannelBank");
     }
-    if (R > 1) detail::configCheck(sdrhip_malloc(_ranks[0].ctx, _C * _outStride * sizeof(cs16), &_gather), "ChannelBank");
+    if (R > 1) _gather.alloc(_ranks[0].ctx, _C * _outStride * sizeof(cs16), "ChannelBank");
     std::fill(_pending.begin(), _pending.end(), false);
     _chunkHave.assign((_C + kChunk - 1) / kChunk, 0);
     _copyOk = true;
     _have = 0;
-    const double oRate = double(size_t(Fs) / _D);
-    for (size_t c = 0; c < _C; c++)
-      _outs[c].configure(Config(_epilogue == SDRHIP_EPI_NONE ? Config::typeId<cs16>() : Config::typeId<int16_t>(), oRate, _outStride, 1));
+    for (size_t c = 0; c < _C; c++) _outs[c].configure(detail::bankOutConfig(_epilogue, Fs, _D, _outStride));
   }
 
   /** Collects one buffer per channel (all of the same length: buffer boundaries are part of the
@@ -1493,27 +1377,23 @@ protected:
       return;
     }
     size_t n = 0;
-    const size_t per = _epilogue == SDRHIP_EPI_NONE ? 1 : 2;   // int16 elements fit twice into a cs16 row
+    const size_t per = detail::fusedPer<cs16>(_epilogue);   // int16 elements fit twice into a cs16 row
     const size_t R = _ranks.size(), rowB = _outStride * sizeof(cs16);
     std::vector<const void *> send(R); std::vector<size_t> bytes(R);
     bool ok = _copyOk;
     for (size_t r = 0; r < R && ok; r++) {   // every rank: its batched launch behind its chunks' H2D copies (same stream), all asynchronous
       Rank &k = _ranks[r];
-      ok = detail::processOk(sdrhip_iqbb_i16_process_dev(k.plan, reinterpret_cast<const int16_t *>(k.din), _len, _bs, k.dout,
+      ok = detail::processOk(sdrhip_iqbb_i16_process_dev(k.plan, k.din.as<int16_t>(), _len, _bs, k.dout.get(),
                                                          _outStride * per, &n), "gpu::ChannelBank");
-      send[r] = k.dout; bytes[r] = (k.c1 - k.c0) * rowB;
+      send[r] = k.dout.get(); bytes[r] = (k.c1 - k.c0) * rowB;
     }
     if (ok && R > 1)   // rows gathered on rank 0's device in channel order (RCCL over xGMI), then one copy to the host
-      ok = detail::processOk(sdrhip_comm_gather(_comm, send.data(), bytes.data(), _gather, 0), "gpu::ChannelBank") &&
-           detail::processOk(sdrhip_memcpy_d2h_async(_ranks[0].ctx, _stageOut.data(), _gather, _C * rowB), "gpu::ChannelBank");
+      ok = detail::processOk(sdrhip_comm_gather(_comm, send.data(), bytes.data(), _gather.get(), 0), "gpu::ChannelBank") &&
+           detail::processOk(sdrhip_memcpy_d2h_async(_ranks[0].ctx, _stageOut.data(), _gather.get(), _C * rowB), "gpu::ChannelBank");
     else if (ok)
-      ok = detail::processOk(sdrhip_memcpy_d2h_async(_ranks[0].ctx, _stageOut.data(), _ranks[0].dout, _C * rowB), "gpu::ChannelBank");
+      ok = detail::processOk(sdrhip_memcpy_d2h_async(_ranks[0].ctx, _stageOut.data(), _ranks[0].dout.get(), _C * rowB), "gpu::ChannelBank");
     if (!detail::processOk(sdrhip_comm_synchronize(_comm), "gpu::ChannelBank") || !ok) return;
-    for (size_t ch = 0; ch < _C; ch++) {
-      if (_epilogue == SDRHIP_EPI_NONE) _outs[ch].emit(_stageOut.sub(ch * _outStride, n), false);
-      else if (!(_epilogue == SDRHIP_EPI_FM && n == 0))
-        _outs[ch].emit(Buffer<int16_t>(_stageOut).sub(ch * _outStride * 2, n), false);
-    }
+    for (size_t ch = 0; ch < _C; ch++) detail::sendDemodulated(_outs[ch], _epilogue, _stageOut, ch * _outStride, n, false);
   }
 
   /** H2D copy of the channels [k * kChunk, (k + 1) * kChunk) of the round being collected: each rank's part on that rank's stream. */
@@ -1523,7 +1403,7 @@ protected:
       Rank &rk = _ranks[r];
       const size_t lo = std::max(a, rk.c0), hi = std::min(b, rk.c1);
       if (lo >= hi) continue;
-      if (!detail::processOk(sdrhip_memcpy_h2d_async(rk.ctx, static_cast<char *>(rk.din) + (lo - rk.c0) * _bs * sizeof(cs16),
+      if (!detail::processOk(sdrhip_memcpy_h2d_async(rk.ctx, rk.din.as<char>() + (lo - rk.c0) * _bs * sizeof(cs16),
                                                      _stageIn.data() + lo * _bs * sizeof(cs16), (hi - lo) * _bs * sizeof(cs16)), "gpu::ChannelBank"))
         _copyOk = false;
     }
@@ -1537,9 +1417,10 @@ protected:
   size_t _order, _D;
   int _epilogue;
   std::vector<int> _devices;
-  sdrhip_comm *_comm;
+  detail::Handle<sdrhip_comm, sdrhip_comm_destroy> _comm;
   std::vector<Rank> _ranks;
-  void *_gather;
+  detail::DeviceMem _gather;
+  detail::Pinned _pinIn, _pinOut;   // the registrations of _stageIn and _stageOut
   Config _cfg;
   size_t _bs, _have, _len, _outStride;
   std::vector<In> _ins;
@@ -1571,8 +1452,8 @@ public:
   enum { PerChannel = -1 };
 
   TunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
-    : _order(std::max(size_t(1), order)), _D(std::max(size_t(1), sub_sample)), _epilogue(epilogue), _device(device), _ctx(0), _plan(0),
-      _din(0), _dout(0), _bs(0), _outStride(0), _Fs(0) {}
+    : _order(std::max(size_t(1), order)), _D(std::max(size_t(1), sub_sample)), _epilogue(epilogue), _device(device), _ctx(0),
+      _bs(0), _outStride(0), _Fs(0) {}
   virtual ~TunerBank() {
     _release();
     for (size_t c = 0; c < _outs.size(); c++) delete _outs[c];
@@ -1620,11 +1501,7 @@ public:
 
   virtual void config(const Config &cfg) {
     if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
-    if (Config::typeId<cs16>() != cfg.type()) {
-      ConfigError err;
-      err << "Can not configure TunerBank: Invalid type " << cfg.type() << ", expected " << Config::typeId<cs16>();
-      throw err;
-    }
+    detail::checkType<cs16>(cfg, "TunerBank");
     _bs = cfg.bufferSize();
     _Fs = int32_t(cfg.sampleRate());
     _rebuild();
@@ -1640,19 +1517,15 @@ public:
       Logger::get().log(msg);
       return;
     }
-    const size_t C = _tunes.size(), per = _epilogue == SDRHIP_EPI_NONE ? 1 : 2;   // int16 elements fit twice into a cs16 row
+    const size_t C = _tunes.size(), per = detail::fusedPer<cs16>(_epilogue);   // int16 elements fit twice into a cs16 row
     size_t n = 0;
     if (b.size() == 0) return;
-    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din, b.data(), b.size() * sizeof(cs16)), "gpu::TunerBank") ||
-        !detail::processOk(sdrhip_tuner_i16_process_dev(_plan, _din, b.size(), _dout, _outStride * per, &n), "gpu::TunerBank") ||
-        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout, C * _outStride * sizeof(cs16)), "gpu::TunerBank") ||
+    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din.get(), b.data(), b.size() * sizeof(cs16)), "gpu::TunerBank") ||
+        !detail::processOk(sdrhip_tuner_i16_process_dev(_plan, _din.get(), b.size(), _dout.get(), _outStride * per, &n), "gpu::TunerBank") ||
+        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout.get(), C * _outStride * sizeof(cs16)), "gpu::TunerBank") ||
         !detail::processOk(sdrhip_ctx_synchronize(_ctx), "gpu::TunerBank"))
       return;
-    for (size_t ch = 0; ch < C; ch++) {
-      if (_epilogue == SDRHIP_EPI_NONE) _outs[ch]->emit(_stageOut.sub(ch * _outStride, n), false);
-      else if (!(_modes[ch] == SDRHIP_EPI_FM && n == 0))   // (FMDemod does not send on an empty buffer)
-        _outs[ch]->emit(Buffer<int16_t>(_stageOut).sub(ch * _outStride * 2, n), false);
-    }
+    for (size_t ch = 0; ch < C; ch++) detail::sendDemodulated(*_outs[ch], _modes[ch], _stageOut, ch * _outStride, n, false);
   }
 
 protected:
@@ -1674,18 +1547,17 @@ protected:
 
   void _retap(size_t c) {
     if (!_plan) return;
-    std::vector<int32_t> taps(2 * _order);
-    design::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data());
-    detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), taps.data()), "TunerBank");
+    detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), detail::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order).data()), "TunerBank");
   }
 
+  /** In this order: the device is idle before anything it may still use goes. */
   void _release() {
     if (_ctx) sdrhip_ctx_synchronize(_ctx);
-    if (_plan) sdrhip_tuner_i16_destroy(_plan);
-    if (_din) sdrhip_free(_ctx, _din);
-    if (_dout) sdrhip_free(_ctx, _dout);
-    _plan = 0; _din = 0; _dout = 0;
-    if (!_stageOut.isEmpty()) { sdrhip_host_unregister(_stageOut.data()); _stageOut.unref(); }
+    _plan.reset();
+    _din.reset();
+    _dout.reset();
+    _pinOut.reset();
+    _stageOut.unref();
   }
 
   void _rebuild() {
@@ -1693,7 +1565,8 @@ protected:
     const size_t C = _tunes.size();
     if (C == 0 || _bs == 0) return;
     _ctx = Device::get(_device);
-    std::vector<int32_t> taps(C * 2 * _order), lut(2 * design::kLutSize);
+    std::vector<int32_t> taps(C * 2 * _order);
+    const std::vector<int32_t> lut = detail::freqShiftLut();
     std::vector<uint32_t> inc(C);
     std::vector<int> neg(C);
     for (size_t c = 0; c < C; c++) {
@@ -1701,28 +1574,26 @@ protected:
       inc[c] = design::freqShiftIncrement(_tunes[c].shift, double(_Fs));
       neg[c] = 0 > _tunes[c].shift;
     }
-    design::freqShiftLutI16(lut.data());
     _outStride = (_bs + _D - 1) / _D + 1;
     if (perChannel())
       detail::configCheck(sdrhip_tunermodes_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), _modes.data(),
-                                                       int(_D), int(C), _bs, &_plan), "TunerBank");
+                                                       int(_D), int(C), _bs, _plan.out()), "TunerBank");
     else
       detail::configCheck(sdrhip_tuner_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), int(_D), int(C), _bs,
-                                                  _epilogue, &_plan), "TunerBank");
-    detail::configCheck(sdrhip_malloc(_ctx, _bs * sizeof(cs16), &_din), "TunerBank");
-    detail::configCheck(sdrhip_malloc(_ctx, C * _outStride * sizeof(cs16), &_dout), "TunerBank");
+                                                  _epilogue, _plan.out()), "TunerBank");
+    _din.alloc(_ctx, _bs * sizeof(cs16), "TunerBank");
+    _dout.alloc(_ctx, C * _outStride * sizeof(cs16), "TunerBank");
     _stageOut = Buffer<cs16>(C * _outStride);
-    detail::configCheck(sdrhip_host_register(_stageOut.data(), C * _outStride * sizeof(cs16)), "TunerBank");
-    const double oRate = double(size_t(_Fs) / _D);
-    for (size_t c = 0; c < C; c++)
-      _outs[c]->configure(Config(_epilogue == SDRHIP_EPI_NONE ? Config::typeId<cs16>() : Config::typeId<int16_t>(), oRate, _outStride, 1));
+    _pinOut.reset(_stageOut.data(), C * _outStride * sizeof(cs16), "TunerBank");
+    for (size_t c = 0; c < C; c++) _outs[c]->configure(detail::bankOutConfig(_epilogue, _Fs, _D, _outStride));
   }
 
   size_t _order, _D;
   int _epilogue, _device;
   sdrhip_ctx *_ctx;
-  sdrhip_tuner_i16 *_plan;
-  void *_din, *_dout;
+  detail::Handle<sdrhip_tuner_i16, sdrhip_tuner_i16_destroy> _plan;
+  detail::DeviceMem _din, _dout;
+  detail::Pinned _pinOut;   // the registration of _stageOut
   size_t _bs, _outStride;
   int32_t _Fs;
   std::vector<Tune> _tunes;
@@ -1758,7 +1629,7 @@ template <class Scalar>
 class FFTPlan {
 public:
   FFTPlan(const Buffer< std::complex<Scalar> > &in, const Buffer< std::complex<Scalar> > &out, FFT::Direction dir, int device = 0)
-    : _in(in), _out(out), _sign(dir == FFT::BACKWARD ? 1 : -1), _device(device), _plan(0) {
+    : _in(in), _out(out), _sign(dir == FFT::BACKWARD ? 1 : -1), _device(device) {
     if (in.size() != out.size()) {
       ConfigError err;
       err << "Can not construct FFT plan: input & output buffers are of different size!";
@@ -1772,7 +1643,7 @@ public:
     _make();
   }
   FFTPlan(const Buffer< std::complex<Scalar> > &inplace, FFT::Direction dir, int device = 0)
-    : _in(inplace), _out(inplace), _sign(dir == FFT::BACKWARD ? 1 : -1), _device(device), _plan(0) {
+    : _in(inplace), _out(inplace), _sign(dir == FFT::BACKWARD ? 1 : -1), _device(device) {
     if (inplace.isEmpty()) {
       ConfigError err;
       err << "Can not construct FFT plan: Buffer is empty!";
@@ -1780,7 +1651,7 @@ public:
     }
     _make();
   }
-  virtual ~FFTPlan() { if (_plan) sdrhip_fft_plan_destroy(_plan); }
+  virtual ~FFTPlan() {}
   /** Performs the transformation. */
   void operator() () {
     detail::configCheck(sdrhip_fft_plan_exec(_plan, _sign, _in.data(), _out.data()), "FFT plan");
@@ -1789,22 +1660,17 @@ public:
   const char *form() const { const char *s = ""; sdrhip_fft_plan_form(_plan, &s); return s; }
 
 protected:
-  static int _dtype() { return sizeof(Scalar) == 8 ? SDRHIP_T_CF64 : SDRHIP_T_CF32; }
   void _make() {
     if (_in.size() > (size_t(1) << 27)) {
       ConfigError err;
       err << "Can not construct FFT plan: " << _in.size() << " points exceed the device plans (2^27)";
       throw err;
     }
-    detail::configCheck(sdrhip_fft_plan_create(Device::get(_device), _dtype(), int(_in.size()), &_plan), "FFT plan");
+    detail::configCheck(sdrhip_fft_plan_create(Device::get(_device), detail::TypeTag< std::complex<Scalar> >::dtype, int(_in.size()), _plan.out()), "FFT plan");
   }
   Buffer< std::complex<Scalar> > _in, _out;
   int _sign, _device;
-  sdrhip_fft_plan *_plan;
-
-private:
-  FFTPlan(const FFTPlan &);              // (owns a device plan)
-  FFTPlan &operator=(const FFTPlan &);
+  detail::Handle<sdrhip_fft_plan, sdrhip_fft_plan_destroy> _plan;
 };
 
 }  // namespace gpu

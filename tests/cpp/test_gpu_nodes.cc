@@ -5,7 +5,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <iostream>
+#include <sstream>
 #include <vector>
 
 #include "sdr/sdr.hh"
@@ -443,6 +445,32 @@ static void testRealBaseBand() {
   CHECK(thrown);
 }
 
+// BaseBand<int16_t> with FM / AM / USB fused into its launch against the same node followed by the gpu demodulator node
+// (direct edge, in place over the baseband's buffer); the unfused baseband is pinned to the reference by testRealBaseBand
+static void testRealBaseBandFused() {
+  std::vector<int16_t> x = slurp<int16_t>("g10_real_in.bin");
+  CHECK(x.size() == 3 * 4096);
+  struct S16Feeder : public Source { void cfg() { setConfig(Config(Config::Type_s16, 1e6, 4096, 1)); }
+                                     void feed(int16_t *p, size_t n) { Buffer<int16_t> b(p, n); send(b, false); } };
+  const int modes[3] = {SDRHIP_EPI_FM, SDRHIP_EPI_AM, SDRHIP_EPI_USB};
+  for (int m = 0; m < 3; m++) {
+    S16Feeder a, b; a.cfg(); b.cfg();
+    gpu::BaseBand<int16_t> fused(100e3, 100e3, 50e3, 21, 8), plain(100e3, 100e3, 50e3, 21, 8);
+    fused.setDemod(modes[m]);
+    gpu::FMDemod<int16_t> fm; gpu::AMDemod<int16_t> am; gpu::USBDemod<int16_t> usb;
+    Recorder<int16_t> got, want;
+    a.connect(&fused, true); fused.connect(&got, true);
+    b.connect(&plain, true);
+    if (modes[m] == SDRHIP_EPI_FM) { plain.connect(&fm, true); fm.connect(&want, true); }
+    else if (modes[m] == SDRHIP_EPI_AM) { plain.connect(&am, true); am.connect(&want, true); }
+    else { plain.connect(&usb, true); usb.connect(&want, true); }
+    CHECK(fused.type() == Config::Type_s16 && fused.Source::sampleRate() == 125000.0);
+    for (int k = 0; k < 3; k++) { a.feed(&x[k * 4096], 4096); b.feed(&x[k * 4096], 4096); }
+    if (got.data != want.data) std::printf("  fused BaseBand, mode %d: %zu samples, unfused %zu\n", modes[m], got.data.size(), want.data.size());
+    CHECK(want.data.size() == 3 * 512 && got.data == want.data && got.lens == want.lens);
+  }
+}
+
 // the real-input node retuned and reconfigured between buffers (golden g16: setFrequencyShift, then a new source buffer size)
 static void testRealBaseBandRetune() {
   std::vector<int16_t> x = slurp<int16_t>("g10_real_in.bin"), ref = slurp<int16_t>("g16_bb_real_retune_out.bin");
@@ -717,14 +745,33 @@ static void testFilterNodeAnySizeAndDouble() {
 // src/firfilter.hh:172-207, src/demod.hh:195-226): silent return while the upstream Config is incomplete, ConfigError on
 // a type mismatch; with a complete Config either the plan is made (a GPU is present) or a ConfigError says that there
 // is no device and no CPU fallback — never a crash, and every node destructs cleanly either way.
-template <class Node> static void hostConfigRules(Node &n, Config::Type good, Config::Type bad, const char *what) {
-  n.config(Config());                                  // nothing known yet: silent
-  n.config(Config(good, 0, 0, 1));                     // type only: still silent
-  bool threw = false;
-  try { n.config(Config(bad, FS, 4096, 1)); } catch (ConfigError &) { threw = true; }
-  if (!threw) std::printf("  %s accepted a wrong input type\n", what);
-  CHECK(threw);
-  try { n.config(Config(good, FS, 4096, 1)); } catch (ConfigError &e) { (void)e; }   // no device here: a ConfigError, not a crash
+enum { kType = 1, kRate = 2, kBs = 4 };   // the fields a node's config() waits for (its guard set)
+static std::string typeError(const char *head, Config::Type got, Config::Type shown) {
+  std::ostringstream s; s << head << got << ", expected " << shown; return s.str();
+}
+template <class Node> static void expectConfigError(Node &n, const Config &cfg, const std::string &text, const char *what) {
+  std::string got = "(no ConfigError)";
+  try { n.config(cfg); } catch (ConfigError &e) { got = e.what(); }
+  if (got != text) std::printf("  %s: ConfigError text\n    got  \"%s\"\n    want \"%s\"\n", what, got.c_str(), text.c_str());
+  CHECK(got == text);
+}
+/** `needs`: the node's guard set; every Config that lacks one of those fields is silent, even with the wrong type (the guard
+ * comes first). `error`: the whole ConfigError text for Config(bad, rate, 4096, 1). */
+template <class Node> static void hostConfigRules(Node &n, Config::Type good, Config::Type bad, const char *what, int needs,
+                                                  const std::string &error, double rate = FS) {
+  bool silent = true;
+  try {
+    n.config(Config());                                  // nothing known yet: silent
+    if (needs & kType) n.config(Config(Config::Type_UNDEFINED, rate, 4096, 1));
+    for (Config::Type t : {good, bad}) {
+      if (needs & kRate) n.config(Config(t, 0, 4096, 1));
+      if (needs & kBs) n.config(Config(t, rate, 0, 1));
+      if ((needs & kRate) && (needs & kBs)) n.config(Config(t, 0, 0, 1));   // type only: still silent
+    }
+  } catch (ConfigError &e) { silent = false; std::printf("  %s threw on an incomplete Config: %s\n", what, e.what()); }
+  CHECK(silent);
+  expectConfigError(n, Config(bad, rate, 4096, 1), error, what);
+  try { n.config(Config(good, rate, 4096, 1)); } catch (ConfigError &e) { (void)e; }   // no device here: a ConfigError, not a crash
 }
 static void testHostOnly() {
   std::vector<int32_t> taps(254), lut(256);
@@ -738,17 +785,85 @@ static void testHostOnly() {
     gpu::design::firLowPass(order, 100e3, FS, a.data());
     CHECK(a == slurp<double>("g2_firlp_alpha" + std::to_string(order) + ".bin"));
   }
-  { gpu::IQBaseBand<int16_t> n(100e3, 100e3, 50e3, 127, 8); hostConfigRules(n, Config::Type_cs16, Config::Type_cf32, "IQBaseBand<int16_t>"); }
-  { gpu::IQBaseBand<float> n(100e3, 200e3, 127, 8); hostConfigRules(n, Config::Type_cf32, Config::Type_cs16, "IQBaseBand<float>"); }
-  { gpu::IQBaseBand<uint8_t> n(100e3, 100e3, 50e3, 21, 8); hostConfigRules(n, Config::Type_cu8, Config::Type_cs16, "IQBaseBand<uint8_t>"); }
-  { gpu::BaseBand<int16_t> n(100e3, 100e3, 50e3, 64, 8); hostConfigRules(n, Config::Type_s16, Config::Type_cs16, "BaseBand<int16_t>"); }
-  { gpu::FIRLowPass<cs16> n(127, 100e3); hostConfigRules(n, Config::Type_cs16, Config::Type_s16, "FIRLowPass<cs16>"); }
-  { gpu::FIRLowPass<cf32> n(127, 100e3); hostConfigRules(n, Config::Type_cf32, Config::Type_cs16, "FIRLowPass<cf32>"); }
-  { gpu::FMDemod<int16_t> n; hostConfigRules(n, Config::Type_cs16, Config::Type_cf32, "FMDemod<int16_t>"); }
-  { gpu::AMDemod<int16_t> n; hostConfigRules(n, Config::Type_cs16, Config::Type_cf32, "AMDemod<int16_t>"); }
-  { gpu::USBDemod<float> n; hostConfigRules(n, Config::Type_cf32, Config::Type_cs16, "USBDemod<float>"); }
-  { gpu::SubSample<cs16> n(size_t(8)); hostConfigRules(n, Config::Type_cs16, Config::Type_cf32, "SubSample<cs16>"); }
-  { gpu::FMDeemph<int16_t> n; hostConfigRules(n, Config::Type_s16, Config::Type_cs16, "FMDeemph<int16_t>"); }
+  const Config::Type s16 = Config::Type_s16, c16 = Config::Type_cs16, c32 = Config::Type_cf32, cu8 = Config::Type_cu8,
+                     cs8 = Config::Type_cs8, u8 = Config::Type_u8;
+  const int all = kType | kRate | kBs;
+  { gpu::IQBaseBand<int16_t> n(100e3, 100e3, 50e3, 127, 8);
+    hostConfigRules(n, c16, c32, "IQBaseBand<int16_t>", all, typeError("Can not configure IQBaseBand: Invalid type ", c32, c16)); }
+  { gpu::IQBaseBand<float> n(100e3, 200e3, 127, 8);
+    hostConfigRules(n, c32, c16, "IQBaseBand<float>", all, typeError("Can not configure IQBaseBand: Invalid type ", c16, c32)); }
+  { gpu::IQBaseBand<uint8_t> n(100e3, 100e3, 50e3, 21, 8);
+    hostConfigRules(n, cu8, c16, "IQBaseBand<uint8_t>", all, typeError("Can not configure IQBaseBand: Invalid type ", c16, cu8)); }
+  { gpu::IQBaseBand<int8_t> n(100e3, 100e3, 50e3, 21, 8);
+    hostConfigRules(n, cs8, c16, "IQBaseBand<int8_t>", all, typeError("Can not configure IQBaseBand: Invalid type ", c16, cs8)); }
+  { gpu::BaseBand<int16_t> n(100e3, 100e3, 50e3, 64, 8);
+    hostConfigRules(n, s16, c16, "BaseBand<int16_t>", all, typeError("Can not configure BaseBand: Invalid type ", c16, s16)); }
+  { gpu::FIRLowPass<cs16> n(127, 100e3);
+    hostConfigRules(n, c16, s16, "FIRLowPass<cs16>", all, typeError("Can not configure FIRLowPass: Invalid type ", s16, c16)); }
+  { gpu::FIRLowPass<cf32> n(127, 100e3);
+    hostConfigRules(n, c32, c16, "FIRLowPass<cf32>", all, typeError("Can not configure FIRLowPass: Invalid type ", c16, c32)); }
+  { gpu::FMDemod<int16_t> n;
+    hostConfigRules(n, c16, c32, "FMDemod<int16_t>", kType | kBs, typeError("Can not configure FMDemod: Invalid type ", c32, c16)); }
+  { gpu::FMDemod<int8_t, int16_t> n;
+    hostConfigRules(n, cs8, c16, "FMDemod<int8_t,int16_t>", kType | kBs, typeError("Can not configure FMDemod: Invalid type ", c16, cs8)); }
+  { gpu::AMDemod<int16_t> n;
+    hostConfigRules(n, c16, c32, "AMDemod<int16_t>", kType | kBs, typeError("Can not configure AMDemod: Invalid type ", c32, c16)); }
+  { gpu::USBDemod<float> n;
+    hostConfigRules(n, c32, c16, "USBDemod<float>", kType | kBs, typeError("Can not configure USBDemod: Invalid type ", c16, c32)); }
+  { gpu::SubSample<cs16> n(size_t(8));
+    hostConfigRules(n, c16, c32, "SubSample<cs16>", kType | kBs,
+                    typeError("Can not configure SubSample node: Invalid buffer type ", c32, c16)); }
+  { gpu::FMDeemph<int16_t> n;
+    hostConfigRules(n, s16, c16, "FMDeemph<int16_t>", all, typeError("Can not configure FMDeemph: Invalid type ", c16, s16)); }
+  // audio to bits, at an audio rate; BitStream compares with uint8_t and names int16_t (reference src/fsk.cc:116)
+  { gpu::BitStream n(1200.0f);
+    hostConfigRules(n, u8, s16, "BitStream", kType | kRate, typeError("Can not configure BitStream: Invalid type ", s16, s16), 22050.0); }
+  { gpu::FSKDetector n(1200.0f, 1200.0f, 2200.0f);
+    hostConfigRules(n, s16, c16, "FSKDetector", kType | kRate, typeError("Can not configure FSKBase: Invalid type ", c16, s16), 22050.0); }
+  { gpu::ASKDetector<int16_t> n;
+    hostConfigRules(n, s16, c16, "ASKDetector<int16_t>", kType | kRate,
+                    typeError("Can not configure ASKDetector: Invalid type ", c16, s16), 22050.0); }
+  // the split FFT filter: FilterSink and FilterNode's input share a text; FilterSource checks the block size only
+  { gpu::FilterSink<float> n(4096);
+    hostConfigRules(n, c32, c16, "FilterSink<float>", all, typeError("Can not configure filter-sink: Invalid type ", c16, c32));
+    gpu::FilterSink<float> m(1024);
+    expectConfigError(m, Config(c32, FS, 4096, 1), "Can not configure filter-sink: Invalid buffer size 4096, expected 1024",
+                      "FilterSink<float>(1024)"); }
+  { gpu::FilterSource<float> n(1024, 10e3, 50e3);
+    hostConfigRules(n, c32, c16, "FilterSource<float>", kRate | kBs,
+                    "Can not configure FilterSource, block-size (=1024) != buffer-size (=4096)!");
+    expectConfigError(n, Config(c32, FS, 4096, 1), "Can not configure FilterSource, block-size (=1024) != buffer-size (=4096)!",
+                      "FilterSource<float>"); }
+  { gpu::FilterNode<float> bank(1024); bank.addFilter(10e3, 50e3);
+    hostConfigRules(*bank.sink(), c32, c16, "FilterNode<float>::sink()", all,
+                    typeError("Can not configure filter-sink: Invalid type ", c16, c32)); }
+  { gpu::ChannelBank<int16_t> bank(2, 100e3, 100e3, 50e3, 127, 8);
+    hostConfigRules(*bank.sink(0), c16, c32, "ChannelBank<int16_t>::sink(0)", all,
+                    typeError("Can not configure ChannelBank: Invalid type ", c32, c16)); }
+  { gpu::TunerBank<int16_t> bank(127, 8); bank.addChannel(100e3, 100e3, 50e3);
+    hostConfigRules(bank, c16, c32, "TunerBank<int16_t>", all, typeError("Can not configure TunerBank: Invalid type ", c32, c16)); }
+  {   // TunerBank's modes before config(): a mode the bank cannot have is a ConfigError; the bank's own mode is accepted silently
+    std::string got;
+    gpu::TunerBank<int16_t> per(21, 8, gpu::TunerBank<int16_t>::PerChannel);
+    try { per.addChannel(100e3, 100e3, 50e3, SDRHIP_EPI_NONE); } catch (ConfigError &e) { got = e.what(); }
+    CHECK(got == "TunerBank: mode " + std::to_string(int(SDRHIP_EPI_NONE)) + " is none of SDRHIP_EPI_FM, SDRHIP_EPI_AM, SDRHIP_EPI_USB");
+    CHECK(per.channels() == 0 && per.addChannel(100e3, 100e3, 50e3) == 0 && per.mode(0) == SDRHIP_EPI_FM);
+    per.setMode(0, SDRHIP_EPI_USB); CHECK(per.mode(0) == SDRHIP_EPI_USB);
+    gpu::TunerBank<int16_t> fm(21, 8, SDRHIP_EPI_FM); fm.addChannel(100e3, 100e3, 50e3);
+    got.clear();
+    try { fm.setMode(0, SDRHIP_EPI_AM); } catch (ConfigError &e) { got = e.what(); }
+    CHECK(got == "TunerBank: mode " + std::to_string(int(SDRHIP_EPI_AM)) + " in a bank whose channels all have the demodulator " +
+                 std::to_string(int(SDRHIP_EPI_FM)));
+    got.clear();
+    try { fm.setMode(0, SDRHIP_EPI_FM); } catch (ConfigError &e) { got = e.what(); }
+    CHECK(got.empty() && fm.mode(0) == SDRHIP_EPI_FM);
+  }
+  {   // IQBaseBand<float> not configured yet: a filter frequency off the centre is only recorded (it is refused at config())
+    gpu::IQBaseBand<float> n(100e3, 200e3, 127, 8);
+    bool threw = false;
+    try { n.setFilterFrequency(120e3); } catch (ConfigError &) { threw = true; }
+    CHECK(!threw && n.filterFrequency() == 120e3 && n.centerFrequency() == 100e3);
+  }
   {   // the designers' own DFT (the spectrum of a FilterNode kernel, any 2N): composite, small-prime and large-prime lengths
       // (a large prime runs the chirp transform) against the direct sum, both signs; the f64 golden spectrum of N = 1000
     for (size_t n : {12u, 61u, 2018u, 20014u}) {
@@ -771,6 +886,14 @@ static void testHostOnly() {
       }
     }
   }
+  // a node owns its device plan, device memory and pinned registrations: none can be copied (a copy would free them twice)
+  static_assert(!std::is_copy_constructible< gpu::FMDemod<int16_t> >::value && !std::is_copy_constructible< gpu::IQBaseBand<int16_t> >::value &&
+                !std::is_copy_constructible< gpu::BaseBand<int16_t> >::value && !std::is_copy_constructible< gpu::FFTPlan<float> >::value,
+                "a node with a device plan is not copyable");
+  static_assert(!std::is_copy_constructible<gpu::BitStream>::value && !std::is_copy_constructible< gpu::FilterSink<float> >::value,
+                "a node with device memory is not copyable");
+  static_assert(!std::is_copy_constructible< gpu::ChannelBank<int16_t> >::value && !std::is_copy_constructible< gpu::TunerBank<int16_t> >::value,
+                "a bank with pinned staging buffers is not copyable");
   {   // buffers and views as the nodes hand them on (ownership rules of src/buffer.hh:54-104)
     Buffer<cs16> b(64); CHECK(b.isUnused());
     Buffer<cs16> v = b.head(10); b.ref(); CHECK(!b.isUnused() && v.size() == 10); b.unref(); CHECK(b.isUnused());
@@ -802,6 +925,7 @@ int main(int argc, char **argv) {
     testFloatBaseBandNode();
     testSdrFmChainCu8();
     testRealBaseBand();
+    testRealBaseBandFused();
     testRealBaseBandRetune();
     testRetuneMidStream();
     testRegeometryMidStream();
