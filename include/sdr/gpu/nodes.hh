@@ -1434,27 +1434,51 @@ protected:
 // =================================================================================================
 template <class Scalar> class TunerBank;
 
-/** Several IQBaseBand<int16_t> nodes connected to one source, as one node: a Sink<cs16> with one Source per channel
- * (source(c), the ChannelBank::Out pattern). Every channel has its own centre frequency, filter frequency and width;
- * order, sub-sampling and the fused demodulator are the bank's. Per buffer: one H2D copy, one launch for all channels
- * (sdrhip_tuner_i16_*), one D2H copy of all rows into a pinned staging buffer, then one send per channel, in channel
- * order, as views of it. addChannel() after config() rebuilds the device plan: every channel restarts as a freshly
- * configured node (FIR history, decimator and LUT phases at zero).
- * With epilogue = TunerBank::PerChannel every channel has a demodulator of its own (SDRHIP_EPI_FM | _AM | _USB: the modes of
- * the reference's receiver, examples/sdr_rec.cc:44-110, on one antenna), still in one launch; setMode() replaces the
- * demodulator node behind ONE channel's baseband, which goes on as it is (sdrhip_tunermodes_i16_set_mode). Every output's Config
- * is int16_t at the decimated rate, whatever the modes are. */
-template <>
-class TunerBank<int16_t> : public Sink<cs16> {
+namespace detail {
+/** What the two kinds of bank differ in: the sample type, how the node keeps its frequencies and derives its output rate
+ * (IQBaseBand: int32 members, truncated, and the integer quotient, src/baseband.hh:266-272; the real-input BaseBand: doubles
+ * and the double quotient, :357-395,520-526), the tap design and the create calls. */
+struct ComplexBank {
+  typedef cs16 In;
+  typedef int32_t Freq;
+  static const char *name() { return "TunerBank"; }
+  static const char *gname() { return "gpu::TunerBank"; }
+  static double outRate(Freq Fs, size_t D) { return double(size_t(Fs) / D); }
+  static void taps(double Ff, double width, double Fs, size_t order, int32_t *dst) { design::iqbbTaps(Ff, width, Fs, order, dst); }
+  static int create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *inc, const int *neg, const int *modes,
+                    int D, int C, size_t bs, int epilogue, sdrhip_tuner_i16 **out) {
+    return modes ? sdrhip_tunermodes_i16_create(ctx, taps, order, lut, inc, neg, modes, D, C, bs, out)
+                 : sdrhip_tuner_i16_create(ctx, taps, order, lut, inc, neg, D, C, bs, epilogue, out);
+  }
+};
+struct RealBank {
+  typedef int16_t In;
+  typedef double Freq;
+  static const char *name() { return "RealTunerBank"; }
+  static const char *gname() { return "gpu::RealTunerBank"; }
+  static double outRate(Freq Fs, size_t D) { return Fs / double(D); }
+  static void taps(double Ff, double width, double Fs, size_t order, int32_t *dst) { design::bbTaps(Ff, width, Fs, order, dst); }
+  static int create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *inc, const int *neg, const int *modes,
+                    int D, int C, size_t bs, int epilogue, sdrhip_tuner_i16 **out) {
+    return modes ? sdrhip_tunermodes_bb_i16_create(ctx, taps, order, lut, inc, neg, modes, D, C, bs, out)
+                 : sdrhip_tunerbb_i16_create(ctx, taps, order, lut, inc, neg, D, C, bs, epilogue, out);
+  }
+};
+
+/** The node both kinds of bank are (TunerBank<int16_t> and RealTunerBank<int16_t> below say what it does). */
+template <class K>
+class TunerBank16 : public Sink<typename K::In> {
 public:
+  typedef typename K::In In;
+  typedef typename K::Freq Freq;
   typedef ChannelBank<int16_t>::Out Out;
   /** The constructor's `epilogue` of a bank with a demodulator per channel. */
   enum { PerChannel = -1 };
 
-  TunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
+  TunerBank16(size_t order, size_t sub_sample, int epilogue, int device)
     : _order(std::max(size_t(1), order)), _D(std::max(size_t(1), sub_sample)), _epilogue(epilogue), _device(device), _ctx(0),
       _bs(0), _outStride(0), _Fs(0) {}
-  virtual ~TunerBank() {
+  virtual ~TunerBank16() {
     _release();
     for (size_t c = 0; c < _outs.size(); c++) delete _outs[c];
   }
@@ -1482,7 +1506,7 @@ public:
   void setMode(size_t c, int mode) {
     _checkMode(mode);
     if (!perChannel()) return;
-    if (_plan) detail::configCheck(sdrhip_tunermodes_i16_set_mode(_plan, int(c), mode), "TunerBank");
+    if (_plan) detail::configCheck(sdrhip_tunermodes_i16_set_mode(_plan, int(c), mode), K::name());
     _modes[c] = mode;
   }
   Source *source(size_t c) { return _outs[c]; }
@@ -1493,37 +1517,37 @@ public:
   /** The reference setters' effects (src/baseband.hh:82-104) on channel c alone. */
   void setCenterFrequency(size_t c, double Fc) {
     Tune &t = _tunes[c];
-    t.Fc = int32_t(Fc); t.shift = t.Fc;   // (truncated before setFrequencyShift, src/baseband.hh:85)
-    if (_plan) detail::configCheck(sdrhip_tuner_i16_set_shift(_plan, int(c), design::freqShiftIncrement(t.shift, double(_Fs)), 0 > t.shift), "TunerBank");
+    t.Fc = Freq(Fc); t.shift = t.Fc;   // (IQBaseBand: truncated before setFrequencyShift, src/baseband.hh:85)
+    if (_plan) detail::configCheck(sdrhip_tuner_i16_set_shift(_plan, int(c), design::freqShiftIncrement(t.shift, double(_Fs)), 0 > t.shift), K::name());
   }
-  void setFilterFrequency(size_t c, double Ff) { _tunes[c].Ff = int32_t(Ff); _retap(c); }
-  void setFilterWidth(size_t c, double width) { _tunes[c].width = int32_t(width); _retap(c); }
+  void setFilterFrequency(size_t c, double Ff) { _tunes[c].Ff = Freq(Ff); _retap(c); }
+  void setFilterWidth(size_t c, double width) { _tunes[c].width = Freq(width); _retap(c); }
 
   virtual void config(const Config &cfg) {
     if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
-    detail::checkType<cs16>(cfg, "TunerBank");
+    detail::checkType<In>(cfg, K::name());
     _bs = cfg.bufferSize();
-    _Fs = int32_t(cfg.sampleRate());
+    _Fs = Freq(cfg.sampleRate());
     _rebuild();
   }
 
-  virtual void process(const Buffer<cs16> &b, bool) {
+  virtual void process(const Buffer<In> &b, bool) {
     if (!_plan || b.size() > _bs) return;
     // the per-channel outputs are views of _stageOut: while a consumer still holds one of the last round, this round is
     // dropped, as every node drops its input while its output buffer is in use (src/baseband.hh:141-150)
     if (!_stageOut.isUnused()) {
       LogMessage msg(LOG_WARNING);
-      msg << "gpu::TunerBank: output of the last round still in use downstream; buffer dropped";
+      msg << K::gname() << ": output of the last round still in use downstream; buffer dropped";
       Logger::get().log(msg);
       return;
     }
     const size_t C = _tunes.size(), per = detail::fusedPer<cs16>(_epilogue);   // int16 elements fit twice into a cs16 row
     size_t n = 0;
     if (b.size() == 0) return;
-    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din.get(), b.data(), b.size() * sizeof(cs16)), "gpu::TunerBank") ||
-        !detail::processOk(sdrhip_tuner_i16_process_dev(_plan, _din.get(), b.size(), _dout.get(), _outStride * per, &n), "gpu::TunerBank") ||
-        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout.get(), C * _outStride * sizeof(cs16)), "gpu::TunerBank") ||
-        !detail::processOk(sdrhip_ctx_synchronize(_ctx), "gpu::TunerBank"))
+    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din.get(), b.data(), b.size() * sizeof(In)), K::gname()) ||
+        !detail::processOk(sdrhip_tuner_i16_process_dev(_plan, _din.get(), b.size(), _dout.get(), _outStride * per, &n), K::gname()) ||
+        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout.get(), C * _outStride * sizeof(cs16)), K::gname()) ||
+        !detail::processOk(sdrhip_ctx_synchronize(_ctx), K::gname()))
       return;
     for (size_t ch = 0; ch < C; ch++) detail::sendDemodulated(*_outs[ch], _modes[ch], _stageOut, ch * _outStride, n, false);
   }
@@ -1532,22 +1556,24 @@ protected:
   // as the reference node keeps them (src/baseband.hh:266-272): int32 members, truncated; only the constructor's frequency
   // shift is the untruncated double (gpu::IQBaseBand: _shift)
   struct Tune {
-    int32_t Fc, Ff, width;
+    Freq Fc, Ff, width;
     double shift;
-    Tune(double fc, double ff, double w) : Fc(int32_t(fc)), Ff(int32_t(ff)), width(int32_t(w)), shift(fc) {}
+    Tune(double fc, double ff, double w) : Fc(Freq(fc)), Ff(Freq(ff)), width(Freq(w)), shift(fc) {}
   };
 
   void _checkMode(int mode) const {
     if (perChannel() ? (mode == SDRHIP_EPI_FM || mode == SDRHIP_EPI_AM || mode == SDRHIP_EPI_USB) : mode == _epilogue) return;
     ConfigError err;
-    if (perChannel()) err << "TunerBank: mode " << mode << " is none of SDRHIP_EPI_FM, SDRHIP_EPI_AM, SDRHIP_EPI_USB";
-    else err << "TunerBank: mode " << mode << " in a bank whose channels all have the demodulator " << _epilogue;
+    if (perChannel()) err << K::name() << ": mode " << mode << " is none of SDRHIP_EPI_FM, SDRHIP_EPI_AM, SDRHIP_EPI_USB";
+    else err << K::name() << ": mode " << mode << " in a bank whose channels all have the demodulator " << _epilogue;
     throw err;
   }
 
   void _retap(size_t c) {
     if (!_plan) return;
-    detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), detail::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order).data()), "TunerBank");
+    std::vector<int32_t> taps(2 * _order);
+    K::taps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data());
+    detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), taps.data()), K::name());
   }
 
   /** In this order: the device is idle before anything it may still use goes. */
@@ -1570,22 +1596,18 @@ protected:
     std::vector<uint32_t> inc(C);
     std::vector<int> neg(C);
     for (size_t c = 0; c < C; c++) {
-      design::iqbbTaps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data() + c * 2 * _order);
+      K::taps(_tunes[c].Ff, _tunes[c].width, _Fs, _order, taps.data() + c * 2 * _order);
       inc[c] = design::freqShiftIncrement(_tunes[c].shift, double(_Fs));
       neg[c] = 0 > _tunes[c].shift;
     }
     _outStride = (_bs + _D - 1) / _D + 1;
-    if (perChannel())
-      detail::configCheck(sdrhip_tunermodes_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), _modes.data(),
-                                                       int(_D), int(C), _bs, _plan.out()), "TunerBank");
-    else
-      detail::configCheck(sdrhip_tuner_i16_create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), int(_D), int(C), _bs,
-                                                  _epilogue, _plan.out()), "TunerBank");
-    _din.alloc(_ctx, _bs * sizeof(cs16), "TunerBank");
-    _dout.alloc(_ctx, C * _outStride * sizeof(cs16), "TunerBank");
+    detail::configCheck(K::create(_ctx, taps.data(), int(_order), lut.data(), inc.data(), neg.data(), perChannel() ? _modes.data() : 0,
+                                  int(_D), int(C), _bs, _epilogue, _plan.out()), K::name());
+    _din.alloc(_ctx, _bs * sizeof(In), K::name());
+    _dout.alloc(_ctx, C * _outStride * sizeof(cs16), K::name());
     _stageOut = Buffer<cs16>(C * _outStride);
-    _pinOut.reset(_stageOut.data(), C * _outStride * sizeof(cs16), "TunerBank");
-    for (size_t c = 0; c < C; c++) _outs[c]->configure(detail::bankOutConfig(_epilogue, _Fs, _D, _outStride));
+    _pinOut.reset(_stageOut.data(), C * _outStride * sizeof(cs16), K::name());
+    for (size_t c = 0; c < C; c++) _outs[c]->configure(Config(detail::fusedType<cs16>(_epilogue), K::outRate(_Fs, _D), _outStride, 1));
   }
 
   size_t _order, _D;
@@ -1595,11 +1617,42 @@ protected:
   detail::DeviceMem _din, _dout;
   detail::Pinned _pinOut;   // the registration of _stageOut
   size_t _bs, _outStride;
-  int32_t _Fs;
+  Freq _Fs;
   std::vector<Tune> _tunes;
   std::vector<int> _modes;   // per channel: its demodulator (the bank's epilogue, where it has one for all)
   std::vector<Out *> _outs;
   Buffer<cs16> _stageOut;
+};
+}  // namespace detail
+
+/** Several IQBaseBand<int16_t> nodes connected to one source, as one node: a Sink<cs16> with one Source per channel
+ * (source(c), the ChannelBank::Out pattern). Every channel has its own centre frequency, filter frequency and width;
+ * order, sub-sampling and the fused demodulator are the bank's. Per buffer: one H2D copy, one launch for all channels
+ * (sdrhip_tuner_i16_*), one D2H copy of all rows into a pinned staging buffer, then one send per channel, in channel
+ * order, as views of it. addChannel() after config() rebuilds the device plan: every channel restarts as a freshly
+ * configured node (FIR history, decimator and LUT phases at zero).
+ * With epilogue = TunerBank::PerChannel every channel has a demodulator of its own (SDRHIP_EPI_FM | _AM | _USB: the modes of
+ * the reference's receiver, examples/sdr_rec.cc:44-110, on one antenna), still in one launch; setMode() replaces the
+ * demodulator node behind ONE channel's baseband, which goes on as it is (sdrhip_tunermodes_i16_set_mode). Every output's Config
+ * is int16_t at the decimated rate, whatever the modes are. */
+template <>
+class TunerBank<int16_t> : public detail::TunerBank16<detail::ComplexBank> {
+public:
+  TunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
+    : detail::TunerBank16<detail::ComplexBank>(order, sub_sample, epilogue, device) {}
+};
+
+template <class Scalar> class RealTunerBank;
+/** The bank for a real-sampled antenna (a direct-sampling HF receiver): several BaseBand<int16_t> nodes connected to one source
+ * of real int16 samples, as one node — a Sink<int16_t> with one Source per channel, everything else as TunerBank<int16_t>:
+ * the same constructor forms (RealTunerBank::PerChannel included), addChannel, setMode and the per-channel setters, one launch
+ * per buffer (sdrhip_tunerbb_i16_create / sdrhip_tunermodes_bb_i16_create). As the reference's real-input node it keeps
+ * its frequencies and the sample rate as doubles (src/baseband.hh:520-526), designs Q16 taps and sends at Fs / sub_sample. */
+template <>
+class RealTunerBank<int16_t> : public detail::TunerBank16<detail::RealBank> {
+public:
+  RealTunerBank(size_t order, size_t sub_sample, int epilogue = SDRHIP_EPI_NONE, int device = 0)
+    : detail::TunerBank16<detail::RealBank>(order, sub_sample, epilogue, device) {}
 };
 
 // =================================================================================================

@@ -291,6 +291,36 @@ int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, con
 int sdrhip_tunermodes_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                                  const int *negative, const int *modes, int decim, int channels, size_t max_in,
                                  sdrhip_tuner_i16 **out);
+/* A bank for a REAL-sampled antenna (a direct-sampling HF receiver: one int16 per sample): `channels` independent
+ * BaseBand<int16_t> nodes — the real-input node of sdrhip_bb_i16_create (reference src/baseband.hh:425-460) — connected to ONE
+ * source, each optionally followed in place by FMDemod / AMDemod / USBDemod<int16_t>; output row c is bit for bit what the
+ * reference node with channel c's taps and shift produces from the same buffers, for every sequence of calls, retunes and
+ * resets. What is shared and what is per channel is as above. The differences from the complex bank:
+ *   input   ONE row of n_in real int16 samples (2 B per sample); set_input_format returns SDRHIP_E_UNSUPPORTED
+ *   taps    raw Q16 (Kr, Ki) int32 (sdrhip_design_bb_taps), any |component| < 2^23
+ *   FIR     sum k[i] x taken mod 2^32, then >> 16 (Traits<int16_t>::shift) instead of >> 14
+ *   windows group g is the D samples {gD ... gD + D - 1} from the first sample on: no D + 1 first window
+ *   output  cs16 (SDRHIP_EPI_NONE) or the demodulated int16
+ * sdrhip_tunermodes_bb_i16_create is the form with a demodulator per channel (as sdrhip_tunermodes_i16_create). Both return a
+ * sdrhip_tuner_i16: every sdrhip_tuner_i16_* and sdrhip_tunermodes_i16_* call takes it and keeps its meaning. (The create calls
+ * carry the prefixes sdrhip_tunerbb_ / sdrhip_tunermodes_bb_ so that the sdrhip_tuner_i16_* set stays the one every bank answers.)
+ * Valid plans: order 1 ... 513, decim 1 ... 512, channels 1 ... 8192. Errors, checked in this order and BEFORE the context (they
+ * are host rules): a NULL pointer SDRHIP_E_INVALID; order outside 1 ... 513 SDRHIP_E_UNSUPPORTED; decim < 1 SDRHIP_E_INVALID,
+ * decim > 512 SDRHIP_E_UNSUPPORTED; channels, epilogue or a mode out of range SDRHIP_E_INVALID; max_in SDRHIP_E_SIZE; a tap
+ * component or LUT entry of 24 bits or more SDRHIP_E_UNSUPPORTED (as sdrhip_bb_i16_create); then ctx = NULL: SDRHIP_E_NODEVICE on a
+ * machine without a usable device, SDRHIP_E_INVALID elsewhere.
+ * Kernels (kernel_names; in a profile the per-channel-mode instances are tuner_bb_i16_modes_*): "tuner_bb_i16_mfma_kernel" — the
+ * int8 GEMM over the real sample stream, ONE byte per sample and plane, so an order needs S = ceil(order / 32) K steps, half the
+ * complex bank's, and a staged plane half the bytes (plan_info reports both) — for decimations 4 ... 512, calls of at least 512
+ * samples and taps of EVERY channel within two byte planes (|component| < 2^15 - 128: the normal case of a narrow channel of a
+ * wideband stream); "tuner_bb_i16_valu_kernel" (one wrapping 24-bit multiply-add per tap and component) for every other plan and
+ * call. A channel with larger taps moves the whole bank to the plain kernel until set_taps replaces them: a third tap plane
+ * does not exist. SDRHIP_TUNER_PATH and SDRHIP_TUNER_CTW act as above. */
+int sdrhip_tunerbb_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                              const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out);
+int sdrhip_tunermodes_bb_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                                    const int *negative, const int *modes, int decim, int channels, size_t max_in,
+                                    sdrhip_tuner_i16 **out);
 /* Replaces the demodulator node behind channel `channel`'s baseband, between any two calls. The baseband goes on as it is:
  * FIR ring, open window and its partial sum, LUT phase and sample index continue, and no other channel is touched. The new
  * node is a freshly configured one — an FMDemod starts from last angle 0 (src/demod.hh:195-212, _last_value = 0 at :210),
@@ -310,7 +340,7 @@ int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len);
 int sdrhip_tuner_i16_plan_info(sdrhip_tuner_i16 *h, size_t n_in, int *info, int n);
 /* outputs per channel the next call of n_in samples will produce (does not advance the state) */
 int sdrhip_tuner_i16_out_count(sdrhip_tuner_i16 *h, size_t n_in, size_t *n_out);
-/* in: ONE row of n_in samples (cs16, or complex<uint8> after set_input_format); out: channels rows of out_stride
+/* in: ONE row of n_in samples (cs16, or complex<uint8> after set_input_format; a real-input bank: int16); out: channels rows of out_stride
  * elements (cs16 for EPI_NONE, int16 otherwise; 0 = tightly packed). process_dev: the output must not overlap the input. */
 int sdrhip_tuner_i16_process(sdrhip_tuner_i16 *h, const void *in_host, size_t n_in, void *out_host, size_t out_stride, size_t *n_out);
 int sdrhip_tuner_i16_process_dev(sdrhip_tuner_i16 *h, const void *in_dev, size_t n_in, void *out_dev, size_t out_stride, size_t *n_out);
@@ -319,7 +349,8 @@ int sdrhip_tuner_i16_process_dev(sdrhip_tuner_i16 *h, const void *in_dev, size_t
 int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *taps);
 /* setCenterFrequency of ONE channel: new increment and sign, that channel's LUT phase restarts with the next sample */
 int sdrhip_tuner_i16_set_shift(sdrhip_tuner_i16 *h, int channel, uint32_t lut_inc, int negative);
-/* SDRHIP_IN_CS16 | SDRHIP_IN_CU8, before the first buffer or right after a reset (sdrhip_iqbb_i16_set_input_format) */
+/* SDRHIP_IN_CS16 | SDRHIP_IN_CU8, before the first buffer or right after a reset (sdrhip_iqbb_i16_set_input_format); a
+ * real-input bank takes its own sample type only: SDRHIP_E_UNSUPPORTED */
 int sdrhip_tuner_i16_set_input_format(sdrhip_tuner_i16 *h, int format);
 /* every channel at once, flags as sdrhip_iqbb_i16_reset: bit 0 keeps the (shared) FIR ring, | 2 the FM angles */
 int sdrhip_tuner_i16_reset(sdrhip_tuner_i16 *h, int keep_history);

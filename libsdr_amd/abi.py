@@ -102,6 +102,10 @@ def lib():
                                                   sz, C.c_int, pvp]),
             "sdrhip_tunermodes_i16_create": (C.c_int, [vp, i32p, C.c_int, i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                        C.c_int, C.c_int, sz, pvp]),
+            "sdrhip_tunerbb_i16_create": (C.c_int, [vp, i32p, C.c_int, i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                    sz, C.c_int, pvp]),
+            "sdrhip_tunermodes_bb_i16_create": (C.c_int, [vp, i32p, C.c_int, i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                          C.c_int, C.c_int, sz, pvp]),
             "sdrhip_tunermodes_i16_set_mode": (C.c_int, [vp, C.c_int, C.c_int]),
             "sdrhip_tunermodes_i16_get_modes": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int]),
             "sdrhip_tuner_i16_kernel_names": (C.c_int, [vp, C.c_char_p, sz]),

@@ -26,6 +26,16 @@
 //                           recombine, >> 14, rotate by the channel's own increment and phase origin, and add into the
 //                           (channel, group) box sums in LDS (through a wave-private transpose tile; wrapping int32 adds commute: ds_add_u32). Decimations 4 ... 512,
 //                           taps whose high byte plane fits int8, calls of at least HOT_MIN_IN samples.
+// A bank of REAL-input channels (sdrhip_tunerbb_i16_create / sdrhip_tunermodes_bb_i16_create: C BaseBand<int16_t> nodes over ONE
+// row of real int16 samples, src/baseband.hh:425-460) is the third template argument of both bodies and of channel_view, behind
+// entry points of its own (tuner_bb_i16_valu_kernel, tuner_bb_i16_mfma_kernel and their _modes_ forms):
+//   plain form              one wrapping 24-bit multiply-add per tap and component on the raw Q16 (Kr, Ki) pair, >> 16
+//   matrix form             U[k][t] = u[t - KW + 1 + k] over the real stream, ONE byte per sample and plane, KW = 32 S with
+//                           S = ceil(order / 32): half the K steps and half the staged plane bytes of the complex bank; rows
+//                           (c, re) = Kr, (c, im) = Ki; a lane's K slice starts at plane byte tc + 16 hh + 32 s, any byte
+//                           alignment (v_alignbyte by off & 3); recombined mod 2^32, >> 16. Same conditions as above.
+// The windows of D samples from the first sample on (no D + 1 first window) come from call_geometry(.., real = true);
+// finalize_group and epilogue_and_roll see in_real through the channel's view.
 #include "iqbb_common.hpp"
 #include "iqbb_host.hpp"
 #include "entry.hpp"
@@ -63,10 +73,10 @@ struct TunerArgs {
 // finalize_group and epilogue_and_roll stay uniform. Such a bank has the FM geometry (ovl = 1, the angle cache behind
 // ybuf + CGr): an AM / USB channel leaves the overlap slot's ybuf entry unused (epilogue_and_roll starts at a.ovl), and
 // neither writes the angle cache nor fm_new — the host keeps its fm entries at 0 (sdrhip_tunermodes_i16_set_mode).
-template <int EPI, bool CU8>
+template <int EPI, bool CU8, bool REAL>
 __device__ __forceinline__ IqbbArgs channel_view(const TunerArgs &t, int c, bool rolls) {
   IqbbArgs b = t.a;
-  b.in_cu8 = CU8; b.in_real = 0; b.i8 = 0; b.epilogue = EPI == EPI_PER_CHANNEL ? t.mode[c] : EPI;
+  b.in_cu8 = CU8; b.in_real = REAL; b.i8 = 0; b.epilogue = EPI == EPI_PER_CHANNEL ? t.mode[c] : EPI;
   b.taps = t.a.taps + (long)c * t.a.OP;
   b.inc = t.inc[c]; b.negative = t.negative[c];
   b.n0_lo = t.a.n0_lo - t.phase0[c];
@@ -78,11 +88,13 @@ __device__ __forceinline__ IqbbArgs channel_view(const TunerArgs &t, int c, bool
 }
 
 // ---- plain form: iqbb_i16_kernel's general decimation path over the shared row, one channel per blockIdx.y -----------
-template <int EPI, bool CU8>
+// REAL (a bank of BaseBand<int16_t> channels): the staged dwords are sign-extended real samples, a tap is the raw (Kr, Ki)
+// int32 pair and one wrapping 24-bit multiply-add per component replaces the dot2 (iqbb_i16_kernel<.., true>); >> 16.
+template <int EPI, bool CU8, bool REAL>
 __device__ __forceinline__ void tuner_valu_body(const TunerArgs &t) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const int c = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-  const IqbbArgs a = channel_view<EPI, CU8>(t, c, c == 0);
+  const IqbbArgs a = channel_view<EPI, CU8, REAL>(t, c, c == 0);
   const int XS = TI + a.OP + 8;
   uint32_t *xs = smem;                                  // staged samples, x[tb-(OP-1) ...]
   int2 *lut_s = reinterpret_cast<int2 *>(smem + XS);    // 128 entries
@@ -122,17 +134,23 @@ __device__ __forceinline__ void tuner_valu_body(const TunerArgs &t) {
         const uint2 k = tp[i0 + u];   // workgroup-uniform -> scalar loads
 #pragma unroll
         for (int r = 0; r < R; r++) {
-          sre[r] = dot2(w[u + r], k.x, sre[r]);
-          sim[r] = dot2(w[u + r], k.y, sim[r]);
+          if (REAL) {
+            sre[r] = (int)((unsigned)__mul24((int)k.x, (int)w[u + r]) + (unsigned)sre[r]);
+            sim[r] = (int)((unsigned)__mul24((int)k.y, (int)w[u + r]) + (unsigned)sim[r]);
+          } else {
+            sre[r] = dot2(w[u + r], k.x, sre[r]);
+            sim[r] = dot2(w[u + r], k.y, sim[r]);
+          }
         }
       }
 #pragma unroll
       for (int u = 0; u < 8; u++) w[u] = w[u + 8];
     }
+    constexpr int FSH = REAL ? 16 : 14;   // Traits<int16_t>::shift vs the literal 14 of IQBaseBand (src/baseband.hh:459, :235)
 #pragma unroll
     for (int r = 0; r < R; r++) {
       const int rel = tb + R * tid + r;
-      int2 v = rotate(a, lut_s, make_int2(sre[r] >> 14, sim[r] >> 14), a.n0_lo + (uint32_t)rel);
+      int2 v = rotate(a, lut_s, make_int2(sre[r] >> FSH, sim[r] >> FSH), a.n0_lo + (uint32_t)rel);
       if (rel < 0 || rel >= a.N) v = make_int2(0, 0);   // outside this call
       vbuf[R * tid + r] = v;
     }
@@ -162,7 +180,10 @@ __device__ __forceinline__ void tuner_valu_body(const TunerArgs &t) {
 // bytes k = 32 s + 16 hh + j of row m, and row m carries the channel and component that hot_row (iqbb_host.hpp) gives:
 // by the 32x32 C/D map lane (n, h) then holds, in accumulator registers 2j / 2j + 1, (re, im) of channel 8 h + j of the
 // tile at time column n.
-template <int EPI, bool CU8>
+// REAL (a bank of BaseBand<int16_t> channels): the element stream is the real sample stream itself, ONE byte per sample and
+// plane, so a K step of 32 plane bytes covers 32 samples (KW = 32 S, half the complex bank's K steps for an order), row
+// (c, re) is Kr and row (c, im) is Ki, and a lane's K slice starts at plane byte tc + 16 hh + 32 s — any byte alignment.
+template <int EPI, bool CU8, bool REAL>
 __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const IqbbArgs &g = t.a;
@@ -182,11 +203,25 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
   const int tb = g.base0_rel + q0 * g.D;
   const int groups_here = min(g.CG, g.n_groups - q0);
   const int span = groups_here * g.D;          // time columns of this tile
-  const int KW = 16 * t.S;                     // padded filter length: plane byte 0 = re of sample tb - (KW - 1)
+  const int KW = (REAL ? 32 : 16) * t.S;       // padded filter length: plane byte 0 = (re of) sample tb - (KW - 1)
 
   {   // ---- stage the tile's samples as two byte planes, once for every channel tile ------------------------------------
-    IqbbArgs a0 = g; a0.in_cu8 = CU8; a0.in_real = 0; a0.i8 = 0;
-    const int first = tb - (KW - 1), need = t.PLB / 2;
+    IqbbArgs a0 = g; a0.in_cu8 = CU8; a0.in_real = REAL; a0.i8 = 0;
+    const int first = tb - (KW - 1), need = REAL ? t.PLB / 4 : t.PLB / 2;
+    if (REAL) {   // four samples = one dword of each plane per lane and step
+      for (int i = tid; i < need; i += TPB) {
+        uint32_t hi = 0, lo = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int k = 4 * i + j;
+          const uint32_t x = k < span + KW - 1 ? load_x(a0, 0, first + k) : 0u;
+          hi |= ((x >> 8) & 0xffu) << (8 * j);
+          lo |= ((x & 0xffu) ^ 0x80u) << (8 * j);
+        }
+        reinterpret_cast<uint32_t *>(plane_h)[i] = hi;
+        reinterpret_cast<uint32_t *>(plane_l)[i] = lo;
+      }
+    } else
     for (int i = tid; i < need; i += TPB) {
       const uint32_t x = i < span + KW - 1 ? load_x(a0, 0, first + i) : 0u;
       const uint32_t hi = ((x >> 8) & 0xffu) | ((x >> 16) & 0xff00u);
@@ -220,10 +255,10 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
       v16i acc_hh = {0}, acc_mid = {0}, acc_ll;
 #pragma unroll
       for (int r = 0; r < 16; r++) { const int2 k = ccst[8 * h + (r >> 1)]; acc_ll[r] = (r & 1) ? k.y : k.x; }
-      const int off = 2 * tc + 16 * h;       // plane byte of the lane's K slice at step 0 (2-byte aligned)
+      const int off = (REAL ? tc : 2 * tc) + 16 * h;   // plane byte of the lane's K slice at step 0 (2-byte aligned; REAL: any alignment)
       const uint32_t *ph = reinterpret_cast<const uint32_t *>(plane_h + (off & ~3));
       const uint32_t *pl = reinterpret_cast<const uint32_t *>(plane_l + (off & ~3));
-      const uint32_t sh = (uint32_t)(off & 2);
+      const uint32_t sh = (uint32_t)(off & (REAL ? 3 : 2));
       for (int s = 0; s < t.S; s++) {
         const v4i Ah = frag[(2 * s) * 64], Al = frag[(2 * s + 1) * 64];
         uint32_t dh[5], dl[5];
@@ -240,7 +275,7 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
         acc_hh = __builtin_amdgcn_mfma_i32_32x32x32_i8(Ah, uh, acc_hh, 0, 0, 0);
         acc_mid = __builtin_amdgcn_mfma_i32_32x32x32_i8(Ah, ul, acc_mid, 0, 0, 0);
       }
-      // ---- recombine, >> 14, the channel's rotation; then through a wave-private LDS tile [channel][column] so that four
+      // ---- recombine, >> 14 (REAL: >> 16), the channel's rotation; then through a wave-private LDS tile [channel][column] so that four
       // lanes per channel each add 8 consecutive columns in registers and touch the (channel, group) box sums once per
       // group they meet (wrapping int32 adds commute: ds_add_u32), not once per column ------------------------------------
       const int rel = tb + tc;               // call-relative sample index
@@ -252,7 +287,8 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
         const unsigned sr = ((unsigned)acc_hh[2 * j] << 16) + ((unsigned)acc_mid[2 * j] << 8) + (unsigned)acc_ll[2 * j];
         const unsigned si = ((unsigned)acc_hh[2 * j + 1] << 16) + ((unsigned)acc_mid[2 * j + 1] << 8) + (unsigned)acc_ll[2 * j + 1];
         int2 v = make_int2(0, 0);            // outside the call or the tile: r = 0 -> v = 0
-        if (valid) v = rotate_i16(cinc[cl], cneg[cl], lut_s, make_int2((int)sr >> 14, (int)si >> 14), cn0[cl] + (uint32_t)rel);
+        constexpr int FSH = REAL ? 16 : 14;
+        if (valid) v = rotate_i16(cinc[cl], cneg[cl], lut_s, make_int2((int)sr >> FSH, (int)si >> FSH), cn0[cl] + (uint32_t)rel);
         tr[cl * TR_STRIDE + n] = v;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -282,7 +318,7 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
 
     // ---- per channel: carry / first-sample quirk / division / state, then demodulate and store --------------------------
     for (int cl = 0; cl < chans; cl++) {
-      const IqbbArgs a = channel_view<EPI, CU8>(t, c0 + cl, c0 + cl == 0);
+      const IqbbArgs a = channel_view<EPI, CU8, REAL>(t, c0 + cl, c0 + cl == 0);
       for (int ql = tid; ql < groups_here; ql += TPB) {
         const int q = q0 + ql;
         if (q < 0) continue;
@@ -291,7 +327,7 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
     }
     __syncthreads();
     for (int cl = 0; cl < chans; cl++) {
-      const IqbbArgs a = channel_view<EPI, CU8>(t, c0 + cl, c0 + cl == 0);
+      const IqbbArgs a = channel_view<EPI, CU8, REAL>(t, c0 + cl, c0 + cl == 0);
       epilogue_and_roll(a, 0, tile, tid, q0, groups_here, ybuf + cl * 2 * g.CGr);
     }
   }
@@ -301,19 +337,29 @@ __device__ __forceinline__ void tuner_mfma_body(const TunerArgs &t) {
 // mode per channel. The latter have names of their own: the set of tuner_i16_valu_kernel / tuner_i16_mfma_kernel instances is
 // the single-epilogue one.
 template <int EPI, bool CU8>
-__global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI, CU8>(t); }
+__global__ __launch_bounds__(TPB) void tuner_i16_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI, CU8, false>(t); }
 template <int EPI, bool CU8>
-__global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI, CU8>(t); }
+__global__ __launch_bounds__(TPB, 2) void tuner_i16_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI, CU8, false>(t); }
 template <bool CU8>
-__global__ __launch_bounds__(TPB) void tuner_i16_modes_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI_PER_CHANNEL, CU8>(t); }
+__global__ __launch_bounds__(TPB) void tuner_i16_modes_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI_PER_CHANNEL, CU8, false>(t); }
 template <bool CU8>
-__global__ __launch_bounds__(TPB, 2) void tuner_i16_modes_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI_PER_CHANNEL, CU8>(t); }
+__global__ __launch_bounds__(TPB, 2) void tuner_i16_modes_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI_PER_CHANNEL, CU8, false>(t); }
+// ... and of a bank of real-input channels (sdrhip_tunerbb_i16_create / sdrhip_tunermodes_bb_i16_create): one input kind
+template <int EPI>
+__global__ __launch_bounds__(TPB) void tuner_bb_i16_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI, false, true>(t); }
+template <int EPI>
+__global__ __launch_bounds__(TPB, 2) void tuner_bb_i16_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI, false, true>(t); }
+__global__ __launch_bounds__(TPB) void tuner_bb_i16_modes_valu_kernel(const TunerArgs t) { tuner_valu_body<EPI_PER_CHANNEL, false, true>(t); }
+__global__ __launch_bounds__(TPB, 2) void tuner_bb_i16_modes_mfma_kernel(const TunerArgs t) { tuner_mfma_body<EPI_PER_CHANNEL, false, true>(t); }
 
 }  // namespace
 
 struct sdrhip_tuner_i16 {
   sdrhip_ctx *ctx = nullptr;
   int order = 0, OP = 0, S = 0, HH = 0, D = 1, C = 1, epi = 0, in_cu8 = 0, ovl = 0;
+  // a bank of BaseBand<int16_t> channels (sdrhip_tunerbb_i16_create): real int16 samples in, raw Q16 taps, S counts K steps
+  // of 32 SAMPLES, windows of D samples from the first sample on
+  int real = 0;
   // a mode per channel (sdrhip_tunermodes_i16_create): epi = SDRHIP_EPI_FM stands for the bank's geometry, element size and
   // double-buffered angles; the kernels take each channel's demodulator from `mode`
   bool per_channel = false;
@@ -341,12 +387,15 @@ struct sdrhip_tuner_i16 {
   Staging stage;
   std::string last_names;
 
-  Geometry geometry(size_t N) const { return call_geometry(n0, N, D, false); }
+  Geometry geometry(size_t N) const { return call_geometry(n0, N, D, real != 0); }
   size_t out_elem_bytes() const { return epi == SDRHIP_EPI_NONE ? 4 : 2; }
-  size_t in_elem_bytes() const { return in_cu8 ? 2 : 4; }
+  size_t in_elem_bytes() const { return (in_cu8 || real) ? 2 : 4; }
   bool hot_plan() const { return !force_valu && misfits == 0 && D >= HOT_MIN_D; }
   bool hot_call(size_t N) const { return hot_plan() && N >= (size_t)HOT_MIN_IN; }
-  const char *kernel_name(bool hot) const { return hot ? "tuner_i16_mfma_kernel" : "tuner_i16_valu_kernel"; }
+  const char *kernel_name(bool hot) const {
+    if (real) return hot ? "tuner_bb_i16_mfma_kernel" : "tuner_bb_i16_valu_kernel";
+    return hot ? "tuner_i16_mfma_kernel" : "tuner_i16_valu_kernel";
+  }
 
   // what a call of N >= 1 samples with the geometry g launches (launch and sdrhip_tuner_i16_plan_info)
   struct Plan { bool hot; int CG, OG, tiles, ctw, grid_y, PLB; size_t lds; };
@@ -362,7 +411,8 @@ struct sdrhip_tuner_i16 {
       int ctw = 8; while (ctw > 1 && (size_t)p.tiles * ceil_div((size_t)ctiles, (size_t)ctw) < 1024) ctw >>= 1;
       p.ctw = force_ctw ? force_ctw : ctw;
       const int cols = (p.CG * D + 31) & ~31;
-      p.PLB = (2 * (cols + 16 * S) + 16 + 15) & ~15;
+      // (the last K slice of the tile's last column ends at plane byte 2 cols + 32 S; real input: cols + 32 S)
+      p.PLB = ((real ? cols + 32 * S : 2 * (cols + 16 * S)) + 16 + 15) & ~15;
       p.grid_y = (int)ceil_div((size_t)ctiles, (size_t)p.ctw);
       p.lds = 1024 + 2 * (size_t)p.PLB + CT * (4 + 4 + 4 + 8) + (size_t)CT * p.CG * 8 + (size_t)CT * 2 * CGr * 4 + 4 * (size_t)CT * TR_STRIDE * 8;
     } else {
@@ -374,20 +424,22 @@ struct sdrhip_tuner_i16 {
 
   // channel tile ct's fragments (S x 2 x 64 x 16 bytes) and its channels' constant terms (layout: tuner_i16_mfma_kernel)
   void pack_tile(int ct, std::vector<int8_t> &frag, int2 *cst_tile) const {
-    const int KW = 16 * S, pad = KW - order;
-    std::vector<int> are((size_t)CT * 2 * KW, 0), aim((size_t)CT * 2 * KW, 0);
+    // a row of the tap matrix: RL = 32 S elements — KW = 16 S interleaved (re, im) pairs, or KW = 32 S real samples
+    const int RL = 32 * S, pad = (real ? RL : RL / 2) - order;
+    std::vector<int> are((size_t)CT * RL, 0), aim((size_t)CT * RL, 0);
     for (int cl = 0; cl < CT; cl++) {
       const int c = ct * CT + cl;
-      int *re = are.data() + (size_t)cl * 2 * KW, *im = aim.data() + (size_t)cl * 2 * KW;
+      int *re = are.data() + (size_t)cl * RL, *im = aim.data() + (size_t)cl * RL;
       if (c < C && fits[c]) {
         const int32_t *k = taps_host.data() + (size_t)c * order * 2;
         for (int i = 0; i < order; i++) {
           const int kr = k[2 * i], ki = k[2 * i + 1];
+          if (real) { re[pad + i] = kr; im[pad + i] = ki; continue; }
           re[2 * (pad + i)] = kr; re[2 * (pad + i) + 1] = -ki;
           im[2 * (pad + i)] = ki; im[2 * (pad + i) + 1] = kr;
         }
       }
-      cst_tile[cl] = make_int2(planes_const(re, 2 * KW), planes_const(im, 2 * KW));
+      cst_tile[cl] = make_int2(planes_const(re, RL), planes_const(im, RL));
     }
     frag.assign((size_t)S * 2 * 64 * 16, 0);
     for (int st = 0; st < S; st++)
@@ -395,7 +447,7 @@ struct sdrhip_tuner_i16 {
         const int hh = l >> 5;
         int cl, comp, ah, al;
         hot_row(l & 31, cl, comp);
-        const int *row = (comp ? aim.data() : are.data()) + (size_t)cl * 2 * KW;
+        const int *row = (comp ? aim.data() : are.data()) + (size_t)cl * RL;
         for (int j = 0; j < 16; j++) {
           split_planes(row[32 * st + 16 * hh + j], ah, al);
           frag[((size_t)(2 * st) * 64 + l) * 16 + j] = (int8_t)ah;
@@ -413,28 +465,38 @@ struct sdrhip_tuner_i16 {
   }
   void upload_valu(int c) {
     std::vector<uint2> tp(OP);
-    pack_valu_taps(taps_host.data() + (size_t)c * order * 2, order, OP, false, tp.data());
+    pack_valu_taps(taps_host.data() + (size_t)c * order * 2, order, OP, real != 0, tp.data());
     SDRHIP_CHECK_HIP(hipMemcpyAsync(taps.p + (size_t)c * OP, tp.data(), (size_t)OP * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
     SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   }
 
-  template <int EPI, bool CU8>
+  template <int EPI, bool CU8, bool REAL>
   void launch_kernels(bool hot, const TunerArgs &t, dim3 grid, size_t lds) {
-    if (hot) hipLaunchKernelGGL((tuner_i16_mfma_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
-    else hipLaunchKernelGGL((tuner_i16_valu_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+    if constexpr (REAL) {
+      if (hot) hipLaunchKernelGGL((tuner_bb_i16_mfma_kernel<EPI>), grid, dim3(TPB), lds, ctx->stream, t);
+      else hipLaunchKernelGGL((tuner_bb_i16_valu_kernel<EPI>), grid, dim3(TPB), lds, ctx->stream, t);
+    } else {
+      if (hot) hipLaunchKernelGGL((tuner_i16_mfma_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+      else hipLaunchKernelGGL((tuner_i16_valu_kernel<EPI, CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+    }
   }
-  template <bool CU8>
+  template <bool CU8, bool REAL>
   void launch_epi(bool hot, const TunerArgs &t, dim3 grid, size_t lds) {
     if (per_channel) {
-      if (hot) hipLaunchKernelGGL((tuner_i16_modes_mfma_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
-      else hipLaunchKernelGGL((tuner_i16_modes_valu_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+      if constexpr (REAL) {
+        if (hot) hipLaunchKernelGGL(tuner_bb_i16_modes_mfma_kernel, grid, dim3(TPB), lds, ctx->stream, t);
+        else hipLaunchKernelGGL(tuner_bb_i16_modes_valu_kernel, grid, dim3(TPB), lds, ctx->stream, t);
+      } else {
+        if (hot) hipLaunchKernelGGL((tuner_i16_modes_mfma_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+        else hipLaunchKernelGGL((tuner_i16_modes_valu_kernel<CU8>), grid, dim3(TPB), lds, ctx->stream, t);
+      }
       return;
     }
     switch (epi) {
-      case SDRHIP_EPI_FM: launch_kernels<SDRHIP_EPI_FM, CU8>(hot, t, grid, lds); break;
-      case SDRHIP_EPI_AM: launch_kernels<SDRHIP_EPI_AM, CU8>(hot, t, grid, lds); break;
-      case SDRHIP_EPI_USB: launch_kernels<SDRHIP_EPI_USB, CU8>(hot, t, grid, lds); break;
-      default: launch_kernels<SDRHIP_EPI_NONE, CU8>(hot, t, grid, lds); break;
+      case SDRHIP_EPI_FM: launch_kernels<SDRHIP_EPI_FM, CU8, REAL>(hot, t, grid, lds); break;
+      case SDRHIP_EPI_AM: launch_kernels<SDRHIP_EPI_AM, CU8, REAL>(hot, t, grid, lds); break;
+      case SDRHIP_EPI_USB: launch_kernels<SDRHIP_EPI_USB, CU8, REAL>(hot, t, grid, lds); break;
+      default: launch_kernels<SDRHIP_EPI_NONE, CU8, REAL>(hot, t, grid, lds); break;
     }
   }
 
@@ -447,7 +509,7 @@ struct sdrhip_tuner_i16 {
     const bool hot = p.hot;
     TunerArgs t{};
     IqbbArgs &a = t.a;
-    a.in = reinterpret_cast<const uint32_t *>(in_dev); a.in_stride = 0; a.in_cu8 = in_cu8;
+    a.in = reinterpret_cast<const uint32_t *>(in_dev); a.in_stride = 0; a.in_cu8 = in_cu8; a.in_real = real;
     a.hist_old = hist[par].p; a.hist_new = hist[par ^ 1].p; a.HH = HH;
     a.acc_old = acc[par].p; a.acc_new = acc[par ^ 1].p;
     // (every FM channel writes its fm_new entry in such a call; the other channels of a per-channel bank have 0 in both)
@@ -464,9 +526,12 @@ struct sdrhip_tuner_i16 {
     t.C = C; t.S = S; t.ctiles = ctiles; t.ctw = p.ctw; t.PLB = p.PLB;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.grid_y);
     const size_t lds = p.lds;
-    // (every valid plan fits: the plain form needs at most 44 KB at decimation 1, the matrix form 55200 B at decimation 4 and 513 taps)
+    // (every valid plan fits: the plain form needs at most 44 KB at decimation 1, the matrix form 55200 B at decimation 4 and 513
+    // taps; a real-input bank's matrix form 53152 B there: its planes hold one byte per sample)
     SDRHIP_REQUIRE(lds <= 64 * 1024, SDRHIP_E_HIP, "internal error: %zu B of LDS for a valid plan", lds);
-    if (in_cu8) launch_epi<true>(hot, t, grid, lds); else launch_epi<false>(hot, t, grid, lds);
+    if (real) launch_epi<false, true>(hot, t, grid, lds);
+    else if (in_cu8) launch_epi<true, false>(hot, t, grid, lds);
+    else launch_epi<false, false>(hot, t, grid, lds);
     SDRHIP_CHECK_HIP(hipGetLastError());
     par ^= 1;
     if (fm_flip) par_fm ^= 1;
@@ -478,28 +543,46 @@ struct sdrhip_tuner_i16 {
 
 static inline bool valid_mode(int m) { return m == SDRHIP_EPI_FM || m == SDRHIP_EPI_AM || m == SDRHIP_EPI_USB; }
 
-// sdrhip_tuner_i16_create (modes = NULL) and sdrhip_tunermodes_i16_create (epilogue = SDRHIP_EPI_FM: the geometry)
+// the argument rules of the four create calls: host only, nothing is allocated before them (all pointers non-NULL)
+static void tuner_check_args(const int32_t *taps, int order, const int32_t *lut, const int *modes, int decim, int channels, size_t max_in,
+                             int epilogue, bool real) {
+  SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
+  SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
+  SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
+  require_channels(channels, TUNER_MAX_CHANNELS);
+  require_max_in(max_in);
+  SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
+  for (int c = 0; modes && c < channels; c++)
+    SDRHIP_REQUIRE(valid_mode(modes[c]), SDRHIP_E_INVALID, "channel %d: mode %d is none of SDRHIP_EPI_FM, _AM, _USB", c, modes[c]);
+  for (size_t i = 0; i < (size_t)channels * order * 2; i++)
+    SDRHIP_REQUIRE(tap_in_range(taps[i], real), SDRHIP_E_UNSUPPORTED,
+                   real ? "channel %zu: tap %zu = %d exceeds 24 bits" : "channel %zu: tap %zu = %d does not fit the packed int16 path",
+                   i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
+  for (int i = 0; i < 256; i++)
+    SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
+}
+
+// where no device exists there is no context to pass: say that, not "NULL argument"
+static void require_device_for_null_ctx(sdrhip_ctx *ctx) {
+  if (ctx) return;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    SDRHIP_FAIL(SDRHIP_E_NODEVICE, "no HIP device available, hence no context; libsdrhip has no CPU fallback");
+  }
+}
+
+// sdrhip_tuner_i16_create (modes = NULL), sdrhip_tunermodes_i16_create (epilogue = SDRHIP_EPI_FM: the geometry) and their
+// real-input forms sdrhip_tunerbb_i16_create / sdrhip_tunermodes_bb_i16_create (real)
 static void tuner_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc, const int *negative,
-                         const int *modes, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
+                         const int *modes, int decim, int channels, size_t max_in, int epilogue, bool real, sdrhip_tuner_i16 **out) {
   make_handle(ctx, out, taps && lut && lut_inc && negative, [&](sdrhip_tuner_i16 *h) {
-    SDRHIP_REQUIRE(order >= 1 && order <= TUNER_MAX_ORDER, SDRHIP_E_UNSUPPORTED, "order %d outside [1,%d]", order, TUNER_MAX_ORDER);
-    SDRHIP_REQUIRE(decim >= 1, SDRHIP_E_INVALID, "decim %d < 1", decim);
-    SDRHIP_REQUIRE(decim <= TUNER_MAX_DECIM, SDRHIP_E_UNSUPPORTED, "decim %d > %d", decim, TUNER_MAX_DECIM);
-    require_channels(channels, TUNER_MAX_CHANNELS);
-    require_max_in(max_in);
-    SDRHIP_REQUIRE(epilogue >= SDRHIP_EPI_NONE && epilogue <= SDRHIP_EPI_USB, SDRHIP_E_INVALID, "bad epilogue %d", epilogue);
-    for (int c = 0; modes && c < channels; c++)
-      SDRHIP_REQUIRE(valid_mode(modes[c]), SDRHIP_E_INVALID, "channel %d: mode %d is none of SDRHIP_EPI_FM, _AM, _USB", c, modes[c]);
-    for (size_t i = 0; i < (size_t)channels * order * 2; i++)
-      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "channel %zu: tap %zu = %d does not fit the packed int16 path",
-                     i / ((size_t)order * 2), (i / 2) % (size_t)order, taps[i]);
-    for (int i = 0; i < 256; i++)
-      SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
-    h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in;
+    tuner_check_args(taps, order, lut, modes, decim, channels, max_in, epilogue, real);
+    h->order = order; h->D = decim; h->C = channels; h->epi = epilogue; h->max_in = max_in; h->real = real ? 1 : 0;
     h->ovl = epilogue == SDRHIP_EPI_FM ? 1 : 0;
     h->OP = (int)ceil_div((size_t)order, (size_t)TAPC) * TAPC;
-    h->S = (int)ceil_div((size_t)order, (size_t)16);
-    h->HH = 16 * h->S;   // >= OP, and the whole ring (reset with keep_history)
+    h->S = (int)ceil_div((size_t)order, (size_t)(real ? 32 : 16));   // K steps of 32 plane bytes: 16 complex or 32 real samples
+    h->HH = (real ? 32 : 16) * h->S;   // >= OP, and the whole ring (reset with keep_history)
     h->ctiles = (int)ceil_div((size_t)channels, (size_t)CT);
     { const char *force = getenv("SDRHIP_TUNER_PATH"); h->force_valu = force && !strcmp(force, "valu"); }
     if (const char *f = getenv("SDRHIP_TUNER_CTW")) { if (f[0] && !f[1] && strchr("1248", f[0])) h->force_ctw = f[0] - '0'; }
@@ -513,7 +596,7 @@ static void tuner_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const 
     h->taps.alloc((size_t)channels * h->OP);
     {
       std::vector<uint2> all((size_t)channels * h->OP);
-      for (int c = 0; c < channels; c++) pack_valu_taps(taps + (size_t)c * order * 2, order, h->OP, false, all.data() + (size_t)c * h->OP);
+      for (int c = 0; c < channels; c++) pack_valu_taps(taps + (size_t)c * order * 2, order, h->OP, real, all.data() + (size_t)c * h->OP);
       h->taps.upload(all.data(), all.size(), st);
     }
     h->tapfrag.alloc((size_t)h->ctiles * h->S * 2 * 64);
@@ -542,7 +625,7 @@ extern "C" {
 
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
                             const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
-  return guarded([&] { tuner_create(ctx, taps, order, lut, lut_inc, negative, nullptr, decim, channels, max_in, epilogue, out); });
+  return guarded([&] { tuner_create(ctx, taps, order, lut, lut_inc, negative, nullptr, decim, channels, max_in, epilogue, false, out); });
 }
 
 int sdrhip_tunermodes_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
@@ -550,15 +633,34 @@ int sdrhip_tunermodes_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order
                                  sdrhip_tuner_i16 **out) {
   return guarded([&] {
     if (out) *out = nullptr;
-    if (!ctx) {   // where no device exists there is no context to pass: say that, not "NULL argument"
-      int n = 0;
-      if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        SDRHIP_FAIL(SDRHIP_E_NODEVICE, "no HIP device available, hence no context; libsdrhip has no CPU fallback");
-      }
-    }
+    require_device_for_null_ctx(ctx);
     SDRHIP_REQUIRE(!ctx || modes, SDRHIP_E_INVALID, "modes is NULL");   // (ctx = NULL on a machine with a device: make_handle's message)
-    tuner_create(ctx, taps, order, lut, lut_inc, negative, modes, decim, channels, max_in, SDRHIP_EPI_FM, out);
+    tuner_create(ctx, taps, order, lut, lut_inc, negative, modes, decim, channels, max_in, SDRHIP_EPI_FM, false, out);
+  });
+}
+
+// The real-input banks check their arguments BEFORE the context (the rules are host rules: a caller can learn them on a
+// machine without a device); a NULL context then is SDRHIP_E_NODEVICE where no device exists, SDRHIP_E_INVALID elsewhere.
+int sdrhip_tunerbb_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                              const int *negative, int decim, int channels, size_t max_in, int epilogue, sdrhip_tuner_i16 **out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && taps && lut && lut_inc && negative, SDRHIP_E_INVALID, "NULL argument");
+    tuner_check_args(taps, order, lut, nullptr, decim, channels, max_in, epilogue, true);
+    require_device_for_null_ctx(ctx);
+    tuner_create(ctx, taps, order, lut, lut_inc, negative, nullptr, decim, channels, max_in, epilogue, true, out);
+  });
+}
+
+int sdrhip_tunermodes_bb_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
+                                    const int *negative, const int *modes, int decim, int channels, size_t max_in,
+                                    sdrhip_tuner_i16 **out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && taps && lut && lut_inc && negative && modes, SDRHIP_E_INVALID, "NULL argument");
+    tuner_check_args(taps, order, lut, modes, decim, channels, max_in, SDRHIP_EPI_FM, true);
+    require_device_for_null_ctx(ctx);
+    tuner_create(ctx, taps, order, lut, lut_inc, negative, modes, decim, channels, max_in, SDRHIP_EPI_FM, true, out);
   });
 }
 
@@ -647,7 +749,8 @@ int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *t
     SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
     SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
     for (int i = 0; i < 2 * h->order; i++)
-      SDRHIP_REQUIRE(tap_in_range(taps[i], false), SDRHIP_E_UNSUPPORTED, "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
+      SDRHIP_REQUIRE(tap_in_range(taps[i], h->real != 0), SDRHIP_E_UNSUPPORTED,
+                     h->real ? "tap %d = %d exceeds 24 bits" : "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
     h->ctx->use();
     std::copy(taps, taps + (size_t)h->order * 2, h->taps_host.begin() + (size_t)channel * h->order * 2);
     // (taps whose high byte plane does not fit int8 move the whole bank to the plain form until they are replaced)
@@ -679,6 +782,7 @@ int sdrhip_tuner_i16_set_input_format(sdrhip_tuner_i16 *h, int format) {
   return guarded([&] {
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(format == SDRHIP_IN_CS16 || format == SDRHIP_IN_CU8, SDRHIP_E_INVALID, "bad input format %d", format);
+    SDRHIP_REQUIRE(!h->real, SDRHIP_E_UNSUPPORTED, "a bank of real-input channels takes real int16 samples only");
     SDRHIP_REQUIRE(h->n0 == 0, SDRHIP_E_INVALID, "the input format can only change before the first buffer / after a reset");
     h->in_cu8 = format == SDRHIP_IN_CU8;
   });

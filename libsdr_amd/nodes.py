@@ -338,11 +338,14 @@ class IQBaseBandI16(_Node):
 class TunerBankI16(_Node):
     """Tuner bank — C IQBaseBand<int16_t> channels (+ fused FM/AM/USB) over ONE shared input row, each with its own taps
     and frequency shift. modes (a sequence of EPI_FM | EPI_AM | EPI_USB, one per channel) makes a bank with a demodulator per
-    channel (sdrhip_tunermodes_i16_create) instead of the one `epilogue`. Mirrors sdr::gpu::TunerBank<int16_t>."""
+    channel (sdrhip_tunermodes_i16_create) instead of the one `epilogue`. Mirrors sdr::gpu::TunerBank<int16_t>.
+    real=True: the channels are BaseBand<int16_t> nodes over ONE row of real int16 samples (sdrhip_tunerbb_i16_create /
+    sdrhip_tunermodes_bb_i16_create; taps Q16 from design_bb_taps); mirrors sdr::gpu::RealTunerBank<int16_t>."""
     _destroy = "sdrhip_tuner_i16_destroy"
 
-    def __init__(self, ctx, taps, lut, lut_inc, negative, decim, max_in=65536, epilogue=EPI_NONE, modes=None):
+    def __init__(self, ctx, taps, lut, lut_inc, negative, decim, max_in=65536, epilogue=EPI_NONE, modes=None, real=False):
         super().__init__()
+        self.real = bool(real)
         taps = np.ascontiguousarray(taps, np.int32)
         assert taps.ndim == 3 and taps.shape[2] == 2, taps.shape
         lut = np.ascontiguousarray(lut, np.int32).reshape(128, 2)
@@ -356,15 +359,17 @@ class TunerBankI16(_Node):
             m = np.ascontiguousarray(modes, np.intc).reshape(-1)
             assert m.size == channels
             self.epilogue = EPI_FM   # (int16 rows; the bank's geometry is FM's)
-            check(abi.lib().sdrhip_tunermodes_i16_create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
-                                                         lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                         neg.ctypes.data_as(C.POINTER(C.c_int)), m.ctypes.data_as(C.POINTER(C.c_int)),
-                                                         decim, channels, max_in, C.byref(self._h)))
+            create = abi.lib().sdrhip_tunermodes_bb_i16_create if real else abi.lib().sdrhip_tunermodes_i16_create
+            check(create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
+                         lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                         neg.ctypes.data_as(C.POINTER(C.c_int)), m.ctypes.data_as(C.POINTER(C.c_int)),
+                         decim, channels, max_in, C.byref(self._h)))
             return
-        check(abi.lib().sdrhip_tuner_i16_create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
-                                                lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                neg.ctypes.data_as(C.POINTER(C.c_int)), decim, channels, max_in, epilogue,
-                                                C.byref(self._h)))
+        create = abi.lib().sdrhip_tunerbb_i16_create if real else abi.lib().sdrhip_tuner_i16_create
+        check(create(ctx.handle, taps.ctypes.data_as(C.POINTER(C.c_int32)), order,
+                     lut.ctypes.data_as(C.POINTER(C.c_int32)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                     neg.ctypes.data_as(C.POINTER(C.c_int)), decim, channels, max_in, epilogue,
+                     C.byref(self._h)))
 
     @property
     def kernel_names(self):
@@ -386,9 +391,13 @@ class TunerBankI16(_Node):
         return n.value
 
     def process(self, x):
-        """x: ONE row [n, 2] (int16, or uint8 after set_input_format(IN_CU8)); returns [C, n_out(, 2)]."""
+        """x: ONE row [n, 2] (int16, or uint8 after set_input_format(IN_CU8)) — a real bank: [n] int16; returns
+        [C, n_out(, 2)]."""
         x = np.ascontiguousarray(x, np.uint8 if self._cu8 else np.int16)
-        assert x.ndim == 2 and x.shape[1] == 2, x.shape
+        if self.real:
+            assert x.ndim == 1, x.shape
+        else:
+            assert x.ndim == 2 and x.shape[1] == 2, x.shape
         n_in = x.shape[0]
         no = self.out_count(n_in)
         out = np.zeros((self.channels, no, 2) if self.epilogue == EPI_NONE else (self.channels, no), np.int16)

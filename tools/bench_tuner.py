@@ -15,7 +15,15 @@ kernel forms, interleaved in the same way:
   mixed    the per-channel bank, FM / AM / USB in turn
 Before anything is timed, all_fm is compared with fm on every row and every row of mixed with the row of the single-demodulator
 bank of its mode, bit for bit. Writes profiles/tuner_modes_bench.json; exits non-zero when a comparison failed. No speed gate.
-usage: python tools/bench_tuner.py [--modes] [reps] [rounds] [out.json]"""
+--real: the bank of real-input channels (TunerBankI16(real=True): BaseBand<int16_t> over ONE row of real int16 samples) instead,
+127 taps: 1024 channels at /20 FM, /8 FM and /20 USB, and 16 and 128 channels at /20 FM, interleaved in the same way:
+  a        what the library offered before: C one-channel BaseBandI16 plans run back to back on the same device row
+  complex  the complex bank at the same order, decimation, demodulator and C on a cs16 row of as many samples (matrix form)
+  c        the real bank, matrix form          d  the real bank, plain form (SDRHIP_TUNER_PATH=valu)
+Before anything is timed one step of c is compared with a's rows bit for bit. Writes profiles/tuner_real_bench.json with the
+ratios a_over_c (and whether a's fastest round is still slower than c's slowest: the bank beats the one-channel plans by more
+than the spread of the two measurements), c_over_complex and d_over_c; exits non-zero when c was not verified or that fails.
+usage: python tools/bench_tuner.py [--modes | --real] [reps] [rounds] [out.json]"""
 import json
 import os
 import sys
@@ -28,10 +36,11 @@ sys.path.insert(0, ROOT)
 import libsdr_amd as sa
 
 MODES = "--modes" in sys.argv[1:]
-ARGS = [a for a in sys.argv[1:] if a != "--modes"]
+REAL = "--real" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a not in ("--modes", "--real")]
 REPS = int(ARGS[0]) if len(ARGS) > 0 and ARGS[0].isdigit() else 50
 ROUNDS = int(ARGS[1]) if len(ARGS) > 1 else 5
-OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "tuner_modes_bench.json" if MODES else "tuner_bench.json")
+OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "tuner_modes_bench.json" if MODES else "tuner_real_bench.json" if REAL else "tuner_bench.json")
 N = 65536
 CHANNELS = (16, 128, 1024)
 PLANS = {"fm127d8": dict(order=127, D=8, Fs=2.4e6, cu8=False), "sdr_fm": dict(order=21, D=125, Fs=1e6, cu8=True)}
@@ -77,13 +86,13 @@ def measure(ctx, fns):
     return out
 
 
-def bank(ctx, tn, lut, D, cu8, valu, epilogue=sa.EPI_FM, modes=None):
+def bank(ctx, tn, lut, D, cu8, valu, epilogue=sa.EPI_FM, modes=None, real=False):
     old = os.environ.pop("SDRHIP_TUNER_PATH", None)
     if valu:
         os.environ["SDRHIP_TUNER_PATH"] = "valu"
     try:
         b = sa.TunerBankI16(ctx, np.stack([np.asarray(t[0], np.int32).reshape(-1, 2) for t in tn]), lut, [t[1] for t in tn],
-                            [t[2] for t in tn], D, max_in=N, epilogue=epilogue, modes=modes)
+                            [t[2] for t in tn], D, max_in=N, epilogue=epilogue, modes=modes, real=real)
     finally:
         os.environ.pop("SDRHIP_TUNER_PATH", None)
         if old is not None:
@@ -217,9 +226,95 @@ def main_modes():
     sys.exit(0 if ok else 1)
 
 
+REAL_FS = 2.0e6
+# (decimation, demodulator, channels)
+REAL_CASES = [(20, "fm", 1024), (8, "fm", 1024), (20, "usb", 1024), (20, "fm", 16), (20, "fm", 128)]
+
+
+def real_tunes(C, order):
+    """C different narrow channels spread over the band 0 ... 0.45 Fs of a real stream, widths 3 ... 12 kHz."""
+    out = []
+    for c in range(C):
+        Fc = float(int(0.45 * (c + 0.5) / C * REAL_FS))
+        out.append((sa.design_bb_taps(Fc, 3e3 + 9e3 * (c % 7) / 7, REAL_FS, order), sa.design_freqshift_inc(Fc, REAL_FS), False))
+    return out
+
+
+def run_real_case(ctx, rng, order, D, epi_name, C):
+    epi = {"fm": sa.EPI_FM, "usb": sa.EPI_USB}[epi_name]
+    lut = sa.design_freqshift_lut_i16()
+    tn = real_tunes(C, order)
+    n = np.arange(N)
+    x = np.rint(9000 * np.cos(2 * np.pi * (0.04 * n + 0.3 * np.sin(2 * np.pi * n / 5000.0))) + rng.normal(0, 2500, N)).astype(np.int16)
+    xc = signal(rng, False)
+    M = N // D + 2
+    din, dcx = ctx.malloc(N * 2), ctx.malloc(N * 4)
+    da, dc = ctx.malloc(C * M * 2), ctx.malloc(C * M * 2)
+    try:
+        ctx.h2d(din, x); ctx.h2d(dcx, xc)
+        ya, yc = np.full((C, M), 0x5A5A, np.int16), np.full((C, M), 0x5A5A, np.int16)
+        ctx.h2d(da, ya); ctx.h2d(dc, yc)
+        a_nodes = [sa.BaseBandI16(ctx, t[0], lut, t[1], t[2], D, channels=1, max_in=N, epilogue=epi) for t in tn]
+        c_bank = bank(ctx, tn, lut, D, False, False, epilogue=epi, real=True)
+        no = c_bank.process_dev(din, N, dc, M)
+        for c, nd in enumerate(a_nodes):
+            assert nd.process_dev(din, N, N, da + c * M * 2, M) == no
+        ctx.synchronize()
+        ctx.d2h(ya, da); ctx.d2h(yc, dc)
+        verified = bool(np.array_equal(ya, yc)) and c_bank.kernel_names == ["tuner_bb_i16_mfma_kernel"]
+        d_bank = bank(ctx, tn, lut, D, False, True, epilogue=epi, real=True)
+        x_bank = bank(ctx, tunes(C, order, 2.4e6), lut, D, False, False, epilogue=epi)
+
+        def run_a():
+            for c, nd in enumerate(a_nodes):
+                nd.process_dev(din, N, N, da + c * M * 2, M)
+
+        r = measure(ctx, {"a_one_channel_plans": run_a,
+                          "complex_bank_hot": lambda: x_bank.process_dev(dcx, N, da, M),
+                          "c_bank_hot": lambda: c_bank.process_dev(din, N, dc, M),
+                          "d_bank_plain": lambda: d_bank.process_dev(din, N, dc, M)})
+        r.update({"order": order, "D": D, "epilogue": epi_name, "channels": C, "verified_c_equals_a": verified, "outputs_per_channel": no,
+                  "plan_info": c_bank.plan_info(N), "complex_plan_info": x_bank.plan_info(N),
+                  "kernels": {"a": a_nodes[0].kernel_names, "complex": x_bank.kernel_names, "c": c_bank.kernel_names, "d": d_bank.kernel_names},
+                  "a_over_c": round(r["a_one_channel_plans"]["ms"] / r["c_bank_hot"]["ms"], 2),
+                  "c_over_complex": round(r["c_bank_hot"]["ms"] / r["complex_bank_hot"]["ms"], 3),
+                  "d_over_c": round(r["d_bank_plain"]["ms"] / r["c_bank_hot"]["ms"], 2),
+                  "channel_msamples_per_s": round(C * N / r["c_bank_hot"]["ms"] / 1e3, 1)})
+        # beyond the run-to-run spread of both measurements: a's fastest round against c's slowest
+        r["c_faster_than_a_beyond_spread"] = r["c_bank_hot"]["max_ms"] < r["a_one_channel_plans"]["min_ms"]
+        for nd in a_nodes + [c_bank, d_bank, x_bank]:
+            nd.close()
+        return r
+    finally:
+        for q in (din, dcx, da, dc):
+            ctx.free(q)
+
+
+def main_real():
+    ctx = sa.Context(0)
+    rng = np.random.default_rng(7)
+    result = {"device": ctx.device_name(), "samples_per_step": N, "order": 127, "reps": REPS, "rounds": ROUNDS, "cases": []}
+    for D, epi, C in REAL_CASES:
+        r = run_real_case(ctx, rng, 127, D, epi, C)
+        result["cases"].append(r)
+        print(json.dumps(r), flush=True)
+    ctx.close()
+    result["conditions"] = {"c_verified_everywhere": all(r["verified_c_equals_a"] for r in result["cases"]),
+                            "c_faster_than_a_beyond_spread_everywhere": all(r["c_faster_than_a_beyond_spread"] for r in result["cases"])}
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    ok = all(result["conditions"].values())
+    print("conditions:", json.dumps(result["conditions"]), "->", "ok" if ok else "FAILED")
+    sys.exit(0 if ok else 1)
+
+
 def main():
     if MODES:
         return main_modes()
+    if REAL:
+        return main_real()
     ctx = sa.Context(0)
     rng = np.random.default_rng(7)
     result = {"device": ctx.device_name(), "samples_per_step": N, "reps": REPS, "rounds": ROUNDS, "plans": {}}
