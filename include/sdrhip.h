@@ -468,6 +468,54 @@ int sdrhip_bits_process_dev(sdrhip_bits *h, const uint8_t *sym_dev, size_t n, si
 int sdrhip_bits_kernel_names(sdrhip_bits *h, char *buf, size_t len);
 int sdrhip_bits_reset(sdrhip_bits *h);
 int sdrhip_bits_destroy(sdrhip_bits *h);
+/* A detector and a bit clock PER CHANNEL: the rows of one call carry different services (AFSK at 1200 baud beside RTTY at
+ * 90.90 baud beside ASK pagers), as the rows of a tuner bank's audio do. The handle types and the process / process_dev /
+ * reset / destroy / kernel_names calls are the ones above; the arithmetic of every row is that of a one-parameter handle
+ * with the row's parameters (bit for bit), the parameters are run-time facts of the channel, and the node behind ONE channel
+ * can be replaced between two calls while the others stream on. One launch per call serves all rows.
+ *
+ * sdrhip_detectorbank_create: kinds / corr_len / invert hold `channels` entries (corr_len[c] is read for an FSK
+ * channel, invert[c] for an ASK channel). mark_luts / space_luts: the FSK channels' LUTs, corr_len[c] x (re, im) each,
+ * concatenated in channel order — an ASK channel contributes none (both may be NULL when no channel is FSK). max_corr_len
+ * (1 ... 2048; 0: the largest corr_len of the bank, 1 without an FSK channel) is the longest correlator a later set_channel
+ * may ask for: it sizes the per-channel LUT slots and history rows. State per channel: kind, corr_len, invert, its LUT, the
+ * last max_corr_len - 1 samples (double-buffered; an FSK channel uses the last corr_len[c] - 1 of them) and the sample count
+ * at which its node started — the slot index of a sample is (samples the handle has seen - that origin) mod corr_len[c],
+ * evaluated in the kernel. Kernel: "detectorbank_kernel" (one workgroup serves one channel: the kind is uniform in it).
+ * Device memory of such a handle: channels x max_corr_len x 16 bytes of LUT (a slot per channel, whether or not two channels
+ * share their parameters) and 2 x channels x (max_corr_len - 1) x 2 bytes of history; channels x max_corr_len above 2^24
+ * (256 MiB of LUT) is SDRHIP_E_UNSUPPORTED — choose max_corr_len for the services the antenna carries, not 2048 by default.
+ *
+ * sdrhip_detectorbank_set_channel: channel c becomes a freshly configured node of the given kind (reference: a new node
+ * connected in the old one's place; FSKDetector::config, src/fsk.cc:32-51) — its history zeroed in both copies, its slot
+ * index 0 at the next sample, its LUT replaced (mark_lut / space_lut: corr_len x (re, im), ignored for ASK). The same
+ * parameters as before still restart the channel. No other channel's state moves. Ordered on the context's stream behind
+ * the calls already enqueued; returns when it has taken effect.
+ *
+ * sdrhip_bitsbank_create: baud[c], mode[c] per channel at ONE sample rate; max_corr_len (0: the largest
+ * int(sample_rate / baud[c]) of the bank) is the longest window a later set_channel may ask for (<= 2048).
+ * sdrhip_bitsbank_set_channel: a fresh BitStream node behind channel c (src/fsk.cc:125-140): ring zeroed in both copies, phase
+ * 0, omega = baud / sample_rate, last bits 0. On such a handle sdrhip_bits_out_capacity reports the LARGEST channel's
+ * capacity — the row stride a caller needs, which a set_channel to a faster baud rate raises — and sdrhip_bits_corr_len
+ * the largest window; sdrhip_bitsbank_channel_info returns channel c's own corr_len, omegaMin / omegaMax and capacity for a
+ * call of n_in samples (any of the four pointers may be NULL). No row is written beyond min(its own capacity, out_stride).
+ * Device memory: 2 x channels x max_corr_len bytes of ring, 16 bytes per channel and 64 symbols of max_in, 32 per channel.
+ * Kernels: "bitsbank_pll_kernel" behind "bitsbank_flags_kernel".
+ *
+ * Errors: a channel outside the bank, a bad kind or mode, corr_len < 1, a baud rate above the sample rate: SDRHIP_E_INVALID;
+ * corr_len (or int(sample_rate / baud)) above max_corr_len, max_corr_len above 2048: SDRHIP_E_UNSUPPORTED — and nothing has
+ * changed. set_channel and channel_info on a handle made by sdrhip_detector_create / sdrhip_bits_create (one parameter set
+ * for all rows): SDRHIP_E_UNSUPPORTED. The create calls check their arguments BEFORE the context, so the rules answer on a
+ * machine without a device too; a NULL context then is SDRHIP_E_NODEVICE where no device exists, SDRHIP_E_INVALID elsewhere. */
+int sdrhip_detectorbank_create(sdrhip_ctx *ctx, const int *kinds, const int *corr_len, const int *invert, const float *mark_luts,
+                               const float *space_luts, int max_corr_len, int channels, size_t max_in, sdrhip_detector **out);
+int sdrhip_detectorbank_set_channel(sdrhip_detector *h, int channel, int kind, const float *mark_lut, const float *space_lut,
+                                    int corr_len, int invert);
+int sdrhip_bitsbank_create(sdrhip_ctx *ctx, double sample_rate, const float *baud, const int *mode, int channels, size_t max_in,
+                           int max_corr_len, sdrhip_bits **out);
+int sdrhip_bitsbank_set_channel(sdrhip_bits *h, int channel, float baud, int mode);
+int sdrhip_bitsbank_channel_info(sdrhip_bits *h, int channel, size_t n_in, int *corr_len, float *omega_min, float *omega_max,
+                                 size_t *cap);
 
 /* ---- K6: SubSample<complex<int16_t>|complex<float>> (src/subsample.hh:92-101) ------------- */
 int sdrhip_subsample_create(sdrhip_ctx *ctx, int dtype, size_t n, int channels, size_t max_in,

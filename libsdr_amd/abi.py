@@ -153,6 +153,12 @@ def lib():
             "sdrhip_bits_kernel_names": (C.c_int, [vp, C.c_char_p, sz]),
             "sdrhip_bits_reset": (C.c_int, [vp]),
             "sdrhip_bits_destroy": (C.c_int, [vp]),
+            "sdrhip_detectorbank_create": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), f32p, f32p,
+                                                             C.c_int, C.c_int, sz, pvp]),
+            "sdrhip_detectorbank_set_channel": (C.c_int, [vp, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int]),
+            "sdrhip_bitsbank_create": (C.c_int, [vp, C.c_double, f32p, C.POINTER(C.c_int), C.c_int, sz, C.c_int, pvp]),
+            "sdrhip_bitsbank_set_channel": (C.c_int, [vp, C.c_int, C.c_float, C.c_int]),
+            "sdrhip_bitsbank_channel_info": (C.c_int, [vp, C.c_int, sz, C.POINTER(C.c_int), f32p, f32p, psz]),
             "sdrhip_iqbb_i16_set_input_format": (C.c_int, [vp, C.c_int]),
             "sdrhip_subsample_create": (C.c_int, [vp, C.c_int, sz, C.c_int, sz, pvp]),
             "sdrhip_subsample_out_count": (C.c_int, [vp, sz, psz]),

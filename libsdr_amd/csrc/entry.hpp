@@ -47,6 +47,17 @@ static inline void require_max_in(size_t max_in) {
   SDRHIP_REQUIRE(max_in >= 1 && max_in < (size_t(1) << 30), SDRHIP_E_SIZE, "max_in %zu outside [1,2^30)", max_in);
 }
 
+// A create call that checks its argument rules BEFORE the context (host rules: a caller can learn them on a machine without
+// a device) ends them with this: where no device exists there is no context to pass — say that, not "NULL argument".
+static inline void require_device_for_null_ctx(sdrhip_ctx *ctx) {
+  if (ctx) return;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    SDRHIP_FAIL(SDRHIP_E_NODEVICE, "no HIP device available, hence no context; libsdrhip has no CPU fallback");
+  }
+}
+
 // ---- the head of a process / process_dev call ----------------------------------------------------------------------------
 // In this order: handle, n against max_in, the empty call (false: nothing to do, and nothing else is looked at), buffers.
 // n_name: what the header calls the count ("n", "n_in") — it appears in the messages.

@@ -562,16 +562,6 @@ static void tuner_check_args(const int32_t *taps, int order, const int32_t *lut,
     SDRHIP_REQUIRE(lut[i] > -(1 << 23) && lut[i] < (1 << 23), SDRHIP_E_UNSUPPORTED, "LUT entry %d = %d exceeds 24 bits", i / 2, lut[i]);
 }
 
-// where no device exists there is no context to pass: say that, not "NULL argument"
-static void require_device_for_null_ctx(sdrhip_ctx *ctx) {
-  if (ctx) return;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    SDRHIP_FAIL(SDRHIP_E_NODEVICE, "no HIP device available, hence no context; libsdrhip has no CPU fallback");
-  }
-}
-
 // sdrhip_tuner_i16_create (modes = NULL), sdrhip_tunermodes_i16_create (epilogue = SDRHIP_EPI_FM: the geometry) and their
 // real-input forms sdrhip_tunerbb_i16_create / sdrhip_tunermodes_bb_i16_create (real)
 static void tuner_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc, const int *negative,

@@ -751,6 +751,77 @@ class BitStream(_Node):
         super().close()
 
 
+def _lut_pairs(lut):
+    return np.ascontiguousarray(lut, np.float32).reshape(-1, 2)
+
+
+class SymbolDetectorBank(SymbolDetector):
+    """A detector PER CHANNEL (sdrhip_detectorbank_create): `channels` is a list with one entry per row,
+    ("fsk", mark_lut, space_lut) — LUTs as design_fsk_lut makes them — or ("ask", invert). One launch serves all rows;
+    set_channel replaces the node behind one row between two calls. max_corr_len: the longest correlator a later
+    set_channel may ask for (default: the bank's longest)."""
+
+    def __init__(self, ctx, channels, max_in=65536, max_corr_len=0):
+        _Node.__init__(self)
+        self.ctx, self.channels, self.kind = ctx, len(channels), None
+        kinds, lens, inv, marks, spaces = [], [], [], [], []
+        for ch in channels:
+            kind, m, s, L, i = self._channel(ch)
+            kinds.append(kind); lens.append(L); inv.append(i)
+            if kind == abi.DET_FSK:
+                marks.append(m); spaces.append(s)
+        ia = lambda v: np.ascontiguousarray(v, np.intc)
+        kinds, lens, inv = ia(kinds), ia(lens), ia(inv)
+        m = np.concatenate(marks) if marks else np.zeros((0, 2), np.float32)
+        s = np.concatenate(spaces) if spaces else np.zeros((0, 2), np.float32)
+        ip, f32p = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        check(abi.lib().sdrhip_detectorbank_create(
+            ctx.handle, kinds.ctypes.data_as(ip), lens.ctypes.data_as(ip), inv.ctypes.data_as(ip),
+            m.ctypes.data_as(f32p) if marks else None, s.ctypes.data_as(f32p) if marks else None, max_corr_len, self.channels, max_in,
+            C.byref(self._h)))
+
+    @staticmethod
+    def _channel(ch):
+        """-> (kind, mark [L, 2] | None, space | None, corr_len, invert)"""
+        if ch[0] in ("fsk", abi.DET_FSK):
+            m, s = _lut_pairs(ch[1]), _lut_pairs(ch[2])
+            assert m.shape == s.shape, (m.shape, s.shape)
+            return abi.DET_FSK, m, s, m.shape[0], 0
+        assert ch[0] in ("ask", abi.DET_ASK), ch[0]
+        return abi.DET_ASK, None, None, 0, int(bool(ch[1])) if len(ch) > 1 else 0
+
+    def set_channel(self, c, channel):
+        """Row c becomes a freshly configured node — ("fsk", mark_lut, space_lut) or ("ask", invert); the other rows stream on."""
+        kind, m, s, L, inv = self._channel(channel)
+        f32p = C.POINTER(C.c_float)
+        check(abi.lib().sdrhip_detectorbank_set_channel(self._h, c, kind, m.ctypes.data_as(f32p) if m is not None else None,
+                                                    s.ctypes.data_as(f32p) if s is not None else None, L, inv))
+
+
+class BitStreamBank(BitStream):
+    """A BitStream PER CHANNEL at one sample rate (sdrhip_bitsbank_create): bauds[c], modes[c]. out_capacity(n) is the
+    largest channel's capacity (the row stride); channel_info(c, n) the row's own numbers. set_channel replaces the node behind
+    one row between two calls. max_corr_len: the longest window a later set_channel may ask for (default: the bank's longest)."""
+
+    def __init__(self, ctx, Fs, bauds, modes, max_in=65536, max_corr_len=0):
+        _Node.__init__(self)
+        bauds, modes = np.ascontiguousarray(bauds, np.float32).ravel(), np.ascontiguousarray(modes, np.intc).ravel()
+        assert bauds.size == modes.size, (bauds.size, modes.size)
+        self.ctx, self.channels, self._counts_dev = ctx, int(bauds.size), 0
+        check(abi.lib().sdrhip_bitsbank_create(ctx.handle, Fs, bauds.ctypes.data_as(C.POINTER(C.c_float)),
+                                                       modes.ctypes.data_as(C.POINTER(C.c_int)), self.channels, max_in, max_corr_len,
+                                                       C.byref(self._h)))
+
+    def set_channel(self, c, baud, mode=abi.BITS_TRANSITION):
+        check(abi.lib().sdrhip_bitsbank_set_channel(self._h, c, baud, mode))
+
+    def channel_info(self, c, n=0):
+        """-> dict(corr_len, omega_min, omega_max, capacity) of row c for a call of n symbols"""
+        L, lo, hi, cap = C.c_int(0), C.c_float(0), C.c_float(0), C.c_size_t(0)
+        check(abi.lib().sdrhip_bitsbank_channel_info(self._h, c, n, C.byref(L), C.byref(lo), C.byref(hi), C.byref(cap)))
+        return {"corr_len": L.value, "omega_min": lo.value, "omega_max": hi.value, "capacity": cap.value}
+
+
 class SubSample(_Node):
     """K6 — SubSample<complex<int16>|complex<float>>."""
     _destroy = "sdrhip_subsample_destroy"
