@@ -371,6 +371,10 @@ int sdrhip_fir_out_count(sdrhip_fir *h, size_t n_in, size_t *n_out);
  * "fir_cs16_exact_kernel"; complex<float>: "fir_cf32_pipe_kernel" (decimation 8 and enough tiles to give every
  * workgroup several: consecutive tiles software-pipelined in one workgroup) or "fir_cf32_rt_kernel". */
 int sdrhip_fir_kernel_names(sdrhip_fir *h, size_t n_in, char *buf, size_t len);
+/* The kernels the handle's most recent process / process_dev call launched, comma-separated in launch order ("" before the
+ * first call and after a call of 0 samples). A complex<float> plan that runs as FFT convolution answers as
+ * sdrhip_fftconv_last_kernels does for its inner plan; every other plan with its time-domain kernels' names. */
+int sdrhip_fir_last_kernels(sdrhip_fir *h, char *buf, size_t len);
 int sdrhip_fir_process(sdrhip_fir *h, const void *in_host, size_t n_in, size_t in_stride, void *out_host,
                        size_t out_stride, size_t *n_out);
 int sdrhip_fir_process_dev(sdrhip_fir *h, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
@@ -560,6 +564,18 @@ int sdrhip_fftconv_process(sdrhip_fftconv *h, const float *in_host, size_t n_in,
                            float *out_host, size_t out_stride);
 int sdrhip_fftconv_process_dev(sdrhip_fftconv *h, const float *in_dev, size_t n_in, size_t in_stride,
                                float *out_dev, size_t out_stride);
+/* What the most recent process / process_dev call of the handle launched (complex<float> and complex<double> plans alike):
+ * the kernels in launch order, comma-separated, recorded at the launch sites — one entry per launch, so a plan that launches
+ * once per band or per tap partition names its kernel that many times. "" before the first call and after a call of 0
+ * samples. Kernel templates carry their arguments in one spelling, integers and 0 / 1 without spaces:
+ * "fftconv_fused_kernel<LG,BANK,NT,ACC,PIPE,SKIP>" (e.g. "fftconv_fused_kernel<14,0,1024,0,4,2>"), "fftconv_kernel",
+ * "hist_roll_kernel", "conv_kernel<float2>", "big_gather_kernel<double2>", "big_mul_kernel<..>", "big_scatter_kernel<..>",
+ * "big_hist_kernel<..>"; the transforms between the big_* passes appear as one "fft passes<..>" each, and where the four-step
+ * plan carries gather, product and scatter in its own passes they are "fourstep_tile_kernel<float2,gather>", "<float2,product>",
+ * "<float2>" and "<float2,scatter>". Names are separated by the commas OUTSIDE angle brackets. At most 64 launches are kept; a
+ * longer list ends in "...". For tests and profiles: which instance a call runs depends on the plan, the call's length, the
+ * strides and the buffers' alignment. */
+int sdrhip_fftconv_last_kernels(sdrhip_fftconv *h, char *buf, size_t len);
 int sdrhip_fftconv_reset(sdrhip_fftconv *h);
 int sdrhip_fftconv_destroy(sdrhip_fftconv *h);
 /* FFT sizes: the reference plans ANY size (FilterNode(size_t block_size = 1024), src/filternode.hh:235-245;
@@ -663,6 +679,7 @@ int sdrhip_fbb_f32_create(sdrhip_ctx *ctx, double Fc, double Fs, const double *a
                           int channels, size_t max_in, sdrhip_fbb_f32 **out);
 int sdrhip_fbb_f32_out_count(sdrhip_fbb_f32 *h, size_t n_in, size_t *n_out);
 int sdrhip_fbb_f32_kernel_names(sdrhip_fbb_f32 *h, size_t n_in, char *buf, size_t len);   /* as sdrhip_fir_kernel_names */
+int sdrhip_fbb_f32_last_kernels(sdrhip_fbb_f32 *h, char *buf, size_t len);                 /* as sdrhip_fir_last_kernels */
 int sdrhip_fbb_f32_process(sdrhip_fbb_f32 *h, const float *in_host, size_t n_in, size_t in_stride,
                            float *out_host, size_t out_stride, size_t *n_out);
 int sdrhip_fbb_f32_process_dev(sdrhip_fbb_f32 *h, const float *in_dev, size_t n_in, size_t in_stride,

@@ -121,6 +121,7 @@ def lib():
             "sdrhip_fir_create": (C.c_int, [vp, C.c_int, f64p, C.c_int, C.c_int, C.c_int, sz, C.c_int, pvp]),
             "sdrhip_fir_out_count": (C.c_int, [vp, sz, psz]),
             "sdrhip_fir_kernel_names": (C.c_int, [vp, sz, C.c_char_p, sz]),
+            "sdrhip_fir_last_kernels": (C.c_int, [vp, C.c_char_p, sz]),
             "sdrhip_fir_process": (C.c_int, [vp, vp, sz, sz, vp, sz, psz]),
             "sdrhip_fir_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz, psz]),
             "sdrhip_fir_reset": (C.c_int, [vp]),
@@ -169,6 +170,7 @@ def lib():
             "sdrhip_fftconv_create": (C.c_int, [vp, C.c_int, C.c_int, f32p, C.c_int, C.c_int, sz, pvp]),
             "sdrhip_fftconv_process": (C.c_int, [vp, vp, sz, sz, vp, sz]),
             "sdrhip_fftconv_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz]),
+            "sdrhip_fftconv_last_kernels": (C.c_int, [vp, C.c_char_p, sz]),
             "sdrhip_fftconv_reset": (C.c_int, [vp]),
             "sdrhip_fftconv_destroy": (C.c_int, [vp]),
             "sdrhip_fft_c2c": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -177,6 +179,7 @@ def lib():
             "sdrhip_fbb_f32_create": (C.c_int, [vp, C.c_double, C.c_double, f64p, C.c_int, C.c_int, C.c_int, sz, pvp]),
             "sdrhip_fbb_f32_out_count": (C.c_int, [vp, sz, psz]),
             "sdrhip_fbb_f32_kernel_names": (C.c_int, [vp, sz, C.c_char_p, sz]),
+            "sdrhip_fbb_f32_last_kernels": (C.c_int, [vp, C.c_char_p, sz]),
             "sdrhip_fbb_f32_process": (C.c_int, [vp, vp, sz, sz, vp, sz, psz]),
             "sdrhip_fbb_f32_process_dev": (C.c_int, [vp, vp, sz, sz, vp, sz, psz]),
             "sdrhip_fbb_f32_reset": (C.c_int, [vp]),

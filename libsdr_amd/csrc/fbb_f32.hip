@@ -52,10 +52,16 @@ int sdrhip_fbb_f32_kernel_names(sdrhip_fbb_f32 *h, size_t n_in, char *buf, size_
   return sdrhip_fir_kernel_names(h->fir, n_in, buf, len);
 }
 
+int sdrhip_fbb_f32_last_kernels(sdrhip_fbb_f32 *h, char *buf, size_t len) {
+  if (!h) { set_error("handle is NULL"); return SDRHIP_E_INVALID; }
+  return sdrhip_fir_last_kernels(h->fir, buf, len);
+}
+
 int sdrhip_fbb_f32_process_dev(sdrhip_fbb_f32 *h, const float *in_dev, size_t n_in, size_t in_stride, float *out_dev,
                                size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fbb_f32_process_dev");
+    if (h) fir_clear_log(h->fir);
     if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) { if (n_out) *n_out = 0; return; }
     // the strides, the overlap and the launch are the FIR's device entry point's
     int rc = sdrhip_fir_process_dev(h->fir, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
@@ -68,6 +74,7 @@ int sdrhip_fbb_f32_process(sdrhip_fbb_f32 *h, const float *in_host, size_t n_in,
                            size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fbb_f32_process");
+    if (h) fir_clear_log(h->fir);
     if (!call_begin(h, "n_in", n_in, in_host, out_host)) { if (n_out) *n_out = 0; return; }
     size_t no = 0;
     int rc = sdrhip_fir_out_count(h->fir, n_in, &no);

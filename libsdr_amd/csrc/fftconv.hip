@@ -17,6 +17,7 @@
 #include "sdrhip_internal.hpp"
 #include "entry.hpp"
 
+#include <array>
 #include <cmath>
 #include <complex>
 #include <memory>
@@ -783,8 +784,13 @@ void run_conv_staged(sdrhip_ctx *ctx, Staging &st, size_t eb, int C, int B, size
              {out_host, s.out * eb, n_in * eb, out_rows}, [&](void *in, void *out) { launch(in, out); return n_in * eb; });
 }
 
+// a launch record's name for a kernel template over the element type T2 (KernelLog)
+#define SDRHIP_T2_NAME(kernel_) SDRHIP_T2_NAME2(kernel_, "")
+#define SDRHIP_T2_NAME2(kernel_, more_) (sizeof(T2) == sizeof(double2) ? kernel_ "<double2" more_ ">" : kernel_ "<float2" more_ ">")
+
 struct ConvAny {
   bool f64 = false;
+  KernelLog log;   // the kernels of the most recent call (sdrhip_fftconv_last_kernels)
   virtual ~ConvAny() {}
   virtual void load_kernel(int band, const void *kernel) = 0;
   virtual void process_dev(const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride) = 0;
@@ -849,6 +855,7 @@ struct GenConv : ConvAny {
     const size_t lds = plan.lds_bytes() * (a.two ? 2 : 1);
     allow_big_lds(fftgen::conv_kernel<T2>, lds);
     hipLaunchKernelGGL(fftgen::conv_kernel<T2>, dim3((unsigned)ceil_div(N, (size_t)hop), C), dim3(fftgen::GT), lds, ctx->stream, a);
+    log.add(SDRHIP_T2_NAME("conv_kernel"));
     SDRHIP_CHECK_HIP(hipGetLastError());
     if (HH > 0) par ^= 1;
   }
@@ -994,25 +1001,33 @@ struct BigConv : ConvAny {
         f.Kp = Kp.p; f.nb = B; f.band_elems = batch * L;
         f.out = out_dev + (size_t)c0 * out_stride; f.out_stride = (long)out_stride; f.out_band = (long)out_band; f.cg = cg;
         fft.conv_forward(f, batch, Y.p);
+        log.add(SDRHIP_T2_NAME2("fourstep_tile_kernel", ",gather")); log.add(SDRHIP_T2_NAME2("fourstep_tile_kernel", ",product"));
         fft.conv_inverse(f, (long)B * batch, Y.p);
+        log.add(SDRHIP_T2_NAME("fourstep_tile_kernel")); log.add(SDRHIP_T2_NAME2("fourstep_tile_kernel", ",scatter"));
         continue;
       }
       hipLaunchKernelGGL(big_gather_kernel<T2>, dim3(gx, nblk, cg), dim3(256), 0, st, in_dev + (size_t)c0 * in_stride, (long)in_stride,
                          hist[par].p + (size_t)c0 * HH, HH, (int)N, hop, L, nblk, X.p);
+      log.add(SDRHIP_T2_NAME("big_gather_kernel"));
       fft.exec(-1, batch, X.p, X.p);
+      log.add(SDRHIP_T2_NAME("fft passes"));
       for (int band = 0; band < B; band++) {
         for (long z0 = 0; z0 < batch; z0 += 32768) {
           const long zb = std::min<long>(32768, batch - z0);
           hipLaunchKernelGGL(big_mul_kernel<T2>, dim3(gx, (unsigned)zb), dim3(256), 0, st, L, Kp.p + (size_t)band * L, X.p + z0 * L, Y.p + z0 * L);
+          log.add(SDRHIP_T2_NAME("big_mul_kernel"));
         }
         fft.exec(+1, batch, Y.p, Y.p);
+        log.add(SDRHIP_T2_NAME("fft passes"));
         hipLaunchKernelGGL(big_scatter_kernel<T2>, dim3((unsigned)std::min<long>((hop + 255) / 256, 1024), nblk, cg), dim3(256), 0, st, Y.p, L, HH, hop, (int)N, nblk,
                            out_dev + (size_t)band * out_band + (size_t)c0 * out_stride, (long)out_stride);
+        log.add(SDRHIP_T2_NAME("big_scatter_kernel"));
       }
     }
     if (HH > 0) {
       hipLaunchKernelGGL(big_hist_kernel<T2>, dim3((unsigned)std::min<long>((HH + 255) / 256, 1024), C), dim3(256), 0, st, in_dev, (long)in_stride,
                          hist[par].p, hist[par ^ 1].p, HH, (int)N);
+      log.add(SDRHIP_T2_NAME("big_hist_kernel"));
       par ^= 1;
     }
     SDRHIP_CHECK_HIP(hipGetLastError());
@@ -1033,6 +1048,17 @@ struct BigConv : ConvAny {
   void reset() override { ctx->use(); for (int p = 0; p < 2; p++) hist[p].zero(ctx->stream); }
   const char *kernel_names() const override { return fft.fuses() ? "fourstep_tile_kernel x4 (gather, product, scatter fused)" : "big_gather_kernel,fft passes,big_mul_kernel,big_scatter_kernel"; }
 };
+
+// "fftconv_fused_kernel<14,0,1024,0,4,2>": the instance's name in the launch record, written once per instance
+template <int LG, bool BANK, int NT, bool ACC = false, int PIPE = 0, int SKIP = 0>
+const char *fused_name() {
+  static const std::array<char, 64> s = [] {
+    std::array<char, 64> b{};
+    snprintf(b.data(), b.size(), "fftconv_fused_kernel<%d,%d,%d,%d,%d,%d>", LG, (int)BANK, NT, (int)ACC, PIPE, SKIP);
+    return b;
+  }();
+  return s.data();
+}
 
 }  // namespace
 
@@ -1055,6 +1081,8 @@ struct sdrhip_fftconv {
   DevBuf<float2> hist[2];
   Staging stage;
   int stamps_grid = 0;   // (diagnostic builds)
+  KernelLog log;         // the kernels of the most recent call; `any` plans keep their own (sdrhip_fftconv_last_kernels)
+  KernelLog &last() { return any ? any->log : log; }
   DevBuf<float2> dump;   // (the pipelined 16384-point form) 128 bytes per wave of its grid for the stores of masked lanes
 
   // spectrum of one band -> the device layout (digit-reversed position order, pre-scaled by 1/L)
@@ -1127,20 +1155,23 @@ struct sdrhip_fftconv {
     a.hist_new = nullptr;
     a.out = out_dev + (size_t)b0 * out_band; a.out_stride = (long)out_stride; a.N = (int)N; a.hop = hop;
     const int blocks = (int)ceil_div(N, (size_t)hop);
-    auto fused = [&](auto kernel, int nt) {
+    auto fused = [&](auto kernel, const char *name, int nt) {
       if (HL > 0 && b0 + bpl >= B && part + 1 == parts) { a.hist_new = hist[par ^ 1].p; rolled = true; }   // the call's last launch
       allow_big_lds(kernel, lds);
       hipLaunchKernelGGL(kernel, dim3(blocks, C), dim3(nt), lds, ctx->stream, a);
+      log.add(name);
     };
+    // an instance and its name in the launch record, all six template arguments spelled out: K7(14, false, 1024, false, 4, 2)
+#define K7(...) fftconv_fused_kernel<__VA_ARGS__>, fused_name<__VA_ARGS__>()
     const bool fusable = plan.dev.npass >= 2 && plan.dev.radix[0] == 16;
     int nt = plan.L / 16 >= 1024 ? 1024 : plan.L / 16 >= 512 ? 512 : plan.L / 16 >= 256 ? 256 : plan.L / 16 >= 128 ? 128 : 64;
     { const char *e = getenv("SDRHIP_K7_NT"); if (e && a.nb == 1) nt = atoi(e); }   // tuning hook (the bank kernel needs L / 16 lanes)
 #define SDRHIP_FUSED(BANK_) do { switch (nt) { \
-      case 1024: fused(fftconv_fused_kernel<0, BANK_, 1024>, 1024); break; \
-      case 512: fused(fftconv_fused_kernel<0, BANK_, 512>, 512); break; \
-      case 256: fused(fftconv_fused_kernel<0, BANK_, 256>, 256); break; \
-      case 128: fused(fftconv_fused_kernel<0, BANK_, 128>, 128); break; \
-      default: fused(fftconv_fused_kernel<0, BANK_, 64>, 64); break; } } while (0)
+      case 1024: fused(K7(0, BANK_, 1024), 1024); break; \
+      case 512: fused(K7(0, BANK_, 512), 512); break; \
+      case 256: fused(K7(0, BANK_, 256), 256); break; \
+      case 128: fused(K7(0, BANK_, 128), 128); break; \
+      default: fused(K7(0, BANK_, 64), 64); break; } } while (0)
     // compile-time plans (strides, pad offsets and butterfly maps fold into immediates and shifts; the run-time-plan
     // kernel divides by the pass stride per butterfly): 16384 points, and 2048 / 4096 / 8192 with L / 16 lanes
     auto plan_is = [&](int lg) {
@@ -1150,7 +1181,7 @@ struct sdrhip_fftconv {
     };
     const bool ct = getenv("SDRHIP_K7_RUNTIME_PLAN") == nullptr;   // (tuning / tests: the run-time-plan kernel for every size)
     if (plan.L == 16384 && part > 0) {
-      fused(fftconv_fused_kernel<14, false, 1024, true>, 1024);   // (a later tap partition: accumulated)
+      fused(K7(14, false, 1024, true), 1024);   // (a later tap partition: accumulated)
     } else if (plan.L == 16384 && pipe_grid() > 0 && (long)blocks * C > pipe_grid()) {
       // the pipelined form: one persistent workgroup per CU (more units than CUs: otherwise there is no next block to fetch)
       if (HL > 0 && b0 + bpl >= B && part + 1 == parts) { a.hist_new = hist[par ^ 1].p; rolled = true; }   // the call's last launch
@@ -1165,34 +1196,37 @@ struct sdrhip_fftconv {
                       (reinterpret_cast<uintptr_t>(in_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
                       getenv("SDRHIP_K7_PIPE_X2") == nullptr;   // (A/B hook: the 8-byte form everywhere)
       const size_t lds_p = lds + (15 * 64 + 15 * 4) * sizeof(float2);   // (7.5 KB beyond the image that the kernel does not use: the launches were measured with it)
-      auto go = [&](auto kernel) {
+      auto go = [&](auto kernel, const char *name) {
         allow_big_lds(kernel, lds_p);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), lds_p, ctx->stream, a);
+        log.add(name);
       };
       // (the two BASELINE shapes get their stores counted at compile time: 4097 taps keep 12288 of 16384, the reference mode's
       // 8192 taps 8192)
-      if (pv && HH == 4096) go(fftconv_fused_kernel<14, false, 1024, false, 4, 2>);
-      else if (pv && HH == 8192) go(fftconv_fused_kernel<14, false, 1024, false, 4, 4>);
-      else if (pv) go(fftconv_fused_kernel<14, false, 1024, false, 4, 0>);
-      else if (HH == 4096) go(fftconv_fused_kernel<14, false, 1024, false, 2, 4>);
-      else if (HH == 8192) go(fftconv_fused_kernel<14, false, 1024, false, 2, 8>);
-      else go(fftconv_fused_kernel<14, false, 1024, false, 2, 0>);
+      if (pv && HH == 4096) go(K7(14, false, 1024, false, 4, 2));
+      else if (pv && HH == 8192) go(K7(14, false, 1024, false, 4, 4));
+      else if (pv) go(K7(14, false, 1024, false, 4, 0));
+      else if (HH == 4096) go(K7(14, false, 1024, false, 2, 4));
+      else if (HH == 8192) go(K7(14, false, 1024, false, 2, 8));
+      else go(K7(14, false, 1024, false, 2, 0));
     } else if (plan.L == 16384) {   // (never a bank: two images of 16384 points do not fit the LDS)
-      fused(fftconv_fused_kernel<14, false, 1024>, 1024);   // (512 / 256 lanes measured 0.78x / 0.59x)
+      fused(K7(14, false, 1024), 1024);   // (512 / 256 lanes measured 0.78x / 0.59x)
     } else if (ct && fusable && nt == 128 && plan_is(11)) {
-      if (a.nb > 1) fused(fftconv_fused_kernel<11, true, 128>, 128); else fused(fftconv_fused_kernel<11, false, 128>, 128);
+      if (a.nb > 1) fused(K7(11, true, 128), 128); else fused(K7(11, false, 128), 128);
     } else if (ct && fusable && nt == 256 && plan_is(12)) {
-      if (a.nb > 1) fused(fftconv_fused_kernel<12, true, 256>, 256); else fused(fftconv_fused_kernel<12, false, 256>, 256);
+      if (a.nb > 1) fused(K7(12, true, 256), 256); else fused(K7(12, false, 256), 256);
     } else if (ct && fusable && nt == 512 && plan_is(13)) {
-      if (a.nb > 1) fused(fftconv_fused_kernel<13, true, 512>, 512); else fused(fftconv_fused_kernel<13, false, 512>, 512);
+      if (a.nb > 1) fused(K7(13, true, 512), 512); else fused(K7(13, false, 512), 512);
     } else if (fusable && a.nb > 1) {
       SDRHIP_FUSED(true);
     } else if (fusable) {
       SDRHIP_FUSED(false);
 #undef SDRHIP_FUSED
+#undef K7
     } else {
       allow_big_lds(fftconv_kernel, lds);
       hipLaunchKernelGGL(fftconv_kernel, dim3(blocks, C), dim3(FT), lds, ctx->stream, a);
+      log.add("fftconv_kernel");
     }
     }
     }
@@ -1201,6 +1235,7 @@ struct sdrhip_fftconv {
     else if (HL > 0) {
       hipLaunchKernelGGL(hist_roll_kernel, dim3((unsigned)ceil_div((size_t)HL, (size_t)256), C), dim3(256), 0, ctx->stream,
                          in_dev, (long)in_stride, hist[par].p, hist[par ^ 1].p, HL, (int)N);
+      log.add("hist_roll_kernel");
       SDRHIP_CHECK_HIP(hipGetLastError());
       par ^= 1;
     }
@@ -1422,6 +1457,7 @@ int sdrhip_fftconv_process_dev(sdrhip_fftconv *h, const float *in_dev, size_t n_
     Range roctx_range("sdrhip_fftconv_process_dev");
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(!(h->any && h->any->f64), SDRHIP_E_INVALID, "a complex<double> plan: use sdrhip_fftconv_f64_process_dev");
+    h->last().clear();
     if (h->any) { h->any->process_dev(in_dev, n_in, in_stride, out_dev, out_stride); return; }
     if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) return;
     const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
@@ -1436,12 +1472,20 @@ int sdrhip_fftconv_process(sdrhip_fftconv *h, const float *in_host, size_t n_in,
     Range roctx_range("sdrhip_fftconv_process");
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(!(h->any && h->any->f64), SDRHIP_E_INVALID, "a complex<double> plan: use sdrhip_fftconv_f64_process");
+    h->last().clear();
     if (h->any) { h->any->process(in_host, n_in, in_stride, out_host, out_stride); return; }
     if (!call_begin(h, "n_in", n_in, in_host, out_host)) return;
     const Strides s = call_strides("n_in", n_in, in_stride, n_in, out_stride, STRIDES_TOGETHER);
     run_conv_staged(h->ctx, h->stage, 8, h->C, h->B, h->max_in, in_host, n_in, s, out_host, [&](void *in, void *out) {
       h->launch(static_cast<const float2 *>(in), n_in, n_in, static_cast<float2 *>(out), n_in, (size_t)h->C * n_in);
     });
+  });
+}
+
+int sdrhip_fftconv_last_kernels(sdrhip_fftconv *h, char *buf, size_t len) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
+    h->last().write(buf, len);
   });
 }
 
@@ -1500,6 +1544,7 @@ int sdrhip_fftconv_f64_process(sdrhip_fftconv *h, const double *in_host, size_t 
   return guarded([&] {
     Range roctx_range("sdrhip_fftconv_f64_process");
     SDRHIP_REQUIRE(h && h->any && h->any->f64, SDRHIP_E_INVALID, "not a complex<double> plan");
+    h->any->log.clear();
     h->any->process(in_host, n_in, in_stride, out_host, out_stride);
   });
 }
@@ -1508,6 +1553,7 @@ int sdrhip_fftconv_f64_process_dev(sdrhip_fftconv *h, const double *in_dev, size
   return guarded([&] {
     Range roctx_range("sdrhip_fftconv_f64_process_dev");
     SDRHIP_REQUIRE(h && h->any && h->any->f64, SDRHIP_E_INVALID, "not a complex<double> plan");
+    h->any->log.clear();
     h->any->process_dev(in_dev, n_in, in_stride, out_dev, out_stride);
   });
 }

@@ -627,6 +627,7 @@ struct sdrhip_fir {
   DevBuf<float2> etab, etab2, wtab, ptab;   // phase tables of the fused shift (see Fir32Args)
   DevBuf<float2> hist32[2];
   Staging stage;
+  KernelLog log;   // the time-domain kernels of the most recent call (sdrhip_fir_last_kernels; an FFT plan keeps its own)
   ~sdrhip_fir() { if (fftc) (void)sdrhip_fftconv_destroy(fftc); }   // (create's failure path and destroy)
 
   size_t in_elem() const { return kind == SDRHIP_FIR_CS16_EXACT ? 4 : 8; }
@@ -654,6 +655,7 @@ struct sdrhip_fir {
 
   void launch(const void *in_dev, size_t N, size_t in_stride, void *out_dev, size_t out_stride, size_t *n_out) {
     ctx->use();
+    log.clear();
     if (N == 0) { if (n_out) *n_out = 0; return; }
     const size_t no = out_count(N);
     SDRHIP_REQUIRE(out_stride >= no, SDRHIP_E_SIZE, "out_stride %zu < outputs %zu", out_stride, no);
@@ -675,6 +677,7 @@ struct sdrhip_fir {
         if (wrap) hipLaunchKernelGGL((fir_cs16_exact_kernel<true, 4>), grid, block, lds, ctx->stream, a);
         else hipLaunchKernelGGL((fir_cs16_exact_kernel<false, 4>), grid, block, lds, ctx->stream, a);
       }
+      log.add("fir_cs16_exact_kernel");
       SDRHIP_CHECK_HIP(hipGetLastError());
       if (epi == SDRHIP_EPI_FM && N >= 2) par_fm ^= 1;
     } else {
@@ -705,6 +708,7 @@ struct sdrhip_fir {
             a.ptab = ptab.p;
             hipLaunchKernelGGL(tile_phasor_kernel, dim3((unsigned)ceil_div((size_t)tiles, (size_t)64)), dim3(64), 0, ctx->stream, ptab.p, tiles,
                                n_first, step, fc, fs);
+            log.add("tile_phasor_kernel");
           }
         }
         dim3 grid(tiles, C), block(TPB);
@@ -719,11 +723,13 @@ struct sdrhip_fir {
         else if (R == 4) hipLaunchKernelGGL((fir_cf32_rt_kernel<4, 0>), grid, block, lds3, ctx->stream, a);
         else if (R == 2) hipLaunchKernelGGL((fir_cf32_rt_kernel<2, 0>), grid, block, lds3, ctx->stream, a);
         else hipLaunchKernelGGL((fir_cf32_rt_kernel<1, 0>), grid, block, lds3, ctx->stream, a);
+        log.add(D == 8 && (R == 4 || R == 2) && tpw > 1 ? "fir_cf32_pipe_kernel" : "fir_cf32_rt_kernel");
         SDRHIP_CHECK_HIP(hipGetLastError());
       }
       if (M > 1 && !no) {   // (a call that completes no output launches no tile: the history still rolls)
         dim3 grid((unsigned)ceil_div((size_t)(M - 1), (size_t)256), C);
         hipLaunchKernelGGL(hist_roll_cf32, grid, dim3(256), 0, ctx->stream, a.in, a.in_stride, a.hist_old, a.hist_new, M - 1, (int)N);
+        log.add("hist_roll_cf32");
         SDRHIP_CHECK_HIP(hipGetLastError());
       }
     }
@@ -871,6 +877,7 @@ int fir_create_impl(sdrhip_ctx *ctx, int kind, const double *alpha, int order, i
   });
 }
 // the float baseband's host-pointer call: the launch alone, on its own staging rows
+void fir_clear_log(sdrhip_fir *h) { h->log.clear(); }
 void fir_launch(sdrhip_fir *h, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride, size_t *n_out) {
   h->launch(in_dev, n_in, in_stride, out_dev, out_stride, n_out);
 }
@@ -891,6 +898,14 @@ int sdrhip_fir_kernel_names(sdrhip_fir *h, size_t n_in, char *buf, size_t len) {
   });
 }
 
+int sdrhip_fir_last_kernels(sdrhip_fir *h, char *buf, size_t len) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
+    if (h->fftc) { const int rc = sdrhip_fftconv_last_kernels(h->fftc, buf, len); if (rc != SDRHIP_OK) throw Failure{rc}; return; }
+    h->log.write(buf, len);
+  });
+}
+
 int sdrhip_fir_out_count(sdrhip_fir *h, size_t n_in, size_t *n_out) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
@@ -902,6 +917,8 @@ int sdrhip_fir_process_dev(sdrhip_fir *h, const void *in_dev, size_t n_in, size_
                            size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fir_process_dev");
+    if (h) h->log.clear();
+    if (h && h->fftc && n_in == 0) (void)sdrhip_fftconv_process_dev(h->fftc, nullptr, 0, 0, nullptr, 0);   // (the empty call clears the inner plan's record too)
     if (!call_begin(h, "n_in", n_in, in_dev, out_dev)) { if (n_out) *n_out = 0; return; }
     if (h->fftc) {
       const int rc = sdrhip_fftconv_process_dev(h->fftc, static_cast<const float *>(in_dev), n_in, in_stride, static_cast<float *>(out_dev), out_stride);
@@ -921,6 +938,8 @@ int sdrhip_fir_process(sdrhip_fir *h, const void *in_host, size_t n_in, size_t i
                        size_t out_stride, size_t *n_out) {
   return guarded([&] {
     Range roctx_range("sdrhip_fir_process");
+    if (h) h->log.clear();
+    if (h && h->fftc && n_in == 0) (void)sdrhip_fftconv_process_dev(h->fftc, nullptr, 0, 0, nullptr, 0);   // (the empty call clears the inner plan's record too)
     if (!call_begin(h, "n_in", n_in, in_host, out_host)) { if (n_out) *n_out = 0; return; }
     if (h->fftc) {
       const int rc = sdrhip_fftconv_process(h->fftc, static_cast<const float *>(in_host), n_in, in_stride, static_cast<float *>(out_host), out_stride);

@@ -75,6 +75,26 @@ inline int ols_fft_size(int n_taps, size_t channels, size_t max_in, int cus) {
   return n_taps <= 2048 ? 4096 : 16384;
 }
 
+// The kernels a handle's most recent process / process_dev call launched, in launch order (sdrhip_*_last_kernels): written
+// beside each launch as a pointer to a name that lives as long as the library, into a fixed array — a launch allocates
+// nothing. Beyond kMax launches only the count goes on and the list ends in "...".
+struct KernelLog {
+  static constexpr int kMax = 64;
+  const char *name[kMax];
+  int n = 0;
+  void clear() { n = 0; }
+  void add(const char *s) { if (n < kMax) name[n] = s; n++; }
+  void write(char *buf, size_t len) const {
+    size_t at = 0;
+    buf[0] = 0;
+    for (int i = 0; i < n && i <= kMax && at + 1 < len; i++) {
+      const int w = snprintf(buf + at, len - at, "%s%s", i ? "," : "", i < kMax ? name[i] : "...");
+      if (w < 0) break;
+      at += (size_t)w;
+    }
+  }
+};
+
 }  // namespace sdrhip
 
 struct sdrhip_ctx {
@@ -181,6 +201,7 @@ static inline void require_disjoint(const void *in, size_t in_stride, size_t in_
 // fir.hip: turn on the frequency shift fused into the cf32 FIR's staging (used by the float baseband, fbb_f32.hip)
 void fir_set_shift(sdrhip_fir *h, double fc, double fs);
 void fir_load_taps(sdrhip_fir *h, const double *alpha);
+void fir_clear_log(sdrhip_fir *h);   // a call of the float baseband that launches nothing: sdrhip_fbb_f32_last_kernels then says so
 void fir_launch(sdrhip_fir *h, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride, size_t *n_out);
 int fir_create_impl(sdrhip_ctx *ctx, int kind, const double *alpha, int order, int decim, int channels, size_t max_in, int epilogue,
                     bool allow_fft, sdrhip_fir **out);

@@ -507,6 +507,19 @@ class IQBaseBandI8(IQBaseBandI16):
         return out
 
 
+def _split_kernels(text):
+    """A *_last_kernels answer -> the list of names: split at the commas outside angle brackets (template arguments)."""
+    out, depth, cur = [], 0, ""
+    for ch in text:
+        depth += (ch == "<") - (ch == ">")
+        if ch == "," and depth == 0:
+            out.append(cur)
+            cur = ""
+        else:
+            cur += ch
+    return [k for k in out + [cur] if k]
+
+
 class FIR(_Node):
     """K2/K3 — FIRFilter<complex<int16>> exact / FIRFilter<complex<float>> (+ folded SubSample, + demod)."""
     _destroy = "sdrhip_fir_destroy"
@@ -524,6 +537,13 @@ class FIR(_Node):
         b = C.create_string_buffer(256)
         check(abi.lib().sdrhip_fir_kernel_names(self._h, n_in, b, 256))
         return b.value.decode().split(",")
+
+    def last_kernels(self):
+        """The kernels the most recent process / process_dev call launched, in launch order ([] before the first call and
+        after a call of 0 samples)."""
+        b = C.create_string_buffer(4096)
+        check(abi.lib().sdrhip_fir_last_kernels(self._h, b, 4096))
+        return _split_kernels(b.value.decode())
 
     def out_count(self, n_in):
         n = C.c_size_t(0)
@@ -903,6 +923,13 @@ class FFTConv(_Node):
         fn = abi.lib().sdrhip_fftconv_f64_process_dev if self.f64 else abi.lib().sdrhip_fftconv_process_dev
         check(fn(self._h, C.c_void_p(in_ptr), n, in_stride, C.c_void_p(out_ptr), out_stride))
 
+    def last_kernels(self):
+        """The kernels the most recent process / process_dev call launched, in launch order ([] before the first call and
+        after a call of 0 samples)."""
+        b = C.create_string_buffer(4096)
+        check(abi.lib().sdrhip_fftconv_last_kernels(self._h, b, 4096))
+        return _split_kernels(b.value.decode())
+
     def reset(self):
         check(abi.lib().sdrhip_fftconv_reset(self._h))
 
@@ -997,6 +1024,13 @@ class FloatBaseBand(_Node):
         b = C.create_string_buffer(256)
         check(abi.lib().sdrhip_fbb_f32_kernel_names(self._h, n_in, b, 256))
         return b.value.decode().split(",")
+
+    def last_kernels(self):
+        """The kernels the most recent process / process_dev call launched, in launch order ([] before the first call and
+        after a call of 0 samples)."""
+        b = C.create_string_buffer(4096)
+        check(abi.lib().sdrhip_fbb_f32_last_kernels(self._h, b, 4096))
+        return _split_kernels(b.value.decode())
 
     def out_count(self, n_in):
         n = C.c_size_t(0)

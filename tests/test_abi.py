@@ -53,6 +53,18 @@ def test_hot_kernels_keep_out_of_scratch(tmp_path):
     assert len(bad) <= 1 and all("anyd" in n and b <= 12 for n, b in bad), bad
 
 
+def test_last_kernels_entry_points():
+    """The three *_last_kernels calls refuse a NULL handle or buffer without touching a device; the binding splits their answer
+    at the commas outside template arguments."""
+    L = abi.lib()
+    b = C.create_string_buffer(16)
+    for fn in (L.sdrhip_fftconv_last_kernels, L.sdrhip_fir_last_kernels, L.sdrhip_fbb_f32_last_kernels):
+        assert fn(None, b, 16) == abi.E_INVALID
+    assert nodes._split_kernels("") == []
+    assert nodes._split_kernels("fftconv_fused_kernel<14,0,1024,0,4,2>,hist_roll_kernel,big_mul_kernel<double2>,...") == [
+        "fftconv_fused_kernel<14,0,1024,0,4,2>", "hist_roll_kernel", "big_mul_kernel<double2>", "..."]
+
+
 def test_strerror_and_errors_without_device():
     L = abi.lib()
     assert L.sdrhip_strerror(0) == b"ok" and b"device" in L.sdrhip_strerror(abi.E_NODEVICE)
