@@ -1257,6 +1257,8 @@ public:
   public:
     void configure(const Config &c) { this->setConfig(c); }
     void emit(const RawBuffer &b, bool aw) { this->send(b, aw); }
+    /** true while some sink is connected (a bank copies a row to the host only for one that has a receiver) */
+    bool connected() const { return !this->_sinks.empty(); }
   };
 
   /** All channels share the band-select parameters (taps / LUT are read-only data, designed once on the host). */
@@ -1576,8 +1578,9 @@ protected:
     detail::configCheck(sdrhip_tuner_i16_set_taps(_plan, int(c), taps.data()), K::name());
   }
 
-  /** In this order: the device is idle before anything it may still use goes. */
-  void _release() {
+  /** In this order: the device is idle before anything it may still use goes. (Virtual, as _rebuild: gpu::ReceiverBank
+   * builds its later stages around this bank's plan.) */
+  virtual void _release() {
     if (_ctx) sdrhip_ctx_synchronize(_ctx);
     _plan.reset();
     _din.reset();
@@ -1586,7 +1589,7 @@ protected:
     _stageOut.unref();
   }
 
-  void _rebuild() {
+  virtual void _rebuild() {
     _release();
     const size_t C = _tunes.size();
     if (C == 0 || _bs == 0) return;

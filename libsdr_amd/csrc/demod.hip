@@ -7,8 +7,11 @@
 //   SubSample<Scalar>::_process                       src/subsample.hh:92-101
 // Each lane handles 4 consecutive samples: one 16-byte (cs16) or two 16-byte (cf32) loads, one
 // 8/16-byte store; grid-stride over the (channel, sample) plane.
+#include <type_traits>
+
 #include "fm_phi.hpp"
 #include "sdrhip_internal.hpp"
+#include "sdrhip_rx.h"
 #include "entry.hpp"
 
 using namespace sdrhip;
@@ -218,6 +221,7 @@ __global__ __launch_bounds__(TPB) void subsample_cf32_kernel(const SubArgs a) {
 //   deemph_i16_copy_kernel   alpha = 1: the update is avg = x
 //   deemph_i16_seq_kernel    one lane walks one channel's row in registers
 //   deemph_i16_spec_kernel   long rows, alpha <= 32: P lanes per channel from guessed segment states, checked and repaired
+//   (the three above are templates: <false> is the one-parameter handle's kernel, <true> the bank's — a flag per row)
 //   deemph_i16_kernel        rounds 1-2 (kept as a parity form, SDRHIP_DEEMPH_TILED): a 64-lane workgroup moves 64 channels x 128
 //                            samples at a time through LDS so that global loads and stores stay coalesced along the channel rows
 // ---------------------------------------------------------------------------------------------
@@ -229,6 +233,14 @@ struct DeemphArgs {
   short *avg;   // one per channel, updated in place (each channel has exactly one lane)
   unsigned magic;   // floor(2^32 / alpha) + 1: trunc(m / alpha) = umulhi(m, magic) for m < 2^16 (alpha < 2^15)
 };
+// A de-emphasis node per channel (sdrhip_deemphbank_i16_create): one flag per row. The kernels below are written once and
+// instantiated twice, BANK = false on DeemphArgs — the one-parameter handle's kernels, compiled as they always were — and
+// BANK = true on these. A row whose flag is 0 is the reference node after enable(false) (src/demod.hh:328): its samples pass
+// through — the same loads and stores with the arithmetic left out — and its average is neither read nor written.
+struct DeemphBankArgs : DeemphArgs { const unsigned char *en; };
+template <bool BANK> using DeemphArgsOf = std::conditional_t<BANK, DeemphBankArgs, DeemphArgs>;
+__device__ __forceinline__ constexpr bool deemph_on(const DeemphArgs &, int) { return true; }
+__device__ __forceinline__ bool deemph_on(const DeemphBankArgs &a, int c) { return a.en[c] != 0; }
 
 // The recursion as a latency chain, nothing else: one lane walks one channel's row in registers — 16-byte loads, DE_PF chunks
 // of 8 samples in flight ahead of the arithmetic (a lane's loads are its own row: uncoalesced, but a buffer of demodulated
@@ -278,12 +290,14 @@ __device__ __forceinline__ void deemph_chunk(uint32_t (&w)[4], int &avg, int hal
   }
   avg = (int)(short)avg;
 }
-__global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgs a) {
+template <bool BANK>
+__global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgsOf<BANK> a) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= a.C) return;
+  const bool on = deemph_on(a, c);
   const short *in = a.in + (long)c * a.in_stride;
   short *out = a.out + (long)c * a.out_stride;
-  int avg = (int)a.avg[c];
+  int avg = on ? (int)a.avg[c] : 0;
   const int half = a.alpha / 2;
   const unsigned magic = a.magic;
   // the row's samples before its first 16-byte boundary (0 .. 7, a lane's own count), one by one
@@ -293,7 +307,7 @@ __global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgs a) 
 #pragma unroll
     for (int j = 0; j < 7; j++) hd[j] = in[min(j, max(head - 1, 0))];   // (all loads first: one latency)
 #pragma unroll
-    for (int j = 0; j < 7; j++) if (j < head) out[j] = (short)deemph_step((int)hd[j], avg, half, magic);
+    for (int j = 0; j < 7; j++) if (j < head) out[j] = on ? (short)deemph_step((int)hd[j], avg, half, magic) : hd[j];
   }
   const int nch = (a.N - head) >> 3;   // whole 16-byte chunks of 8 samples
   const uint4 *in4 = reinterpret_cast<const uint4 *>(in + head);
@@ -312,7 +326,7 @@ __global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgs a) 
     for (int k = 0; k < DE_PF; k++) {
       if (g + k < nch) {
         uint32_t w[4] = {cur[k].x, cur[k].y, cur[k].z, cur[k].w};
-        deemph_chunk(w, avg, half, magic);
+        if (on) deemph_chunk(w, avg, half, magic);
         if (out16) reinterpret_cast<uint4 *>(o8)[g + k] = make_uint4(w[0], w[1], w[2], w[3]);
         else {
 #pragma unroll
@@ -329,9 +343,9 @@ __global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgs a) 
 #pragma unroll
     for (int j = 0; j < 7; j++) tl[j] = in[done + min(j, rem - 1)];
 #pragma unroll
-    for (int j = 0; j < 7; j++) if (j < rem) out[done + j] = (short)deemph_step((int)tl[j], avg, half, magic);
+    for (int j = 0; j < 7; j++) if (j < rem) out[done + j] = on ? (short)deemph_step((int)tl[j], avg, half, magic) : tl[j];
   }
-  a.avg[c] = (short)avg;
+  if (on) a.avg[c] = (short)avg;
 }
 
 // The same chain, cut in time. The recursion cannot be split exactly ahead of time — but it forgets: two runs over the same
@@ -345,7 +359,7 @@ __global__ __launch_bounds__(64) void deemph_i16_seq_kernel(const DeemphArgs a) 
 // checks again). The result is the sequential recursion's, bit for bit, whatever the data; what the data decides is the
 // time: (n / P + 8 wc) steps when the guesses hold, at worst (constant rows sit inside the rounding dead zone and never
 // meet) one sequential pass on top.
-struct DeemphSpecArgs { DeemphArgs d; int lgP, Lc, wc; };
+template <bool BANK> struct DeemphSpecArgs { DeemphArgsOf<BANK> d; int lgP, Lc, wc; };
 __device__ __forceinline__ void deemph_store(short *o8, bool out16, int id, const uint32_t (&w)[4]) {
   if (out16) reinterpret_cast<uint4 *>(o8)[id] = make_uint4(w[0], w[1], w[2], w[3]);
   else {
@@ -353,13 +367,18 @@ __device__ __forceinline__ void deemph_store(short *o8, bool out16, int id, cons
     for (int j = 0; j < 4; j++) { o8[8 * id + 2 * j] = (short)(w[j] & 0xffffu); o8[8 * id + 2 * j + 1] = (short)(w[j] >> 16); }
   }
 }
-__global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecArgs sa) {
+// BANK: the flag is uniform over a row's P lanes but not over the wave, so the lanes of a disabled row go through every
+// wave-wide step (shuffle, vote, ballot, barrier) with the others: they copy their segments in the pass, never ask for a
+// repair (their "state" is nobody's), and their row is never given up.
+template <bool BANK>
+__global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecArgs<BANK> sa) {
   __shared__ int redo_from[128], redo_state[128];   // per channel of the workgroup (at most 128: P >= 2): where a given-up row resumes
-  const DeemphArgs &a = sa.d;
+  const DeemphArgsOf<BANK> &a = sa.d;
   const int P = 1 << sa.lgP, Lc = sa.Lc;
   const int lin = blockIdx.x * 256 + threadIdx.x;
   const bool live = (lin >> sa.lgP) < a.C;
   const int c = min(lin >> sa.lgP, a.C - 1), p = lin & (P - 1);   // (lanes beyond the last channel shadow it, without stores)
+  const bool on = deemph_on(a, c);
   const short *in = a.in + (long)c * a.in_stride;
   short *out = a.out + (long)c * a.out_stride;
   const int half = a.alpha / 2;
@@ -372,12 +391,12 @@ __global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecAr
   const int c0 = p * Lc;                          // the lane's first chunk; its segment: [c0, min(c0 + Lc, nch))
   int avg;
   if (p == 0) {                                   // the channel's first lane: the true state, and the samples before the first chunk
-    avg = (int)a.avg[c];
+    avg = on ? (int)a.avg[c] : 0;
     short hd[7];
 #pragma unroll
     for (int j = 0; j < 7; j++) hd[j] = in[min(j, max(head - 1, 0))];
 #pragma unroll
-    for (int j = 0; j < 7; j++) if (j < head) { const int y = deemph_step((int)hd[j], avg, half, magic); if (live) out[j] = (short)y; }
+    for (int j = 0; j < 7; j++) if (j < head) { const int y = on ? deemph_step((int)hd[j], avg, half, magic) : (int)hd[j]; if (live) out[j] = (short)y; }
   } else avg = (int)(in + head)[8 * min(max(c0 - sa.wc, 0), max(nch - 1, 0))];   // the guess: the sample the run-in starts at
   int s = avg, f;
   uint4 cur[DE_PF];
@@ -393,7 +412,7 @@ __global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecAr
       const int id = c0 + g + k;
       if (id >= 0 && id < nch && g + k < Lc && (p > 0 || g >= 0)) {
         uint32_t w[4] = {cur[k].x, cur[k].y, cur[k].z, cur[k].w};
-        deemph_chunk(w, avg, half, magic);
+        if (on) deemph_chunk(w, avg, half, magic);
         if (g >= 0 && live) deemph_store(o8, out16, id, w);
       }
     }
@@ -405,7 +424,7 @@ __global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecAr
   bool given_up = false;
   for (int it = 1; it < P; it++) {
     const int pf = __shfl_up(f, 1, 64);
-    const bool need = !given_up && p > 0 && pf != s;
+    const bool need = !given_up && p > 0 && pf != s && on;
     if (!__any(need)) break;
     bool unmet = false;
     if (need) {
@@ -458,9 +477,9 @@ __global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecAr
 #pragma unroll
       for (int j = 0; j < 7; j++) tl[j] = in[done + min(j, rem - 1)];
 #pragma unroll
-      for (int j = 0; j < 7; j++) if (j < rem) { const int y = deemph_step((int)tl[j], avg, half, magic); if (live) out[done + j] = (short)y; }
+      for (int j = 0; j < 7; j++) if (j < rem) { const int y = on ? deemph_step((int)tl[j], avg, half, magic) : (int)tl[j]; if (live) out[done + j] = (short)y; }
     }
-    if (live) a.avg[c] = (short)avg;
+    if (live && on) a.avg[c] = (short)avg;
   }
   // The rows that were given up, one per LANE of the workgroup's first wave: a wave's chain keeps its SIMD's issue port busy
   // whatever the number of active lanes (about 14 instructions of 4 cycles per step), so the walkers are packed — left in
@@ -517,12 +536,13 @@ __global__ __launch_bounds__(256) void deemph_i16_spec_kernel(const DeemphSpecAr
 
 // alpha = 1 (sample rates below about 11 kS/s: src/demod.hh:305-306 rounds 1 / (1 - exp(-1 / (Fs 75 us))) to 1): the
 // update is avg = x exactly — a copy, and the last sample as the state
-__global__ __launch_bounds__(256) void deemph_i16_copy_kernel(const DeemphArgs a) {
+template <bool BANK>
+__global__ __launch_bounds__(256) void deemph_i16_copy_kernel(const DeemphArgsOf<BANK> a) {
   const int c = blockIdx.y;
   const short *in = a.in + (long)c * a.in_stride;
   short *out = a.out + (long)c * a.out_stride;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < a.N; i += gridDim.x * 256) out[i] = in[i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.avg[c] = in[a.N - 1];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && deemph_on(a, c)) a.avg[c] = in[a.N - 1];
 }
 
 __global__ __launch_bounds__(DE_CH) void deemph_i16_kernel(const DeemphArgs a) {
@@ -631,6 +651,11 @@ struct sdrhip_deemph {
   size_t max_in = 0;
   DevBuf<short> avg;
   Staging stage;
+  // a de-emphasis node per channel (sdrhip_deemphbank_i16_create): one flag per row, on the device for the kernels (written
+  // stream-ordered by set_enabled) and on the host for get_enabled; the calls launch the kernels' BANK instances
+  bool bank = false;
+  std::vector<unsigned char> en_host;
+  DevBuf<unsigned char> en;
   // which kernel a call of N samples per channel runs: 0 copy (alpha = 1), 1 one lane per channel, 2 P = 2^lgP lanes per
   // channel (long rows of a filter that forgets fast: the run-in is 16 alpha samples — measured on noise-like rows, two
   // runs meet within about 12 alpha — in whole groups of 64; P is the largest of 32 … 4 whose segments are at least as
@@ -665,19 +690,35 @@ struct sdrhip_deemph {
     a.magic = (unsigned)((1ull << 32) / (unsigned)alpha) + 1u;   // (alpha = 1 never divides)
     int lgP = 0, wc = 0;
     const int k = plan(N, &lgP, &wc);
-    if (k == 0)
-      hipLaunchKernelGGL(deemph_i16_copy_kernel, dim3((unsigned)std::min<size_t>(ceil_div(N, (size_t)256), 64), C), dim3(256), 0, ctx->stream, a);
-    else if (k == 2) {
-      DeemphSpecArgs sa;
-      sa.d = a; sa.lgP = lgP; sa.Lc = ((int)(N / 8) + (1 << lgP) - 1) >> lgP; sa.wc = wc;
-      hipLaunchKernelGGL(deemph_i16_spec_kernel, dim3((unsigned)ceil_div((size_t)C << lgP, (size_t)256)), dim3(256), 0, ctx->stream, sa);
-    } else if (k == 1)
-      hipLaunchKernelGGL(deemph_i16_seq_kernel, dim3((unsigned)ceil_div((size_t)C, (size_t)64)), dim3(64), 0, ctx->stream, a);
-    else
+    // (the check behind the launch is for this launch: an error that an earlier, unrelated call of the process left in the
+    // runtime's last-error slot — a handle destroyed after its context, another library's failed query — is not its)
+    (void)hipGetLastError();
+    DeemphBankArgs b;
+    static_cast<DeemphArgs &>(b) = a; b.en = en.p;
+    const dim3 copy_grid((unsigned)std::min<size_t>(ceil_div(N, (size_t)256), 64), C), seq_grid((unsigned)ceil_div((size_t)C, (size_t)64));
+    if (k == 0) {
+      if (bank) hipLaunchKernelGGL(deemph_i16_copy_kernel<true>, copy_grid, dim3(256), 0, ctx->stream, b);
+      else hipLaunchKernelGGL(deemph_i16_copy_kernel<false>, copy_grid, dim3(256), 0, ctx->stream, a);
+    } else if (k == 2) {
+      const dim3 spec_grid((unsigned)ceil_div((size_t)C << lgP, (size_t)256));
+      const int Lc = ((int)(N / 8) + (1 << lgP) - 1) >> lgP;
+      if (bank) hipLaunchKernelGGL(deemph_i16_spec_kernel<true>, spec_grid, dim3(256), 0, ctx->stream, DeemphSpecArgs<true>{b, lgP, Lc, wc});
+      else hipLaunchKernelGGL(deemph_i16_spec_kernel<false>, spec_grid, dim3(256), 0, ctx->stream, DeemphSpecArgs<false>{a, lgP, Lc, wc});
+    } else if (k == 1) {
+      if (bank) hipLaunchKernelGGL(deemph_i16_seq_kernel<true>, seq_grid, dim3(64), 0, ctx->stream, b);
+      else hipLaunchKernelGGL(deemph_i16_seq_kernel<false>, seq_grid, dim3(64), 0, ctx->stream, a);
+    } else
       hipLaunchKernelGGL(deemph_i16_kernel, dim3((unsigned)ceil_div((size_t)C, (size_t)DE_CH)), dim3(DE_CH), 0, ctx->stream, a);
     SDRHIP_CHECK_HIP(hipGetLastError());
   }
 };
+
+// what the receiver bank (rxbank.hip) asks of a de-emphasis handle
+namespace sdrhip {
+sdrhip_ctx *handle_ctx(const sdrhip_deemph *h) { return h->ctx; }
+int handle_channels(const sdrhip_deemph *h) { return h->C; }
+size_t handle_max_in(const sdrhip_deemph *h) { return h->max_in; }
+}  // namespace sdrhip
 
 extern "C" {
 
@@ -751,6 +792,52 @@ int sdrhip_deemph_i16_create(sdrhip_ctx *ctx, int alpha, int channels, size_t ma
   });
 }
 
+int sdrhip_deemphbank_i16_create(sdrhip_ctx *ctx, int alpha, const int *enabled, int channels, size_t max_in, sdrhip_deemph **out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && enabled, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(alpha >= 1 && alpha <= 32767, SDRHIP_E_INVALID, "alpha %d outside [1,32767]", alpha);
+    require_channels(channels, 8192);
+    require_max_in(max_in);
+    require_device_for_null_ctx(ctx);
+    make_handle(ctx, out, true, [&](sdrhip_deemph *h) {
+      h->alpha = alpha; h->C = channels; h->max_in = max_in; h->read_env();
+      h->bank = true; h->env_tiled = false;   // (the LDS-tiled parity form has no bank instance)
+      h->en_host.resize((size_t)channels);
+      for (int c = 0; c < channels; c++) h->en_host[c] = enabled[c] ? 1 : 0;
+      h->en.alloc((size_t)channels);
+      h->en.upload(h->en_host.data(), h->en_host.size(), ctx->stream);
+      h->avg.alloc(channels); h->avg.zero(ctx->stream);
+    });
+  });
+}
+
+static void require_deemph_bank(const sdrhip_deemph *h) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  SDRHIP_REQUIRE(h->bank, SDRHIP_E_UNSUPPORTED,
+                 "the handle has one de-emphasis for all channels (sdrhip_deemphbank_i16_create makes one per channel)");
+}
+
+// (one byte, set on the context's stream: behind the calls already enqueued, and no other row's flag is touched)
+int sdrhip_deemphbank_i16_set_enabled(sdrhip_deemph *h, int channel, int enabled) {
+  return guarded([&] {
+    require_deemph_bank(h);
+    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    h->ctx->use();
+    SDRHIP_CHECK_HIP(hipMemsetAsync(h->en.p + channel, enabled ? 1 : 0, 1, h->ctx->stream));
+    h->en_host[channel] = enabled ? 1 : 0;
+  });
+}
+
+int sdrhip_deemphbank_i16_get_enabled(sdrhip_deemph *h, int *enabled, int n) {
+  return guarded([&] {
+    require_deemph_bank(h);
+    SDRHIP_REQUIRE(enabled, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(n >= h->C, SDRHIP_E_SIZE, "n %d < channels %d", n, h->C);
+    for (int c = 0; c < h->C; c++) enabled[c] = h->en_host[c];
+  });
+}
+
 int sdrhip_deemph_i16_process_dev(sdrhip_deemph *h, const int16_t *in_dev, size_t n, size_t in_stride, int16_t *out_dev,
                                   size_t out_stride) {
   return guarded([&] {
@@ -781,7 +868,9 @@ int sdrhip_deemph_i16_kernel_names(sdrhip_deemph *h, size_t n, char *buf, size_t
   return guarded([&] {
     SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
     static const char *const nm[4] = {"deemph_i16_copy_kernel", "deemph_i16_seq_kernel", "deemph_i16_spec_kernel", "deemph_i16_kernel"};
-    snprintf(buf, len, "%s", nm[h->plan(n ? n : h->max_in, nullptr, nullptr)]);
+    static const char *const bnm[3] = {"deemphbank_i16_copy_kernel", "deemphbank_i16_seq_kernel", "deemphbank_i16_spec_kernel"};
+    const int k = h->plan(n ? n : h->max_in, nullptr, nullptr);
+    snprintf(buf, len, "%s", h->bank ? bnm[k] : nm[k]);
   });
 }
 
@@ -795,6 +884,7 @@ int sdrhip_deemph_i16_reset(sdrhip_deemph *h) {
 int sdrhip_deemph_i16_destroy(sdrhip_deemph *h) {
   return guarded([&] { destroy_handle(h); });
 }
+
 
 int sdrhip_subsample_create(sdrhip_ctx *ctx, int dtype, size_t n, int channels, size_t max_in, sdrhip_subsample **out) {
   return guarded([&] {

@@ -35,6 +35,7 @@ struct Failure {
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) {                                                                 \
+      (void)hipGetLastError(); /* reported here, once: not left for the next launch's check */ \
       int c_ = (e_ == hipErrorOutOfMemory) ? SDRHIP_E_NOMEM                                 \
                : (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? SDRHIP_E_NODEVICE \
                                                                          : SDRHIP_E_HIP;    \
@@ -205,6 +206,25 @@ void fir_clear_log(sdrhip_fir *h);   // a call of the float baseband that launch
 void fir_launch(sdrhip_fir *h, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride, size_t *n_out);
 int fir_create_impl(sdrhip_ctx *ctx, int kind, const double *alpha, int order, int decim, int channels, size_t max_in, int epilogue,
                     bool allow_fft, sdrhip_fir **out);
+
+// The receiver bank (rxbank.hip) composes handles whose structs are private to their files. What it needs to know of each —
+// context, channels, the largest call — is answered by these, each defined next to its struct; of the tuner also the
+// decimation, whether its rows are cs16 (SDRHIP_EPI_NONE) or demodulated int16, and its input's element size.
+sdrhip_ctx *handle_ctx(const sdrhip_tuner_i16 *h);
+sdrhip_ctx *handle_ctx(const sdrhip_deemph *h);
+sdrhip_ctx *handle_ctx(const sdrhip_detector *h);
+sdrhip_ctx *handle_ctx(const sdrhip_bits *h);
+int handle_channels(const sdrhip_tuner_i16 *h);
+int handle_channels(const sdrhip_deemph *h);
+int handle_channels(const sdrhip_detector *h);
+int handle_channels(const sdrhip_bits *h);
+size_t handle_max_in(const sdrhip_tuner_i16 *h);
+size_t handle_max_in(const sdrhip_deemph *h);
+size_t handle_max_in(const sdrhip_detector *h);
+size_t handle_max_in(const sdrhip_bits *h);
+int tuner_decim(const sdrhip_tuner_i16 *h);
+int tuner_epilogue(const sdrhip_tuner_i16 *h);
+size_t tuner_in_elem_bytes(const sdrhip_tuner_i16 *h);   // of one antenna sample, as the bank is set to read it
 
 #ifdef __HIPCC__
 // XCD-aware unit order for grids of (units-per-channel, channels) whose neighbouring units of a channel re-read each

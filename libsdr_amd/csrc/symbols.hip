@@ -554,6 +554,16 @@ struct sdrhip_bits {
   }
 };
 
+// what the receiver bank (rxbank.hip) asks of the handles of this file
+namespace sdrhip {
+sdrhip_ctx *handle_ctx(const sdrhip_detector *h) { return h->ctx; }
+sdrhip_ctx *handle_ctx(const sdrhip_bits *h) { return h->ctx; }
+int handle_channels(const sdrhip_detector *h) { return h->C; }
+int handle_channels(const sdrhip_bits *h) { return h->C; }
+size_t handle_max_in(const sdrhip_detector *h) { return h->max_in; }
+size_t handle_max_in(const sdrhip_bits *h) { return h->max_in; }
+}  // namespace sdrhip
+
 extern "C" {
 
 int sdrhip_detector_create(sdrhip_ctx *ctx, int kind, const float *mark_lut, const float *space_lut, int corr_len, int invert,

@@ -611,6 +611,16 @@ static void tuner_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const 
   });
 }
 
+// what the receiver bank (rxbank.hip) asks of a tuner bank
+namespace sdrhip {
+sdrhip_ctx *handle_ctx(const sdrhip_tuner_i16 *h) { return h->ctx; }
+int handle_channels(const sdrhip_tuner_i16 *h) { return h->C; }
+size_t handle_max_in(const sdrhip_tuner_i16 *h) { return h->max_in; }
+int tuner_decim(const sdrhip_tuner_i16 *h) { return h->D; }
+int tuner_epilogue(const sdrhip_tuner_i16 *h) { return h->epi; }
+size_t tuner_in_elem_bytes(const sdrhip_tuner_i16 *h) { return h->in_elem_bytes(); }
+}  // namespace sdrhip
+
 extern "C" {
 
 int sdrhip_tuner_i16_create(sdrhip_ctx *ctx, const int32_t *taps, int order, const int32_t *lut, const uint32_t *lut_inc,
