@@ -369,11 +369,18 @@ int sdrhip_fir_create(sdrhip_ctx *ctx, int kind, const double *alpha, int order,
 int sdrhip_fir_out_count(sdrhip_fir *h, size_t n_in, size_t *n_out);
 /* The kernel a call of n_in samples per channel runs (0: the plan's max_in), for profiles and tests:
  * "fir_cs16_exact_kernel"; complex<float>: "fir_cf32_pipe_kernel" (decimation 8 and enough tiles to give every
- * workgroup several: consecutive tiles software-pipelined in one workgroup) or "fir_cf32_rt_kernel". */
+ * workgroup several: consecutive tiles software-pipelined in one workgroup) or "fir_cf32_rt_kernel". These are the BARE
+ * names, without template arguments: what to look for in a kernel trace. Which instance ran is sdrhip_fir_last_kernels'
+ * to say. */
 int sdrhip_fir_kernel_names(sdrhip_fir *h, size_t n_in, char *buf, size_t len);
 /* The kernels the handle's most recent process / process_dev call launched, comma-separated in launch order ("" before the
  * first call and after a call of 0 samples). A complex<float> plan that runs as FFT convolution answers as
- * sdrhip_fftconv_last_kernels does for its inner plan; every other plan with its time-domain kernels' names. */
+ * sdrhip_fftconv_last_kernels does for its inner plan; every other plan with its time-domain kernels, each spelled as the
+ * INSTANCE the launch took (template arguments comma-separated without spaces, bools as 0/1; names are separated by the
+ * commas OUTSIDE angle brackets): "fir_cs16_exact_kernel<WRAP,R2>" (<0|1,4|8>), "fir_cf32_rt_kernel<R,DC>" (<4,0>, <2,0>,
+ * <1,0>, <4,8>, <2,8>), "fir_cf32_pipe_kernel<R,8>" (<4,8>, <2,8>); "tile_phasor_kernel" in front of the FIR kernel when a
+ * call of the fused shift has more than 32 tiles; "hist_roll_cf32" alone for a call that completes no output. The prefix
+ * of the FIR kernel's entry up to '<' is what sdrhip_fir_kernel_names answers for a call of that length. */
 int sdrhip_fir_last_kernels(sdrhip_fir *h, char *buf, size_t len);
 int sdrhip_fir_process(sdrhip_fir *h, const void *in_host, size_t n_in, size_t in_stride, void *out_host,
                        size_t out_stride, size_t *n_out);
@@ -678,8 +685,8 @@ int sdrhip_fftsource_destroy(sdrhip_fftsource *h);
 int sdrhip_fbb_f32_create(sdrhip_ctx *ctx, double Fc, double Fs, const double *alpha, int order, int decim,
                           int channels, size_t max_in, sdrhip_fbb_f32 **out);
 int sdrhip_fbb_f32_out_count(sdrhip_fbb_f32 *h, size_t n_in, size_t *n_out);
-int sdrhip_fbb_f32_kernel_names(sdrhip_fbb_f32 *h, size_t n_in, char *buf, size_t len);   /* as sdrhip_fir_kernel_names */
-int sdrhip_fbb_f32_last_kernels(sdrhip_fbb_f32 *h, char *buf, size_t len);                 /* as sdrhip_fir_last_kernels */
+int sdrhip_fbb_f32_kernel_names(sdrhip_fbb_f32 *h, size_t n_in, char *buf, size_t len);   /* as sdrhip_fir_kernel_names: bare names, for a trace */
+int sdrhip_fbb_f32_last_kernels(sdrhip_fbb_f32 *h, char *buf, size_t len);                 /* as sdrhip_fir_last_kernels: the instances the call ran */
 int sdrhip_fbb_f32_process(sdrhip_fbb_f32 *h, const float *in_host, size_t n_in, size_t in_stride,
                            float *out_host, size_t out_stride, size_t *n_out);
 int sdrhip_fbb_f32_process_dev(sdrhip_fbb_f32 *h, const float *in_dev, size_t n_in, size_t in_stride,

@@ -165,18 +165,15 @@ __global__ __launch_bounds__(TPB) void fir_cs16_exact_kernel(const Fir16Args a) 
 // =============================================================================================
 // K3: complex<float> FIR, decimation folded (outputs at absolute input indices g*D + D-1)
 // =============================================================================================
-constexpr int T3 = TPB;   // one output per lane and tile pass
-
 struct Fir32Args {
   const float2 *in; long in_stride;
   const float2 *hist_old; float2 *hist_new; int HH;   // HH = M-1
-  const float *beta;     // M folded taps (float), beta[M-1] meets the newest sample
   int M, D, N;
   int first_rel;   // call-relative index of the newest sample of the first output of this call
   int n_out;
   void *out; long out_stride; int epilogue;
   // register-tiled kernel
-  const float *betap;      // beta with (R-1)*D zeros on either side
+  const float *betap;      // the M folded taps (float, beta[M-1] meets the newest sample) with (R-1)*D zeros on either side
   unsigned rd_magic;       // ceil(2^32 / (R*D)): i / (R*D) = umulhi(i, rd_magic) for the tile's i
   // fused frequency shift (float baseband, fbb_f32.hip): x[n] * exp(-2 pi i fc n / fs), n = absolute sample index
   // The phase of sample i of a tile (absolute index n = n_tile + i, i = t + TPB*k) splits into three exact factors:
@@ -195,38 +192,6 @@ __device__ __forceinline__ float2 load_x32(const Fir32Args &a, int c, int rel) {
   if (rel >= 0) return rel < a.N ? a.in[(long)c * a.in_stride + rel] : make_float2(0.f, 0.f);
   const int h = a.HH + rel;
   return h >= 0 ? a.hist_old[(long)c * a.HH + h] : make_float2(0.f, 0.f);
-}
-
-__global__ __launch_bounds__(TPB) void fir_cf32_kernel(const Fir32Args a) {
-  extern __shared__ __attribute__((aligned(16))) float2 smemf[];
-  float2 *xs = smemf;   // xs[i] = x[base-(M-1)+i], base = newest sample of the tile's first output
-  const int c = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-  const int j0 = tile * T3;
-  const int outs_here = min(T3, a.n_out - j0);
-  const int base = a.first_rel + j0 * a.D;
-  if (outs_here > 0) {
-    const int need = (outs_here - 1) * a.D + a.M;
-    for (int i = tid; i < need; i += TPB) xs[i] = load_x32(a, c, base - (a.M - 1) + i);
-  }
-  __syncthreads();
-  if (tid < outs_here) {
-    const float2 *px = xs + tid * a.D;
-    const float *__restrict__ b = a.beta;
-    float sr0 = 0.f, si0 = 0.f, sr1 = 0.f, si1 = 0.f;
-    int m = 0;
-    for (; m + 1 < a.M; m += 2) {
-      const float2 x0 = px[m], x1 = px[m + 1];
-      const float b0 = b[m], b1 = b[m + 1];
-      sr0 = __builtin_fmaf(b0, x0.x, sr0); si0 = __builtin_fmaf(b0, x0.y, si0);
-      sr1 = __builtin_fmaf(b1, x1.x, sr1); si1 = __builtin_fmaf(b1, x1.y, si1);
-    }
-    if (m < a.M) { const float2 x0 = px[m]; const float b0 = b[m]; sr0 = __builtin_fmaf(b0, x0.x, sr0); si0 = __builtin_fmaf(b0, x0.y, si0); }
-    const float yr = sr0 + sr1, yi = si0 + si1;
-    const int j = j0 + tid;
-    if (a.epilogue == SDRHIP_EPI_NONE) reinterpret_cast<float2 *>(a.out)[(long)c * a.out_stride + j] = make_float2(yr, yi);
-    else if (a.epilogue == SDRHIP_EPI_AM) reinterpret_cast<float *>(a.out)[(long)c * a.out_stride + j] = sqrtf(yr * yr + yi * yi);
-    else reinterpret_cast<float *>(a.out)[(long)c * a.out_stride + j] = (yr + yi) / 2;
-  }
 }
 
 // Register-tiled form: a lane owns R consecutive outputs (R*D input samples apart from its neighbour's) and walks
@@ -617,7 +582,7 @@ struct sdrhip_fir {
   // K3
   int M = 0, R = 1;
   bool pipe = true;   // D = 8: several tiles per workgroup, software-pipelined (SDRHIP_FIR_PIPE=0: one tile per workgroup, tuning/tests)
-  DevBuf<float> beta, betap;
+  DevBuf<float> betap;
   size_t lds3 = 0;
   // fused frequency shift (set by the float baseband)
   // complex<float>, no decimation, no demodulator: the filter runs as overlap-save FFT convolution behind this handle (see create)
@@ -670,21 +635,21 @@ struct sdrhip_fir {
       const int tiles = (int)ceil_div(N, (size_t)a.OT);
       const size_t lds = ((size_t)T2 + OP + 8 + T2) * 4;
       dim3 grid(tiles, C), block(TPB);
+      // (the record's spelling of the instance is written in the branch that launches it: sdrhip_fir_last_kernels)
       if (R2 == 8) {
-        if (wrap) hipLaunchKernelGGL((fir_cs16_exact_kernel<true, 8>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((fir_cs16_exact_kernel<false, 8>), grid, block, lds, ctx->stream, a);
+        if (wrap) { hipLaunchKernelGGL((fir_cs16_exact_kernel<true, 8>), grid, block, lds, ctx->stream, a); log.add("fir_cs16_exact_kernel<1,8>"); }
+        else { hipLaunchKernelGGL((fir_cs16_exact_kernel<false, 8>), grid, block, lds, ctx->stream, a); log.add("fir_cs16_exact_kernel<0,8>"); }
       } else {
-        if (wrap) hipLaunchKernelGGL((fir_cs16_exact_kernel<true, 4>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((fir_cs16_exact_kernel<false, 4>), grid, block, lds, ctx->stream, a);
+        if (wrap) { hipLaunchKernelGGL((fir_cs16_exact_kernel<true, 4>), grid, block, lds, ctx->stream, a); log.add("fir_cs16_exact_kernel<1,4>"); }
+        else { hipLaunchKernelGGL((fir_cs16_exact_kernel<false, 4>), grid, block, lds, ctx->stream, a); log.add("fir_cs16_exact_kernel<0,4>"); }
       }
-      log.add("fir_cs16_exact_kernel");
       SDRHIP_CHECK_HIP(hipGetLastError());
       if (epi == SDRHIP_EPI_FM && N >= 2) par_fm ^= 1;
     } else {
       Fir32Args a;
       a.in = (const float2 *)in_dev; a.in_stride = (long)in_stride;
       a.hist_old = hist32[par].p; a.hist_new = hist32[par ^ 1].p; a.HH = M - 1;
-      a.beta = beta.p; a.M = M; a.D = D; a.N = (int)N;
+      a.M = M; a.D = D; a.N = (int)N;
       // first output of this call: group g = n0/D completes at absolute index g*D + D-1 >= n0
       const uint64_t g = n0 / (uint64_t)D;
       a.first_rel = (int)((int64_t)(g * D + D - 1) - (int64_t)n0);
@@ -716,14 +681,13 @@ struct sdrhip_fir {
         const int tpw = pipe_tpw(tiles);
         a.tiles = tiles; a.tpw = tpw;
         dim3 gridp((unsigned)ceil_div((size_t)tiles, (size_t)tpw), C);
-        if (R == 4 && D == 8 && tpw > 1) hipLaunchKernelGGL((fir_cf32_pipe_kernel<4, 8>), gridp, block, lds3, ctx->stream, a);
-        else if (R == 2 && D == 8 && tpw > 1) hipLaunchKernelGGL((fir_cf32_pipe_kernel<2, 8>), gridp, block, lds3, ctx->stream, a);
-        else if (R == 4 && D == 8) hipLaunchKernelGGL((fir_cf32_rt_kernel<4, 8>), grid, block, lds3, ctx->stream, a);
-        else if (R == 2 && D == 8) hipLaunchKernelGGL((fir_cf32_rt_kernel<2, 8>), grid, block, lds3, ctx->stream, a);
-        else if (R == 4) hipLaunchKernelGGL((fir_cf32_rt_kernel<4, 0>), grid, block, lds3, ctx->stream, a);
-        else if (R == 2) hipLaunchKernelGGL((fir_cf32_rt_kernel<2, 0>), grid, block, lds3, ctx->stream, a);
-        else hipLaunchKernelGGL((fir_cf32_rt_kernel<1, 0>), grid, block, lds3, ctx->stream, a);
-        log.add(D == 8 && (R == 4 || R == 2) && tpw > 1 ? "fir_cf32_pipe_kernel" : "fir_cf32_rt_kernel");
+        if (R == 4 && D == 8 && tpw > 1) { hipLaunchKernelGGL((fir_cf32_pipe_kernel<4, 8>), gridp, block, lds3, ctx->stream, a); log.add("fir_cf32_pipe_kernel<4,8>"); }
+        else if (R == 2 && D == 8 && tpw > 1) { hipLaunchKernelGGL((fir_cf32_pipe_kernel<2, 8>), gridp, block, lds3, ctx->stream, a); log.add("fir_cf32_pipe_kernel<2,8>"); }
+        else if (R == 4 && D == 8) { hipLaunchKernelGGL((fir_cf32_rt_kernel<4, 8>), grid, block, lds3, ctx->stream, a); log.add("fir_cf32_rt_kernel<4,8>"); }
+        else if (R == 2 && D == 8) { hipLaunchKernelGGL((fir_cf32_rt_kernel<2, 8>), grid, block, lds3, ctx->stream, a); log.add("fir_cf32_rt_kernel<2,8>"); }
+        else if (R == 4) { hipLaunchKernelGGL((fir_cf32_rt_kernel<4, 0>), grid, block, lds3, ctx->stream, a); log.add("fir_cf32_rt_kernel<4,0>"); }
+        else if (R == 2) { hipLaunchKernelGGL((fir_cf32_rt_kernel<2, 0>), grid, block, lds3, ctx->stream, a); log.add("fir_cf32_rt_kernel<2,0>"); }
+        else { hipLaunchKernelGGL((fir_cf32_rt_kernel<1, 0>), grid, block, lds3, ctx->stream, a); log.add("fir_cf32_rt_kernel<1,0>"); }
         SDRHIP_CHECK_HIP(hipGetLastError());
       }
       if (M > 1 && !no) {   // (a call that completes no output launches no tile: the history still rolls)
@@ -767,7 +731,6 @@ void fir_load_taps(sdrhip_fir *h, const double *alpha) {
     for (int k = 0; k < decim; k++) { const int i = m - k; if (i >= 0 && i < order) s += alpha[i]; }
     b[m] = (float)(s / decim);
   }
-  h->beta.upload(b.data(), h->M, h->ctx->stream);
   const int padz = (h->R - 1) * decim;
   std::vector<float> bpad((size_t)h->M + 2 * padz + 16, 0.f);
   for (int m = 0; m < h->M; m++) bpad[padz + m] = b[m];
@@ -866,7 +829,6 @@ int fir_create_impl(sdrhip_ctx *ctx, int kind, const double *alpha, int order, i
                                 (const void *)fir_cf32_pipe_kernel<4, 8>, (const void *)fir_cf32_pipe_kernel<2, 8>};
           for (int k = 0; k < 7; k++) allow_lds_max(fns[k], h->lds3);   // (once per kernel and device, to the hardware's maximum)
         }
-        h->beta.alloc(h->M);
         h->betap.alloc((size_t)h->M + 2 * (size_t)(h->R - 1) * decim + 16);
         fir_load_taps(h, alpha);
         for (int p = 0; p < 2; p++) {

@@ -124,20 +124,22 @@ def test_fftconv_class_case(ctx, case, monkeypatch):
 
 def test_time_domain_fir_and_float_baseband_report_their_kernels(ctx, monkeypatch):
     """sdrhip_fir_last_kernels / sdrhip_fbb_f32_last_kernels where the FIR does not run as FFT convolution: the time-domain
-    kernel of the last call, and the history roll of a call that completes no output."""
+    kernel instance of the last call, and the history roll of a call that completes no output (every instance:
+    tests/test_gpu_parity_fir_classes.py)."""
     rng = np.random.default_rng(9)
     alpha = rng.standard_normal(21) / 21
     x = (rng.standard_normal((2, 4096, 2)) * 0.3).astype(np.float32)
     fir = sa.FIR(ctx, sa.FIR_CF32, alpha, decim=1, channels=2, max_in=4096)     # (21 taps on a small plan: the time-domain kernel)
     assert fir.last_kernels() == []
     fir.process(x)
-    assert fir.last_kernels() == ["fir_cf32_rt_kernel"] and fir.kernel_names(4096) == ["fir_cf32_rt_kernel"]
+    assert fir.last_kernels() == ["fir_cf32_rt_kernel<4,0>"] and fir.kernel_names(4096) == ["fir_cf32_rt_kernel"]
     fir.process(x[:, :0])
     assert fir.last_kernels() == []
     fbb = sa.FloatBaseBand(ctx, 100e3, 2.4e6, alpha, 8, channels=2, max_in=4096)
     assert fbb.last_kernels() == []
     fbb.process(x)
-    assert fbb.last_kernels() == fbb.kernel_names(4096) and fbb.last_kernels()[0] in ("fir_cf32_rt_kernel", "fir_cf32_pipe_kernel")
+    ran = fbb.last_kernels()                                                   # the instance; kernel_names keeps the bare name
+    assert len(ran) == 1 and ran[0] in ("fir_cf32_rt_kernel<2,8>", "fir_cf32_pipe_kernel<2,8>") and [ran[0].split("<")[0]] == fbb.kernel_names(4096)
     fbb.process(x[:, :3])                                                      # 3 samples at /8: no output, the history rolls
     assert fbb.last_kernels() == ["hist_roll_cf32"]
     fbb.process(x[:, :0])
