@@ -73,6 +73,13 @@ public:
   Source *bits(size_t c) { return _bitOuts[c]; }
   Source *audio(size_t c) { return this->source(c); }
 
+  /** Read-only: the bit rows of the last processed buffer as they lie on the device — rows of deviceBitStride() bytes, row c
+   * holding deviceBitCounts()[c] bits (a device array too) — for a node that goes on from them there (gpu::POCSAGBank).
+   * Null before config(); valid until the next buffer, setService or addChannel. */
+  const uint8_t *deviceBitRows() const { return _rx ? _dbits.as<uint8_t>() + _hdr : 0; }
+  size_t deviceBitStride() const { return _cap; }
+  const uint32_t *deviceBitCounts() const { return _rx ? _dbits.as<uint32_t>() : 0; }
+
   /** Channel c's detector and bit stream become freshly configured nodes (sdrhip_detectorbank_set_channel,
    * sdrhip_bitsbank_set_channel), its de-emphasis is switched as the service says; bits(c) is configured anew. */
   void setService(size_t c, const Service &service) {

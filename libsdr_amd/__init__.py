@@ -9,5 +9,6 @@ from .abi import (EPI_NONE, EPI_FM, EPI_AM, EPI_USB, FIR_CS16_EXACT, FIR_CF32, T
                   FFTCONV_OLA, FFTCONV_OLS, DET_FSK, DET_ASK, BITS_NORMAL, BITS_TRANSITION, SdrHipError)
 from .nodes import *  # noqa: F401,F403
 from .receiver import FMDeemphBankI16, ReceiverBank  # noqa: F401
+from .pocsag import POCSAGBank, MessageAssembler, Message  # noqa: F401
 
 __version__ = "0.1.0"

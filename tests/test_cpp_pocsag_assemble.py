@@ -1,0 +1,27 @@
+"""The C++ message assembly of the POCSAG decoder bank (include/sdr/gpu/pocsag_message.hh) on the CPU: tests/cpp/
+test_pocsag_assemble.cc, a stand-alone program with its own main and no HIP, built with ASan/UBSan, fed the golden cases' event
+streams; what it releases at every END has to be what the reference delivered there — address, function, bits, payload, both
+scores and both readings."""
+import os
+import subprocess
+
+import pocsag_cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "tests", "_build")
+CXX = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
+SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+
+
+def test_message_assembly_under_sanitizers(tmp_path):
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "test_pocsag_assemble_san")
+    r = subprocess.run(CXX + SAN + [os.path.join(ROOT, "tests", "cpp", "test_pocsag_assemble.cc"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    n_cases, n_msgs = pocsag_cases.write_cases(tmp_path / "cases.txt")
+    assert n_cases >= 18 and n_msgs > 20
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe, str(tmp_path / "cases.txt")], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "%d cases, %d messages" % (n_cases, n_msgs) in r.stdout, r.stdout[-500:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
