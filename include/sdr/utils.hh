@@ -1,5 +1,6 @@
 // utils.hh — the capture sink the tests and examples record through (own code). The reference's helper nodes
-// (src/utils.hh: DebugStore, Scale, AGC, ...) are out of scope and have no counterpart here.
+// (src/utils.hh: DebugStore, Scale, Cast, ...) are out of scope and have no counterpart here — except AGC,
+// a per-sample recursion with state and no helper: its counterpart is sdr::gpu::AGC / AGCBank (sdr/gpu/agc.hh).
 #ifndef SDR_CORE_UTILS_HH
 #define SDR_CORE_UTILS_HH
 

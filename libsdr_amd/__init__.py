@@ -10,5 +10,6 @@ from .abi import (EPI_NONE, EPI_FM, EPI_AM, EPI_USB, FIR_CS16_EXACT, FIR_CF32, T
 from .nodes import *  # noqa: F401,F403
 from .receiver import FMDeemphBankI16, ReceiverBank  # noqa: F401
 from .pocsag import POCSAGBank, MessageAssembler, Message  # noqa: F401
+from .agc import AGC, AGCBank, design_agc_lambda, design_agc_target  # noqa: F401
 
 __version__ = "0.1.0"
