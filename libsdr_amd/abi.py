@@ -7,6 +7,7 @@ present, loading / context creation raises.
 import ctypes as C
 import os
 import re
+import types
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
@@ -32,11 +33,16 @@ class SdrHipError(RuntimeError):
         self.code = code
 
 
-def header_functions():
-    """Names of every function include/sdrhip.h declares (used by the symbol-export test)."""
-    src = open(HEADER).read()
+def declared_functions(header):
+    """Names of every function the C header at `header` declares."""
+    src = open(header).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(sdrhip_[a-z0-9_]+)\s*\(", src)))
+
+
+def header_functions():
+    """Names of every function include/sdrhip.h declares (used by the symbol-export test)."""
+    return declared_functions(HEADER)
 
 
 def _signatures():
@@ -242,6 +248,32 @@ def lib():
         L._declared = sorted(SIGNATURES)
         _lib = L
     return _lib
+
+
+# The headers beside sdrhip.h, each bound by a module of its own (abi_rx, abi_pocsag, abi_agc, abi_psk31): file name ->
+# what bind_header returned. SIGNATURES above and the library's `_declared` list stay the binding of sdrhip.h alone, and no
+# side module's table is touched by another's.
+SIDE_HEADERS = {}
+
+
+def bind_header(file_name, signatures):
+    """The binding of include/<file_name>: HEADER (its path), SIGNATURES, header_functions() (the names it declares) and
+    lib() = abi.lib() with `signatures` on its function objects — applied once per loaded library."""
+    header = os.path.join(ROOT, "include", file_name)
+    applied = [None]
+
+    def side_lib():
+        L = lib()
+        if applied[0] is not L:
+            for name, (res, args) in signatures.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = res, args
+            applied[0] = L
+        return L
+
+    SIDE_HEADERS[file_name] = types.SimpleNamespace(HEADER=header, SIGNATURES=signatures, lib=side_lib,
+                                                    header_functions=lambda: declared_functions(header))
+    return SIDE_HEADERS[file_name]
 
 
 def check(code):

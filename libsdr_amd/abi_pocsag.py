@@ -1,24 +1,12 @@
 """ctypes prototypes of include/sdrhip_pocsag.h — the POCSAG decoder bank — applied to the function objects of the library
-abi.lib() loaded. A module of its own beside abi.py and abi_rx.py, as the header is one beside sdrhip.h: abi.SIGNATURES,
-abi_rx.SIGNATURES and the library's `_declared` list stay what they were."""
+abi.lib() loaded (abi.bind_header). A module of its own, as the header is one beside sdrhip.h."""
 import ctypes as C
-import os
-import re
 
 from . import abi
-
-HEADER = os.path.join(abi.ROOT, "include", "sdrhip_pocsag.h")
 
 # event kinds (info[1:0]) and node states (sdrhip_pocsag_channel_state)
 SYNC, WORD, END = 0, 1, 2
 WAIT, RECEIVE, CHECK_CONTINUE = 0, 1, 2
-
-
-def header_functions():
-    """Names of every function include/sdrhip_pocsag.h declares."""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdrhip_[a-z0-9_]+)\s*\(", src)))
 
 
 def _signatures():
@@ -41,17 +29,5 @@ def _signatures():
 
 # name -> (restype, argtypes) of every function include/sdrhip_pocsag.h declares
 SIGNATURES = _signatures()
-
-_applied = None
-
-
-def lib():
-    """abi.lib() with this header's prototypes on its function objects."""
-    global _applied
-    L = abi.lib()
-    if _applied is not L:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _applied = L
-    return L
+_binding = abi.bind_header("sdrhip_pocsag.h", SIGNATURES)
+HEADER, header_functions, lib = _binding.HEADER, _binding.header_functions, _binding.lib

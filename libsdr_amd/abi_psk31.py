@@ -1,22 +1,10 @@
 """ctypes prototypes of include/sdrhip_psk31.h — the BPSK31 bank — applied to the function objects of the library abi.lib()
-loaded. A module of its own beside abi.py, abi_rx.py, abi_pocsag.py and abi_agc.py, as the header is one beside sdrhip.h: their
-SIGNATURES and the library's `_declared` list stay what they were."""
+loaded (abi.bind_header). A module of its own, as the header is one beside sdrhip.h."""
 import ctypes as C
-import os
-import re
 
 from . import abi
 
-HEADER = os.path.join(abi.ROOT, "include", "sdrhip_psk31.h")
-
 PSK31_CS16, PSK31_CF32 = 0, 1
-
-
-def header_functions():
-    """Names of every function include/sdrhip_psk31.h declares."""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdrhip_[a-z0-9_]+)\s*\(", src)))
 
 
 def _signatures():
@@ -40,17 +28,5 @@ def _signatures():
 
 # name -> (restype, argtypes) of every function include/sdrhip_psk31.h declares
 SIGNATURES = _signatures()
-
-_applied = None
-
-
-def lib():
-    """abi.lib() with this header's prototypes on its function objects."""
-    global _applied
-    L = abi.lib()
-    if _applied is not L:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _applied = L
-    return L
+_binding = abi.bind_header("sdrhip_psk31.h", SIGNATURES)
+HEADER, header_functions, lib = _binding.HEADER, _binding.header_functions, _binding.lib

@@ -1,20 +1,8 @@
 """ctypes prototypes of include/sdrhip_rx.h — the receiver bank and the per-channel FMDeemph — applied to the function objects
-of the library abi.lib() loaded. A module of its own beside abi.py, as the header is one beside sdrhip.h: abi.SIGNATURES and
-the library's `_declared` list stay the binding of sdrhip.h alone."""
+of the library abi.lib() loaded (abi.bind_header). A module of its own, as the header is one beside sdrhip.h."""
 import ctypes as C
-import os
-import re
 
 from . import abi
-
-HEADER = os.path.join(abi.ROOT, "include", "sdrhip_rx.h")
-
-
-def header_functions():
-    """Names of every function include/sdrhip_rx.h declares."""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdrhip_[a-z0-9_]+)\s*\(", src)))
 
 
 def _signatures():
@@ -34,17 +22,5 @@ def _signatures():
 
 # name -> (restype, argtypes) of every function include/sdrhip_rx.h declares
 SIGNATURES = _signatures()
-
-_applied = None
-
-
-def lib():
-    """abi.lib() with this header's prototypes on its function objects."""
-    global _applied
-    L = abi.lib()
-    if _applied is not L:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _applied = L
-    return L
+_binding = abi.bind_header("sdrhip_rx.h", SIGNATURES)
+HEADER, header_functions, lib = _binding.HEADER, _binding.header_functions, _binding.lib

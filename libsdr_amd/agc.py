@@ -8,7 +8,7 @@ import numpy as np
 from . import abi_agc
 from .abi import check
 from .abi_agc import AGC_I16, AGC_F32
-from .nodes import _EqualLength, _out, _p, _text
+from .nodes import _EqualLength, _TilePlan, _out, _p, _scalar_dtype
 
 __all__ = ["AGC", "AGCBank", "design_agc_lambda", "design_agc_target", "AGC_I16", "AGC_F32"]
 
@@ -24,15 +24,10 @@ def design_agc_target(dtype):
 
 
 def _dtype(dtype):
-    if isinstance(dtype, int):
-        assert dtype in (AGC_I16, AGC_F32), dtype
-        return dtype
-    dt = np.dtype(dtype)
-    assert dt in (np.dtype(np.int16), np.dtype(np.float32)), dt
-    return AGC_I16 if dt == np.int16 else AGC_F32
+    return _scalar_dtype(dtype, AGC_I16, AGC_F32)
 
 
-class AGCBank(_EqualLength):
+class AGCBank(_TilePlan, _EqualLength):
     """An AGC node PER ROW (sdrhip_agcbank_create): lam[c] (design_agc_lambda), target[c] (0: the type's default) and
     enabled[c]. dtype: np.int16 or np.float32. The setters replace or adjust the node behind one row between two calls."""
     _prefix, _calls = "sdrhip_agc", "process process_dev set_channel set_lambda set_enabled set_gain get_state plan_info kernel_names reset"
@@ -82,16 +77,6 @@ class AGCBank(_EqualLength):
         g, s, e = np.zeros(self.channels, np.float32), np.zeros(self.channels, np.float32), np.zeros(self.channels, np.intc)
         check(self._c_get_state(self._h, _p(g, True), _p(s, True), _p(e, True), self.channels))
         return g, s, e.astype(bool)
-
-    def plan_info(self, n=0):
-        """{tile_samples, channels_per_group} of a call of n samples (0: max_in)."""
-        t, g = C.c_int(0), C.c_int(0)
-        check(self._c_plan_info(self._h, n or self.max_in, C.byref(t), C.byref(g)))
-        return {"tile_samples": t.value, "channels_per_group": g.value}
-
-    @property
-    def kernel_names(self):
-        return _text(self._c_kernel_names, self._h, size=256).split(",")
 
 
 class AGC(AGCBank):

@@ -150,18 +150,10 @@ struct sdrhip_agc {
   Staging stage;
   size_t elem() const { return dtype == SDRHIP_AGC_I16 ? 2 : 4; }
 
-  // host -> device on the context's stream, behind the calls already enqueued; the source is a local of the caller
-  void put(void *dst, const void *src, size_t bytes) {
-    hipStream_t s = ctx->stream;
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    SDRHIP_CHECK_HIP(e);
-    SDRHIP_CHECK_HIP(e2);
-  }
   void fresh_state() {
     std::vector<float2> s((size_t)C);
     for (int c = 0; c < C; c++) s[c] = make_float2(par[c].z, 1.0f);
-    put(st.p, s.data(), s.size() * sizeof(float2));
+    put_sync(ctx, st.p, s.data(), s.size() * sizeof(float2));
   }
   void launch(const void *in_dev, size_t N, size_t in_stride, void *out_dev, size_t out_stride) {
     ctx->use();
@@ -177,10 +169,6 @@ struct sdrhip_agc {
   }
 };
 
-static void require_agc_channel(const sdrhip_agc *h, int channel) {
-  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-  SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
-}
 static void require_lambda(float l, int c) { SDRHIP_REQUIRE(lambda_ok(l), SDRHIP_E_INVALID, "lambda %g of channel %d outside [0,1)", (double)l, c); }
 static void require_target(float t, int c) {
   SDRHIP_REQUIRE(target_ok(t), SDRHIP_E_INVALID, "target %g of channel %d is not a finite number above 0", (double)t, c);
@@ -269,53 +257,44 @@ int sdrhip_agc_process(sdrhip_agc *h, const void *in_host, size_t n, size_t in_s
 
 int sdrhip_agc_set_channel(sdrhip_agc *h, int channel, float lambda, float target) {
   return guarded([&] {
-    require_agc_channel(h, channel);
+    require_channel(h, channel);
     require_lambda(lambda, channel);
     require_target(target, channel);
     h->ctx->use();
     const float4 p = make_float4(lambda, 1.0f - lambda, target, 1.f);
     const float2 s = make_float2(target, 1.0f);
-    h->put(h->par_dev.p + channel, &p, sizeof p);
-    try {
-      h->put(h->st.p + channel, &s, sizeof s);
-    } catch (...) {   // parameters and state change together or not at all: the row's old parameters go back
-      const float4 old = h->par[channel];
-      (void)hipMemcpyAsync(h->par_dev.p + channel, &old, sizeof old, hipMemcpyHostToDevice, h->ctx->stream);
-      (void)hipStreamSynchronize(h->ctx->stream);
-      throw;
-    }
-    h->par[channel] = p;
+    replace_row(h->ctx, h->par_dev.p + channel, h->par[channel], p, h->st.p + channel, &s, sizeof s);
   });
 }
 
 int sdrhip_agc_set_lambda(sdrhip_agc *h, int channel, float lambda) {
   return guarded([&] {
-    require_agc_channel(h, channel);
+    require_channel(h, channel);
     require_lambda(lambda, channel);
     h->ctx->use();
     float4 p = h->par[channel];
     p.x = lambda; p.y = 1.0f - lambda;
-    h->put(h->par_dev.p + channel, &p, sizeof p);
+    put_sync(h->ctx, h->par_dev.p + channel, &p, sizeof p);
     h->par[channel] = p;
   });
 }
 
 int sdrhip_agc_set_enabled(sdrhip_agc *h, int channel, int enabled) {
   return guarded([&] {
-    require_agc_channel(h, channel);
+    require_channel(h, channel);
     h->ctx->use();
     float4 p = h->par[channel];
     p.w = enabled ? 1.f : 0.f;
-    h->put(h->par_dev.p + channel, &p, sizeof p);
+    put_sync(h->ctx, h->par_dev.p + channel, &p, sizeof p);
     h->par[channel] = p;
   });
 }
 
 int sdrhip_agc_set_gain(sdrhip_agc *h, int channel, float gain) {
   return guarded([&] {
-    require_agc_channel(h, channel);
+    require_channel(h, channel);
     h->ctx->use();
-    h->put(&h->st.p[channel].y, &gain, sizeof gain);
+    put_sync(h->ctx, &h->st.p[channel].y, &gain, sizeof gain);
   });
 }
 
@@ -325,10 +304,7 @@ int sdrhip_agc_get_state(sdrhip_agc *h, float *gain, float *sd, int *enabled, in
     SDRHIP_REQUIRE(n >= h->C, SDRHIP_E_SIZE, "n %d < channels %d", n, h->C);
     h->ctx->use();
     std::vector<float2> s((size_t)h->C);
-    const hipError_t e = hipMemcpyAsync(s.data(), h->st.p, s.size() * sizeof(float2), hipMemcpyDeviceToHost, h->ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(h->ctx->stream);
-    SDRHIP_CHECK_HIP(e);
-    SDRHIP_CHECK_HIP(e2);
+    get_sync(h->ctx, s.data(), h->st.p, s.size() * sizeof(float2));
     for (int c = 0; c < h->C; c++) {
       if (sd) sd[c] = s[c].x;
       if (gain) gain[c] = s[c].y;
@@ -339,17 +315,14 @@ int sdrhip_agc_get_state(sdrhip_agc *h, float *gain, float *sd, int *enabled, in
 
 int sdrhip_agc_plan_info(sdrhip_agc *h, size_t n, int *tile_samples, int *channels_per_group) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     (void)n;   // one geometry for every call length
-    if (tile_samples) *tile_samples = AGC_T;
-    if (channels_per_group) *channels_per_group = AGC_G;
+    write_tile_plan(h, tile_samples, channels_per_group, AGC_T, AGC_G);
   });
 }
 
 int sdrhip_agc_kernel_names(sdrhip_agc *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", h->dtype == SDRHIP_AGC_I16 ? "agc_i16_kernel" : "agc_f32_kernel");
+    write_names(h, buf, len, [&] { return h->dtype == SDRHIP_AGC_I16 ? "agc_i16_kernel" : "agc_f32_kernel"; });
   });
 }
 

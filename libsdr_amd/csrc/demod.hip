@@ -822,7 +822,7 @@ static void require_deemph_bank(const sdrhip_deemph *h) {
 int sdrhip_deemphbank_i16_set_enabled(sdrhip_deemph *h, int channel, int enabled) {
   return guarded([&] {
     require_deemph_bank(h);
-    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    require_channel_range(h, channel);
     h->ctx->use();
     SDRHIP_CHECK_HIP(hipMemsetAsync(h->en.p + channel, enabled ? 1 : 0, 1, h->ctx->stream));
     h->en_host[channel] = enabled ? 1 : 0;

@@ -108,4 +108,89 @@ static inline void run_staged(sdrhip_ctx *ctx, Staging &st, size_t in_cap_b, siz
   SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
+// The host-pointer call of a node that writes up to capacity(n) bytes per row and says in counts[c] how many: the head
+// checks the counts pointer with the handle, an empty call still zeroes the caller's counts, the staged output is zeroed
+// first (the bytes of a row behind counts[c] reach the caller as zeros) and the counts come back with the rows. H also has
+// `int C`, `capacity(n)`, `DevBuf<uint32_t> counts` and `Staging stage`; launch(in_dev, out_dev, cap) runs the node on
+// packed rows with h->counts.p. in_elem_b: the bytes of one input element.
+template <class H, class Launch>
+static inline void process_counted(H *h, const void *in_host, size_t n, size_t in_stride, size_t in_elem_b, uint8_t *out_host,
+                                   size_t out_stride, uint32_t *counts_host, Launch &&launch) {
+  SDRHIP_REQUIRE(h && counts_host, SDRHIP_E_INVALID, "NULL argument");
+  if (!call_begin(h, "n", n, in_host, out_host)) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
+  const size_t cap = h->capacity(n), C = (size_t)h->C, eb = in_elem_b, out_cap_b = C * h->capacity(h->max_in);
+  const Strides s = call_strides("n", n, in_stride, cap, out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
+  // (where a set_channel can raise the capacity of max_in, the staged rows grow with it)
+  if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
+  run_staged(h->ctx, h->stage, C * h->max_in * eb, out_cap_b, {in_host, s.in * eb, n * eb, C}, {out_host, s.out, cap, C},
+             [&](void *in, void *out) {
+               h->stage.out.zero(h->ctx->stream);
+               launch(in, static_cast<uint8_t *>(out), cap);
+               SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
+               return cap;
+             });
+}
+
+// ---- per-channel banks: a handle with `int C` rows, and the calls that read or write one of them -------------------------
+// The row index of a set_* / get_* call. A call with a rule of its own between the handle's and the range's (a bank-only
+// setter says SDRHIP_E_UNSUPPORTED there; a pointer argument is checked together with the handle) keeps its head and ends
+// it with the range-only form.
+template <class H>
+static inline void require_channel_range(const H *h, int channel) {
+  SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+}
+template <class H>
+static inline void require_channel(const H *h, int channel) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  require_channel_range(h, channel);
+}
+
+// A setter's or getter's copy: enqueued on the context's stream, behind the calls already there, and synchronous — the host
+// side may be a local of the caller. Both error codes are collected before the first one is raised, so nothing is left in
+// flight when the call returns an error.
+static inline void copy_sync(sdrhip_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+  const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  SDRHIP_CHECK_HIP(e);
+  SDRHIP_CHECK_HIP(e2);
+}
+static inline void put_sync(sdrhip_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes) {
+  copy_sync(ctx, dst_dev, src_host, bytes, hipMemcpyHostToDevice);
+}
+static inline void get_sync(sdrhip_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes) {
+  copy_sync(ctx, dst_host, src_dev, bytes, hipMemcpyDeviceToHost);
+}
+
+// set_channel: a row's parameters are replaced and its state starts afresh — together or not at all. The device's
+// parameters are written, then the device's state; if that fails the old parameters (the host copy still has them) go
+// back to the device, and the host copy changes last.
+template <class P>
+static inline void replace_row(sdrhip_ctx *ctx, P *par_dev, P &par_host, const P &par, void *state_dev, const void *state, size_t state_b) {
+  put_sync(ctx, par_dev, &par, sizeof par);
+  try {
+    put_sync(ctx, state_dev, state, state_b);
+  } catch (...) {
+    (void)hipMemcpyAsync(par_dev, &par_host, sizeof par_host, hipMemcpyHostToDevice, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    throw;
+  }
+  par_host = par;
+}
+
+// ---- what a handle says about its plan -------------------------------------------------------------------------------------
+// *_kernel_names where the answer is a fixed string or a choice among some: text() is asked after the handle is checked.
+template <class H, class Text>
+static inline void write_names(const H *h, char *buf, size_t len, Text &&text) {
+  SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
+  snprintf(buf, len, "%s", text());
+}
+
+// *_plan_info of a bank with one geometry for every call length: either pointer may be NULL.
+template <class H>
+static inline void write_tile_plan(const H *h, int *tile_samples, int *channels_per_group, int tile, int group) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  if (tile_samples) *tile_samples = tile;
+  if (channels_per_group) *channels_per_group = group;
+}
+
 }  // namespace sdrhip

@@ -173,11 +173,6 @@ struct sdrhip_pocsag {
   }
 };
 
-static void require_pocsag_channel(const sdrhip_pocsag *h, int channel) {
-  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-  SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
-}
-
 extern "C" {
 
 size_t sdrhip_pocsag_out_capacity(size_t n_bits) { return n_bits / 32 + n_bits / 256 + 4; }
@@ -263,11 +258,10 @@ int sdrhip_pocsag_process(sdrhip_pocsag *h, const uint8_t *bits_host, size_t bit
 
 int sdrhip_pocsag_set_enabled(sdrhip_pocsag *h, int channel, int enabled) {
   return guarded([&] {
-    require_pocsag_channel(h, channel);
+    require_channel(h, channel);
     h->ctx->use();
     const int v = enabled != 0;
-    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->en_dev.p + channel, &v, sizeof(int), hipMemcpyHostToDevice, h->ctx->stream));
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    put_sync(h->ctx, h->en_dev.p + channel, &v, sizeof(int));
     h->enabled[channel] = v;
   });
 }
@@ -289,7 +283,7 @@ int sdrhip_pocsag_reset(sdrhip_pocsag *h) {
 
 int sdrhip_pocsag_reset_channel(sdrhip_pocsag *h, int channel) {
   return guarded([&] {
-    require_pocsag_channel(h, channel);
+    require_channel(h, channel);
     h->ctx->use();
     SDRHIP_CHECK_HIP(hipMemsetAsync(h->st.p + channel, 0, sizeof(PocState), h->ctx->stream));
   });
@@ -297,11 +291,10 @@ int sdrhip_pocsag_reset_channel(sdrhip_pocsag *h, int channel) {
 
 int sdrhip_pocsag_channel_state(sdrhip_pocsag *h, int channel, int *state, int *bitcount, int *slot, uint64_t *shift64) {
   return guarded([&] {
-    require_pocsag_channel(h, channel);
+    require_channel(h, channel);
     h->ctx->use();
     PocState s;
-    SDRHIP_CHECK_HIP(hipMemcpyAsync(&s, h->st.p + channel, sizeof(PocState), hipMemcpyDeviceToHost, h->ctx->stream));
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(h->ctx->stream));
+    get_sync(h->ctx, &s, h->st.p + channel, sizeof(PocState));
     if (state) *state = (int)s.state;
     if (bitcount) *bitcount = (int)s.bitcount;
     if (slot) *slot = (int)s.slot;
@@ -311,8 +304,7 @@ int sdrhip_pocsag_channel_state(sdrhip_pocsag *h, int channel, int *state, int *
 
 int sdrhip_pocsag_kernel_names(sdrhip_pocsag *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", "pocsag_decode_kernel");
+    write_names(h, buf, len, [] { return "pocsag_decode_kernel"; });
   });
 }
 

@@ -252,14 +252,6 @@ struct sdrhip_psk31 {
   }
   size_t capacity(size_t n) const { return n ? 1 + sub_samples(n) / 33 : 0; }
 
-  // host -> device on the context's stream, behind the calls already enqueued; the source is a local of the caller
-  void put(void *dst, const void *src, size_t bytes) {
-    hipStream_t s = ctx->stream;
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    SDRHIP_CHECK_HIP(e);
-    SDRHIP_CHECK_HIP(e2);
-  }
   void fresh_row(float *s) const {
     memset(s, 0, PSK_STATE * sizeof(float));
     s[ST_MU] = 0.25f; s[ST_OMEGA] = omega0;
@@ -269,7 +261,7 @@ struct sdrhip_psk31 {
   void fresh_state() {
     std::vector<float> s((size_t)C * PSK_STATE);
     for (int c = 0; c < C; c++) fresh_row(&s[(size_t)c * PSK_STATE]);
-    put(st.p, s.data(), s.size() * sizeof(float));
+    put_sync(ctx, st.p, s.data(), s.size() * sizeof(float));
   }
   void launch(const void *in_dev, size_t N, size_t in_stride, uint8_t *out_dev, size_t out_stride, uint32_t *counts_dev) {
     ctx->use();
@@ -287,10 +279,6 @@ struct sdrhip_psk31 {
   }
 };
 
-static void require_psk_channel(const sdrhip_psk31 *h, int channel) {
-  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-  SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
-}
 static void require_df(double dF, int c) { SDRHIP_REQUIRE(df_ok(dF), SDRHIP_E_INVALID, "dF %g of channel %d outside (0,pi]", dF, c); }
 
 // dF: `channels` floats, or (one) one double for all rows
@@ -408,38 +396,20 @@ int sdrhip_psk31_process(sdrhip_psk31 *h, const void *in_host, size_t n, size_t 
                          uint32_t *counts_host) {
   return guarded([&] {
     Range roctx_range("sdrhip_psk31_process");
-    SDRHIP_REQUIRE(h && counts_host, SDRHIP_E_INVALID, "NULL argument");
-    if (!call_begin(h, "n", n, in_host, bits_host)) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
-    const size_t cap = h->capacity(n), C = (size_t)h->C, eb = h->elem();
-    const Strides s = call_strides("n", n, in_stride, cap, out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
-    run_staged(h->ctx, h->stage, C * h->max_in * eb, C * h->capacity(h->max_in), {in_host, s.in * eb, n * eb, C}, {bits_host, s.out, cap, C},
-               [&](void *in, void *out) {
-                 h->stage.out.zero(h->ctx->stream);   // the bytes of a row behind counts[c] reach the caller as zeros
-                 h->launch(in, n, n, static_cast<uint8_t *>(out), cap, h->counts.p);
-                 SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
-                 return cap;
-               });
+    process_counted(h, in_host, n, in_stride, h ? h->elem() : 0, bits_host, out_stride, counts_host,
+                    [&](void *in, uint8_t *out, size_t cap) { h->launch(in, n, n, out, cap, h->counts.p); });
   });
 }
 
 int sdrhip_psk31_set_channel(sdrhip_psk31 *h, int channel, double dF) {
   return guarded([&] {
-    require_psk_channel(h, channel);
+    require_channel(h, channel);
     require_df(dF, channel);
     h->ctx->use();
     const float2 p = make_float2((float)(-dF), (float)dF);
     float s[PSK_STATE];
     h->fresh_row(s);
-    h->put(h->par_dev.p + channel, &p, sizeof p);
-    try {
-      h->put(h->st.p + (size_t)channel * PSK_STATE, s, sizeof s);
-    } catch (...) {   // parameters and state change together or not at all: the row's old range goes back
-      const float2 old = h->par[channel];
-      (void)hipMemcpyAsync(h->par_dev.p + channel, &old, sizeof old, hipMemcpyHostToDevice, h->ctx->stream);
-      (void)hipStreamSynchronize(h->ctx->stream);
-      throw;
-    }
-    h->par[channel] = p;
+    replace_row(h->ctx, h->par_dev.p + channel, h->par[channel], p, h->st.p + (size_t)channel * PSK_STATE, s, sizeof s);
   });
 }
 
@@ -476,17 +446,14 @@ int sdrhip_psk31_get_state(sdrhip_psk31 *h, float *P, float *F, float *mu, float
 
 int sdrhip_psk31_plan_info(sdrhip_psk31 *h, size_t n, int *tile_samples, int *channels_per_group) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     (void)n;   // one geometry for every call length
-    if (tile_samples) *tile_samples = PSK_T;
-    if (channels_per_group) *channels_per_group = PSK_G;
+    write_tile_plan(h, tile_samples, channels_per_group, PSK_T, PSK_G);
   });
 }
 
 int sdrhip_psk31_kernel_names(sdrhip_psk31 *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", h->dtype == SDRHIP_PSK31_CS16 ? "psk31_cs16_kernel" : "psk31_cf32_kernel");
+    write_names(h, buf, len, [&] { return h->dtype == SDRHIP_PSK31_CS16 ? "psk31_cs16_kernel" : "psk31_cf32_kernel"; });
   });
 }
 

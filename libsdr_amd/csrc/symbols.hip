@@ -650,7 +650,7 @@ int sdrhip_detectorbank_set_channel(sdrhip_detector *h, int channel, int kind, c
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(h->per_channel, SDRHIP_E_UNSUPPORTED,
                    "the handle has one detector for all channels (sdrhip_detectorbank_create makes one per channel)");
-    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    require_channel_range(h, channel);
     require_detector_channel(channel, kind, mark_lut, space_lut, corr_len, h->maxL);
     h->set_channel(channel, kind, mark_lut, space_lut, corr_len, invert);
   });
@@ -684,8 +684,9 @@ int sdrhip_detector_process(sdrhip_detector *h, const int16_t *in_host, size_t n
 
 int sdrhip_detector_kernel_names(sdrhip_detector *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", h->per_channel ? "detectorbank_kernel" : h->kind == SDRHIP_DET_ASK ? "ask_detect_kernel" : "fsk_detect_kernel");
+    write_names(h, buf, len, [&] {
+      return h->per_channel ? "detectorbank_kernel" : h->kind == SDRHIP_DET_ASK ? "ask_detect_kernel" : "fsk_detect_kernel";
+    });
   });
 }
 
@@ -768,7 +769,7 @@ static void require_per_channel_bits(const sdrhip_bits *h, int channel) {
   SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
   SDRHIP_REQUIRE(h->per_channel, SDRHIP_E_UNSUPPORTED,
                  "the handle has one bit clock for all channels (sdrhip_bitsbank_create makes one per channel)");
-  SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+  require_channel_range(h, channel);
 }
 
 int sdrhip_bitsbank_set_channel(sdrhip_bits *h, int channel, float baud, int mode) {
@@ -822,26 +823,16 @@ int sdrhip_bits_process(sdrhip_bits *h, const uint8_t *sym_host, size_t n, size_
                         uint32_t *counts_host) {
   return guarded([&] {
     Range roctx_range("sdrhip_bits_process");
-    SDRHIP_REQUIRE(h && counts_host, SDRHIP_E_INVALID, "NULL argument");
-    if (!call_begin(h, "n", n, sym_host, bits_host)) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
-    const size_t cap = h->capacity(n), C = (size_t)h->C;
-    const Strides s = call_strides("n", n, in_stride, cap, out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
-    // (a set_channel to a faster baud rate raises the capacity the staged rows need)
-    if (h->stage.out.p && h->stage.out.n < C * h->capacity(h->max_in)) h->stage.out.alloc(C * h->capacity(h->max_in));
-    run_staged(h->ctx, h->stage, C * h->max_in, C * h->capacity(h->max_in), {sym_host, s.in, n, C}, {bits_host, s.out, cap, C},
-               [&](void *in, void *out) {
-                 h->stage.out.zero(h->ctx->stream);   // the bytes of a row behind counts[c] reach the caller as zeros
-                 h->launch(static_cast<const uint8_t *>(in), n, n, static_cast<uint8_t *>(out), cap, h->counts.p);
-                 SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
-                 return cap;
-               });
+    // (a set_channel to a faster baud rate raises capacity(max_in): the one case in which the staged rows grow)
+    process_counted(h, sym_host, n, in_stride, 1, bits_host, out_stride, counts_host, [&](void *in, uint8_t *out, size_t cap) {
+      h->launch(static_cast<const uint8_t *>(in), n, n, out, cap, h->counts.p);
+    });
   });
 }
 
 int sdrhip_bits_kernel_names(sdrhip_bits *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", h->per_channel ? "bitsbank_pll_kernel,bitsbank_flags_kernel" : "bits_pll_kernel,bits_flags_kernel");
+    write_names(h, buf, len, [&] { return h->per_channel ? "bitsbank_pll_kernel,bitsbank_flags_kernel" : "bits_pll_kernel,bits_flags_kernel"; });
   });
 }
 

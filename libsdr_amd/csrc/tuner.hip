@@ -671,7 +671,7 @@ int sdrhip_tunermodes_i16_set_mode(sdrhip_tuner_i16 *h, int channel, int mode) {
   return guarded([&] {
     SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
     SDRHIP_REQUIRE(h->per_channel, SDRHIP_E_UNSUPPORTED, "the bank has one demodulator for all channels (sdrhip_tunermodes_i16_create makes one per channel)");
-    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    require_channel_range(h, channel);
     SDRHIP_REQUIRE(valid_mode(mode), SDRHIP_E_INVALID, "mode %d is none of SDRHIP_EPI_FM, _AM, _USB", mode);
     h->ctx->use();
     hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued
@@ -693,8 +693,7 @@ int sdrhip_tunermodes_i16_get_modes(sdrhip_tuner_i16 *h, int *modes, int n) {
 
 int sdrhip_tuner_i16_kernel_names(sdrhip_tuner_i16 *h, char *buf, size_t len) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h && buf && len, SDRHIP_E_INVALID, "NULL argument");
-    snprintf(buf, len, "%s", h->last_names.c_str());
+    write_names(h, buf, len, [&] { return h->last_names.c_str(); });
   });
 }
 
@@ -747,7 +746,7 @@ int sdrhip_tuner_i16_process(sdrhip_tuner_i16 *h, const void *in_host, size_t n_
 int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *taps) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
-    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    require_channel_range(h, channel);
     for (int i = 0; i < 2 * h->order; i++)
       SDRHIP_REQUIRE(tap_in_range(taps[i], h->real != 0), SDRHIP_E_UNSUPPORTED,
                      h->real ? "tap %d = %d exceeds 24 bits" : "tap %d = %d does not fit the packed int16 path", i / 2, taps[i]);
@@ -765,8 +764,7 @@ int sdrhip_tuner_i16_set_taps(sdrhip_tuner_i16 *h, int channel, const int32_t *t
 
 int sdrhip_tuner_i16_set_shift(sdrhip_tuner_i16 *h, int channel, uint32_t lut_inc, int negative) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    SDRHIP_REQUIRE(channel >= 0 && channel < h->C, SDRHIP_E_INVALID, "channel %d outside [0,%d)", channel, h->C);
+    require_channel(h, channel);
     h->ctx->use();
     hipStream_t st = h->ctx->stream;
     h->inc_host[channel] = lut_inc; h->neg_host[channel] = negative ? 1 : 0;

@@ -7,8 +7,9 @@ device pointers (e.g. torch tensors' data_ptr()). No CPU fallback exists: constr
 without a HIP device raises SdrHipError(E_NODEVICE).
 
 The helper layer, each thing written once: _p (array -> pointer), _out (scalar out-parameter getters), _text (string
-getters), _rows (input layout), _roundtrip (host arrays through fresh device buffers), _Handle (close / __del__ of a handle
-owner), _Node (entry points bound at construction) and the two process families _Counted and _EqualLength.
+getters), _rows (input layout), _scalar_dtype (a bank's int16-or-float code), _roundtrip (host arrays through fresh device
+buffers), _Handle (close / __del__ of a handle owner), _Node (entry points bound at construction), the two process families
+_Counted and _EqualLength, and _TilePlan (plan_info / kernel_names of the tiled per-row banks).
 To add a node: derive from the family its calls belong to, name its `_prefix` and `_calls`, declare its input layout
 (`_in`, `_assert_channels`) and its output (`_out_dtype`, or the array it hands to `_run`), then write the constructor around
 the create call and whatever else is particular to it. A mistyped entry point fails construction, on any machine
@@ -67,6 +68,16 @@ def _rows(x, dtype, comps, channels=None):
     assert x.ndim == nd and (not comps or x.shape[2] == comps), x.shape
     assert channels is None or x.shape[0] == channels, x.shape
     return x
+
+
+def _scalar_dtype(dtype, i16_code, f32_code):
+    """The ABI's code of a bank's scalar type: np.int16 or np.float32 (or a dtype alike), or one of the two codes itself."""
+    if isinstance(dtype, int):
+        assert dtype in (i16_code, f32_code), dtype
+        return dtype
+    dt = np.dtype(dtype)
+    assert dt in (np.dtype(np.int16), np.dtype(np.float32)), dt
+    return i16_code if dt == np.int16 else f32_code
 
 
 def _roundtrip(ctx, x, out, call, staged_out=False):
@@ -331,6 +342,21 @@ class _EqualLength(_Node):
 
     def reset(self):
         check(self._c_reset(self._h))
+
+
+class _TilePlan:
+    """Beside a family: the banks that walk `channels_per_group` rows in tiles of `tile_samples` — `_calls` names plan_info and
+    kernel_names."""
+
+    def plan_info(self, n=0):
+        """{tile_samples, channels_per_group} of a call of n samples (0: max_in)."""
+        t, g = C.c_int(0), C.c_int(0)
+        check(self._c_plan_info(self._h, n or self.max_in, C.byref(t), C.byref(g)))
+        return {"tile_samples": t.value, "channels_per_group": g.value}
+
+    @property
+    def kernel_names(self):
+        return _text(self._c_kernel_names, self._h, size=256).split(",")
 
 
 class IQBaseBandI16(_Counted):

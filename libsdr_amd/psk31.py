@@ -10,7 +10,7 @@ from . import abi_psk31
 from .abi import check
 from .abi_psk31 import PSK31_CS16, PSK31_CF32
 from . import nodes
-from .nodes import _Node, _designed, _out, _p, _text
+from .nodes import _Node, _TilePlan, _designed, _out, _p, _scalar_dtype
 
 __all__ = ["BPSK31", "BPSK31Bank", "Varicode", "design_inpol_taps", "PSK31_CS16", "PSK31_CF32"]
 
@@ -20,16 +20,7 @@ def design_inpol_taps():
     return _designed(abi_psk31.lib().sdrhip_design_inpol_taps, (129, 8), np.float32)
 
 
-def _dtype(dtype):
-    if isinstance(dtype, int):
-        assert dtype in (PSK31_CS16, PSK31_CF32), dtype
-        return dtype
-    dt = np.dtype(dtype)
-    assert dt in (np.dtype(np.int16), np.dtype(np.float32)), dt
-    return PSK31_CS16 if dt == np.int16 else PSK31_CF32
-
-
-class BPSK31Bank(_Node):
+class BPSK31Bank(_TilePlan, _Node):
     """A BPSK31 node PER ROW at one sample rate Fs (sdrhip_psk31bank_create): dF[c] is row c's carrier-loop range in radians per
     sample. dtype: np.int16 (complex<int16> rows) or np.float32. table: the [129, 8] interpolation table (default:
     design_inpol_taps(); the reference's own, quirks included, for bit parity with it). process(x[channels, n, 2]) returns the
@@ -46,7 +37,7 @@ class BPSK31Bank(_Node):
     def _setup(self, ctx, dtype, Fs, channels, table, max_in):
         abi_psk31.lib()
         _Node.__init__(self)
-        self.dtype = _dtype(dtype)
+        self.dtype = _scalar_dtype(dtype, PSK31_CS16, PSK31_CF32)
         self._in = (np.int16 if self.dtype == PSK31_CS16 else np.float32, 2)
         self.table = np.ascontiguousarray(design_inpol_taps() if table is None else table, np.float32).reshape(129, 8)
         self.ctx, self.Fs, self.channels, self.max_in, self._counts_dev = ctx, float(Fs), int(channels), int(max_in), 0
@@ -91,16 +82,6 @@ class BPSK31Bank(_Node):
         i = [np.zeros(self.channels, np.intc) for _ in range(2)]
         check(self._c_get_state(self._h, *[_p(a, True) for a in f + i], self.channels))
         return dict(zip(("P", "F", "mu", "omega", "hist_idx", "last"), f + i))
-
-    def plan_info(self, n=0):
-        """{tile_samples, channels_per_group} of a call of n samples (0: max_in)."""
-        t, g = C.c_int(0), C.c_int(0)
-        check(self._c_plan_info(self._h, n or self.max_in, C.byref(t), C.byref(g)))
-        return {"tile_samples": t.value, "channels_per_group": g.value}
-
-    @property
-    def kernel_names(self):
-        return _text(self._c_kernel_names, self._h, size=256).split(",")
 
     def _release(self):
         if self._counts_dev:

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_checks import LLVM, code_objects, kernels
 from libsdr_amd import abi, nodes
 
 
@@ -23,7 +24,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_library_is_hip_code_for_gfx950():
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", abi.SO_PATH], capture_output=True, text=True)
+    out = subprocess.run([LLVM + "llvm-readelf", "--notes", abi.SO_PATH], capture_output=True, text=True)
     blob = open(abi.SO_PATH, "rb").read()
     assert b"gfx950" in blob, out.stdout[:200]
     for k in (b"iqbb_i16_kernel", b"fir_cs16_exact_kernel", b"fftconv_kernel"):
@@ -34,22 +35,11 @@ def test_hot_kernels_keep_out_of_scratch(tmp_path):
     """No K1 hot kernel may spill vector registers: scratch is HBM traffic behind the kernel's back (a change that left 68
     bytes of it in the /8 USB kernels cost 11 % time and 28 % traffic before it was seen in a profile). Read from the
     code objects' own metadata; the one allowance is a cold-phase spill of three dwords in one any-D kernel."""
-    import re
-    import shutil
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    objs = sorted(tmp_path.glob("lib.so.*gfx950"))
+    objs = code_objects(tmp_path)
     assert len(objs) >= 15, objs
-    seen, bad = 0, []
-    for o in objs:
-        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, scratch in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            if "iqbb_hot" not in name:
-                continue
-            seen += 1
-            if int(scratch):
-                bad.append((name, int(scratch)))
-    assert seen >= 400, seen
+    hot = [(name, scratch) for _, name, scratch in kernels(objs) if "iqbb_hot" in name]
+    assert len(hot) >= 400, len(hot)
+    bad = [(name, scratch) for name, scratch in hot if scratch]
     assert len(bad) <= 1 and all("anyd" in n and b <= 12 for n, b in bad), bad
 
 

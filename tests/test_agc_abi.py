@@ -1,60 +1,31 @@
 """The AGC bank's C calls (include/sdrhip_agc.h), what can be checked without a GPU: every function of the header is exported by
-libsdrhip.so and has a prototype in libsdr_amd/abi_agc.py, and nothing else of the family is exported; the other headers' bindings
-are what they were; the designers give the reference's numbers; every argument rule of the two create calls answers BEFORE the
+libsdrhip.so and has a prototype in libsdr_amd/abi_agc.py, and nothing else of the family is exported (tests/test_side_headers.py holds what the
+headers' bindings owe each other); the designers give the reference's numbers; every argument rule of the two create calls answers BEFORE the
 context is looked at, in the header's order; the calls on a handle refuse a NULL one; both kernels exist for gfx950 and use no
 scratch."""
 import ctypes as C
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import agc_restatement as R
+from abi_checks import assert_header_binding, kernel_scratch, last_error, no_ctx_code
 from libsdr_amd import abi, nodes
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 NEW = ["sdrhip_agc_create", "sdrhip_agc_destroy", "sdrhip_agc_get_state", "sdrhip_agc_kernel_names", "sdrhip_agc_plan_info", "sdrhip_agc_process",
        "sdrhip_agc_process_dev", "sdrhip_agc_reset", "sdrhip_agc_set_channel", "sdrhip_agc_set_enabled", "sdrhip_agc_set_gain",
        "sdrhip_agc_set_lambda", "sdrhip_agcbank_create", "sdrhip_design_agc_lambda", "sdrhip_design_agc_target"]
 ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-NO_CTX = lambda: abi.E_NODEVICE if nodes.device_count() == 0 else abi.E_INVALID
-
-
-def _text():
-    return abi.lib().sdrhip_last_error().decode()
 
 
 def test_header_binding_and_exports_agree():
     from libsdr_amd import abi_agc
-    declared = abi_agc.header_functions()
-    assert declared == sorted(NEW)
-    assert sorted(abi_agc.SIGNATURES) == declared
-    fresh = C.CDLL(abi.SO_PATH)   # (looked up by name in the library's own export table, not through the binding)
-    for f in declared:
-        assert C.cast(getattr(fresh, f), C.c_void_p).value, f
-    L = abi_agc.lib()
-    assert L is abi.lib()
-    for f, (res, args) in abi_agc.SIGNATURES.items():
-        fn = getattr(L, f)
-        assert fn.restype is res and list(fn.argtypes) == args, f
-    syms = subprocess.run([LLVM + "llvm-readelf", "--dyn-syms", "-W", abi.SO_PATH], capture_output=True, text=True, check=True).stdout
-    got = sorted(set(re.findall(r"\b(sdrhip_(?:design_)?agc[a-z0-9_]*)\b", syms)))
-    assert got == declared
+    assert_header_binding(abi_agc, NEW, r"\b(sdrhip_(?:design_)?agc[a-z0-9_]*)\b")
 
 
-def test_the_other_headers_bindings_are_unchanged_by_this_module():
-    from libsdr_amd import abi_pocsag, abi_rx
-    before = dict(abi.SIGNATURES), dict(abi_rx.SIGNATURES), dict(abi_pocsag.SIGNATURES), list(abi.lib()._declared)
-    wrappers = sorted(k for k, v in vars(nodes).items() if isinstance(v, type))
-    from libsdr_amd import abi_agc, agc
-    abi_agc.lib()
-    assert (dict(abi.SIGNATURES), dict(abi_rx.SIGNATURES), dict(abi_pocsag.SIGNATURES), list(abi.lib()._declared)) == before
-    for other in (abi.header_functions(), abi_rx.header_functions(), abi_pocsag.header_functions()):
-        assert not set(NEW) & set(other)
-    assert sorted(k for k, v in vars(nodes).items() if isinstance(v, type)) == wrappers
+def test_the_package_exports_this_modules_classes():
     import libsdr_amd
+    from libsdr_amd import agc
     assert libsdr_amd.AGC is agc.AGC and libsdr_amd.AGCBank is agc.AGCBank
     assert issubclass(agc.AGCBank, nodes._EqualLength) and issubclass(agc.AGC, agc.AGCBank)
 
@@ -67,7 +38,7 @@ def test_designers(tau, Fs):
     assert np.float32(v.value).view(np.uint32) == R.design_lambda(tau, Fs).view(np.uint32)
     assert L.sdrhip_design_agc_target(0, C.byref(v)) == abi.OK and v.value == 16000.0
     assert L.sdrhip_design_agc_target(1, C.byref(v)) == abi.OK and v.value == 0.5
-    assert L.sdrhip_design_agc_target(2, C.byref(v)) == abi.E_INVALID and "dtype" in _text()
+    assert L.sdrhip_design_agc_target(2, C.byref(v)) == abi.E_INVALID and "dtype" in last_error()
     assert L.sdrhip_design_agc_lambda(tau, Fs, None) == abi.E_INVALID and L.sdrhip_design_agc_target(0, None) == abi.E_INVALID
     assert L.sdrhip_design_agc_lambda(0.0, Fs, C.byref(v)) == abi.E_INVALID and L.sdrhip_design_agc_lambda(tau, -1.0, C.byref(v)) == abi.E_INVALID
 
@@ -99,9 +70,9 @@ def _one(dtype=0, lam=0.5, target=16000.0, channels=3, max_in=1024, null=()):
 def test_create_without_a_context():
     for code, h in (_bank(), _one(), _bank(dtype=1), _one(dtype=1), _one(lam=0.0), _one(channels=1), _one(channels=65535), _one(max_in=1),
                     _one(max_in=(1 << 30) - 1), _one(lam=float(np.nextafter(np.float32(1), np.float32(0))))):
-        assert code == NO_CTX() and h is None
+        assert code == no_ctx_code() and h is None
     if nodes.device_count() == 0:
-        assert "no CPU fallback" in _text()
+        assert "no CPU fallback" in last_error()
 
 
 INF, NAN = float("inf"), float("nan")
@@ -130,14 +101,14 @@ ONE_RULES = [
 def test_bank_create_argument_rules_come_before_the_context(kw, want, text):
     code, h = _bank(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 @pytest.mark.parametrize("kw,want,text", ONE_RULES, ids=[str(i) for i in range(len(ONE_RULES))])
 def test_create_argument_rules_come_before_the_context(kw, want, text):
     code, h = _one(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 def test_calls_on_a_null_handle():
@@ -145,25 +116,17 @@ def test_calls_on_a_null_handle():
     L = abi_agc.lib()
     g, e, t = (C.c_float * 4)(), (C.c_int * 4)(), C.c_int(7)
     buf = C.create_string_buffer(64)
-    assert L.sdrhip_agc_process_dev(None, None, 0, 0, None, 0) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_agc_process(None, None, 0, 0, None, 0) == abi.E_INVALID and "NULL" in _text()
+    assert L.sdrhip_agc_process_dev(None, None, 0, 0, None, 0) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_agc_process(None, None, 0, 0, None, 0) == abi.E_INVALID and "NULL" in last_error()
     for call in (lambda: L.sdrhip_agc_set_channel(None, 0, 0.5, 1.0), lambda: L.sdrhip_agc_set_lambda(None, 0, 0.5),
                  lambda: L.sdrhip_agc_set_enabled(None, 0, 1), lambda: L.sdrhip_agc_set_gain(None, 0, 1.0),
                  lambda: L.sdrhip_agc_get_state(None, g, g, e, 4), lambda: L.sdrhip_agc_reset(None),
                  lambda: L.sdrhip_agc_kernel_names(None, buf, 64)):
-        assert call() == abi.E_INVALID and "NULL" in _text()
+        assert call() == abi.E_INVALID and "NULL" in last_error()
     assert L.sdrhip_agc_plan_info(None, 16, C.byref(t), None) == abi.E_INVALID and t.value == 7
     assert L.sdrhip_agc_destroy(None) == abi.OK
 
 
 def test_both_kernels_exist_for_gfx950_without_scratch(tmp_path):
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    seen = {}
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, b in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            m = re.search(r"\d(agc_[a-z0-9_]+_kernel)", name)
-            if m:
-                seen[m.group(1)] = int(b)
+    seen = kernel_scratch(tmp_path, r"\d(agc_[a-z0-9_]+_kernel)")
     assert seen == {"agc_i16_kernel": 0, "agc_f32_kernel": 0}, seen

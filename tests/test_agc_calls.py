@@ -5,7 +5,7 @@ entry point, a wrong argument count or type, a changed call order or a changed r
 libsdrhip.so and without a device."""
 import numpy as np
 
-from libsdr_amd import abi, abi_agc, agc, nodes
+from libsdr_amd import abi, abi_agc, agc
 from test_nodes_calls import A, B, FakeLib, NAMES, OUT_VP, Run, XR16, ramp
 
 OUT_F = ("out", "c_float")
@@ -13,41 +13,21 @@ XF = ramp((2, 16), np.float32, 31)
 LAM = np.array([0.5, 0.25], np.float32)
 Z16, ZF = ("<i2", (2, 16), "zeros"), ("<f4", (2, 16), "zeros")
 E16 = ("<i2", (2, 0), "zeros")
-SIGS = dict(abi.SIGNATURES, **abi_agc.SIGNATURES)
 
 
-class AgcFake(FakeLib):
+def _plan_info(args):
+    args[2]._obj.value, args[3]._obj.value = 256, 16
+
+
+def _get_state(args):
+    for a, v in zip(args[1:4], (2.0, 3.0, 1)):
+        a._arr[...] = v
+
+
+def _run(monkeypatch):
     """The fake of test_nodes_calls.py, answering include/sdrhip_agc.h's names as well."""
-
-    def __getattr__(self, name):
-        if name not in SIGS:
-            raise AttributeError(name)
-        self.reached.add(name)
-        return lambda *args: self._call(name, args)
-
-    def _call(self, name, args):
-        argtypes = SIGS[name][1]
-        assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-        for a, t in zip(args, argtypes):
-            t.from_param(a)
-        config = name.endswith("_create") or "_set_" in name or "_design_" in name
-        self.calls.append((name,) + tuple(self._norm(a, config) for a in args))
-        if name == "sdrhip_agc_plan_info":
-            args[2]._obj.value, args[3]._obj.value = 256, 16
-        elif name == "sdrhip_agc_get_state":
-            for a, v in zip(args[1:4], (2.0, 3.0, 1)):
-                a._arr[...] = v
-        else:
-            self._fill(name, args)
-        return abi.OK
-
-
-class AgcRun(Run):
-    def __init__(self, monkeypatch):
-        super().__init__(monkeypatch)
-        self.fake = AgcFake()
-        monkeypatch.setattr(abi, "_lib", self.fake)
-        monkeypatch.setattr(nodes, "close_hooks", [lambda ctx: self.fake.calls.append(("hook", self.h(ctx)))])
+    return Run(monkeypatch, FakeLib(signatures=dict(abi.SIGNATURES, **abi_agc.SIGNATURES),
+                                    answers={"sdrhip_agc_plan_info": _plan_info, "sdrhip_agc_get_state": _get_state}))
 
 
 def case_agc(r):
@@ -123,7 +103,7 @@ EXPECT = [
 
 
 def test_agc_call_trace(monkeypatch):
-    r = AgcRun(monkeypatch)
+    r = _run(monkeypatch)
     case_agc(r)
     got = r.fake.calls
     for k, (g, w) in enumerate(zip(got, EXPECT)):
@@ -132,13 +112,13 @@ def test_agc_call_trace(monkeypatch):
 
 
 def test_every_wrapper_call_of_the_header_was_reached(monkeypatch):
-    r = AgcRun(monkeypatch)
+    r = _run(monkeypatch)
     case_agc(r)
     assert set(abi_agc.SIGNATURES) <= r.fake.reached, sorted(set(abi_agc.SIGNATURES) - r.fake.reached)
 
 
 def test_a_mistyped_entry_point_fails_construction(monkeypatch):
-    r = AgcRun(monkeypatch)
+    r = _run(monkeypatch)
     ctx = r.ctx()
     monkeypatch.setattr(agc.AGCBank, "_calls", agc.AGCBank._calls + " set_gian")
     try:

@@ -5,19 +5,12 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
+from cpp_build import ROOT, SAN, build
 
 
 def _build(src, out, extra=(), srcdir=("tests", "cpp")):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = CXX + [os.path.join(ROOT, *srcdir, src), "-o", exe] + list(extra) + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
+    """(these programs name their own libraries: the oracle's beside libsdrhip.so, _gpu_link_flags)"""
+    return build(src, extra, link=False, out=out, srcdir=srcdir)
 
 
 def _gpu_link_flags():
@@ -39,9 +32,6 @@ def test_wav_nodes_cpu(tmp_path):
     exe = _build("test_wav.cc", "test_wav")
     r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden"), str(tmp_path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout + r.stderr
-
-
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
 def _run_sanitized(exe, args, timeout=300):

@@ -3,18 +3,13 @@ way tests/test_cpp_pocsag.py builds its program. tests/cpp/test_agc.cc runs ever
 Source -> gpu::AGC -> Sink buffer by buffer, the recorded enable() / setGain() calls included, against the reference's output,
 gain and level bits, and the streams' heads as device rows through AGCBank::processDev. setTau, which no fixture holds, runs
 between two buffers against the restatement with its decay changed (the reference's setTau touches nothing else)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import agc_restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
+from cpp_build import build
 
 
 def write_cases(path):
@@ -54,11 +49,7 @@ def write_tau_cases(path, tmp):
 
 @pytest.mark.gpu
 def test_agc_nodes_and_bank_follow_the_fixtures(tmp_path):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "test_agc")
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_agc.cc"), "-o", exe] + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    exe = build("test_agc.cc")
     n = write_cases(tmp_path / "cases.txt")
     write_tau_cases(tmp_path / "tau.txt", tmp_path)
     r = subprocess.run([exe, str(tmp_path / "cases.txt"), R.GOLDEN, str(tmp_path / "tau.txt")], capture_output=True, text=True, timeout=300)

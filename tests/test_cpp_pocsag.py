@@ -8,20 +8,12 @@ import subprocess
 import pytest
 
 import pocsag_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
+from cpp_build import build
 
 
 @pytest.mark.gpu
 def test_pocsag_bank_delivers_the_golden_messages(tmp_path):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "test_pocsag_bank")
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_pocsag_bank.cc"), "-o", exe] + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    exe = build("test_pocsag_bank.cc")
     n_cases, _ = pocsag_cases.write_cases(tmp_path / "cases.txt")
     g = pocsag_cases.GOLDEN
     r = subprocess.run([exe, str(tmp_path / "cases.txt"), os.path.join(g, "g19_pocsag_inputs.txt"), os.path.join(g, "g19_pocsag_bits.bin")],

@@ -6,18 +6,14 @@ import os
 import subprocess
 
 import pocsag_cases
+from cpp_build import ROOT, SAN, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
+# (its own base flags: -Wextra, no -O2, and no libsdrhip.so — the program has no HIP in it)
 CXX = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
 def test_message_assembly_under_sanitizers(tmp_path):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "test_pocsag_assemble_san")
-    r = subprocess.run(CXX + SAN + [os.path.join(ROOT, "tests", "cpp", "test_pocsag_assemble.cc"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    exe = build("test_pocsag_assemble.cc", SAN, link=False, out="test_pocsag_assemble_san", cxx=CXX)
     n_cases, n_msgs = pocsag_cases.write_cases(tmp_path / "cases.txt")
     assert n_cases >= 18 and n_msgs > 20
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")

@@ -8,24 +8,11 @@ import subprocess
 import pytest
 
 import psk31_restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
-
-
-def build():
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "test_psk31")
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_psk31.cc"), "-o", exe] + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
+from cpp_build import build
 
 
 def test_varicode_on_the_host():
-    exe = build()
+    exe = build("test_psk31.cc")
     m = R.manifest()["g21_varicode"]
     r = subprocess.run([exe, "varicode", os.path.join(R.GOLDEN, m["bits"]), str(m["count"]), os.path.join(R.GOLDEN, m["text"]), str(m["chars"])],
                        capture_output=True, text=True, timeout=120)
@@ -35,7 +22,7 @@ def test_varicode_on_the_host():
 
 @pytest.mark.gpu
 def test_psk31_nodes_and_bank_follow_the_fixtures(tmp_path):
-    exe = build()
+    exe = build("test_psk31.cc")
     man = R.manifest()
     names = R.fixture_names()
     with open(tmp_path / "cases.txt", "w") as f:

@@ -10,26 +10,11 @@ import numpy as np
 import pytest
 
 import receiver_plan as rp
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-
-
-def _build(out, extra=()):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_receiver_bank.cc"), "-o", exe] + list(extra) + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
+from cpp_build import SAN, build
 
 
 def test_receiver_bank_host_half_under_sanitizers():
-    exe = _build("test_receiver_bank_san", SAN)
+    exe = build("test_receiver_bank.cc", SAN, out="test_receiver_bank_san")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, "--host-only"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
@@ -53,6 +38,6 @@ def test_receiver_bank_in_a_graph(tmp_path, orc):
         np.array([b.size for b in bits], np.uint32).tofile(tmp_path / ("bits%d.lens" % c))
         np.concatenate(audio).astype(np.int16).tofile(tmp_path / ("audio%d.i16" % c))
         np.array([a.size for a in audio], np.uint32).tofile(tmp_path / ("audio%d.lens" % c))
-    exe = _build("test_receiver_bank")
+    exe = build("test_receiver_bank.cc")
     r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout + r.stderr

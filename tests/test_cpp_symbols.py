@@ -5,29 +5,15 @@ import os
 import subprocess
 
 import pytest
+from cpp_build import ROOT, SAN, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-
-
-def _build(out, extra=()):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_symbols.cc"), "-o", exe] + list(extra) + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
 
 
 def test_symbol_nodes_host_half_under_sanitizers():
     """Designer LUTs bit for bit, silent return on an incomplete Config, ConfigError on a wrong type, and with a complete
     Config either a plan or a ConfigError (no device, no CPU fallback) — never a crash; clean destructors."""
-    exe = _build("test_symbols_san", SAN)
+    exe = build("test_symbols.cc", SAN, out="test_symbols_san")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, "--host-only", GOLDEN], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
@@ -38,6 +24,6 @@ def test_symbol_nodes_host_half_under_sanitizers():
 def test_symbol_nodes_in_graphs():
     """sdr_ax25's graph reproduces the g18 AX.25 bits in both modes, with the symbols handed over on the device and through
     the host buffer; BitStream sends nothing for a bit-less buffer; ASK both ways; a Config change restarts both nodes."""
-    exe = _build("test_symbols")
+    exe = build("test_symbols.cc")
     r = subprocess.run([exe, GOLDEN], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout + r.stderr

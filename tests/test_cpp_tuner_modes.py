@@ -6,28 +6,13 @@ import os
 import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-
-
-def _build(out, extra=()):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_tuner_modes.cc"), "-o", exe] + list(extra) + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
+from cpp_build import SAN, build
 
 
 def test_tuner_modes_host_half_under_sanitizers():
     """Modes recorded before config() and read back with mode(c); ConfigError for a mode the bank has no demodulator for, in
     both kinds of bank, with nothing changed; with a complete Config a plan or a ConfigError — never a crash."""
-    exe = _build("test_tuner_modes_san", SAN)
+    exe = build("test_tuner_modes.cc", SAN, out="test_tuner_modes_san")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, "--host-only"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
@@ -38,6 +23,6 @@ def test_tuner_modes_host_half_under_sanitizers():
 def test_tuner_modes_in_graphs():
     """FM, AM and USB channels of one bank equal the rows of three single-demodulator banks on the same source over 4
     buffers; setMode(1, FM) after buffer 2 changes source 1 alone, which goes on from a fresh FMDemod."""
-    exe = _build("test_tuner_modes")
+    exe = build("test_tuner_modes.cc")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout + r.stderr

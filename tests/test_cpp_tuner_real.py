@@ -8,12 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
+from cpp_build import SAN, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "_build")
-CXX = ["g++", "-O2", "-std=c++17", "-Wall", "-Werror=return-type", "-I" + os.path.join(ROOT, "include")]
-LINK = ["-L" + os.path.join(ROOT, "libsdr_amd"), "-lsdrhip", "-Wl,-rpath," + os.path.join(ROOT, "libsdr_amd")]
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 # as tests/cpp/test_tuner_real.cc states them
 FS, BS, ORDER, D = 2.0e6, 4096, 127, 20
@@ -21,21 +17,11 @@ TUNES = [(101.5e3, 101.5e3, 12.5e3, "fm"), (455000.25, 455000.25, 9e3, "am"), (1
 CUTS = [BS, BS, BS, 1000]
 
 
-def _build(out, extra=()):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = CXX + [os.path.join(ROOT, "tests", "cpp", "test_tuner_real.cc"), "-o", exe] + list(extra) + LINK + ["-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "warning" not in r.stderr, r.stderr[-3000:]
-    return exe
-
-
 def test_real_tuner_bank_host_half_under_sanitizers():
     """A Sink<int16_t>; tunes kept as doubles; silent return on an incomplete Config, ConfigError on a complex or byte input
     type and on a mode the bank has no demodulator for; with a complete Config either a plan or a ConfigError (no device, no CPU
     fallback) — never a crash; clean destructors."""
-    exe = _build("test_tuner_real_san", SAN)
+    exe = build("test_tuner_real.cc", SAN, out="test_tuner_real_san")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, "--host-only"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
@@ -61,6 +47,6 @@ def test_real_tuner_bank_in_a_graph(tmp_path, orc):
             rows.append(fm.process(y) if mode == "fm" else orc.am_i16(y) if mode == "am" else orc.usb_i16(y))
         assert [len(r) for r in rows] == [204, 205, 205, 50]
         np.concatenate(rows).astype(np.int16).tofile(tmp_path / ("row%d.i16" % c))
-    exe = _build("test_tuner_real")
+    exe = build("test_tuner_real.cc")
     r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK (0 failures)" in r.stdout, r.stdout + r.stderr

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import fsk_restatement as fr
+from abi_checks import kernel_scratch
 from libsdr_amd import abi, nodes
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -149,15 +150,5 @@ def test_new_entry_points_are_declared_and_exported():
 def test_symbol_kernels_keep_out_of_scratch(tmp_path):
     """The detector serves L = 18 and L = 242 from one kernel whose ring lives in LDS (L is a run-time argument): no
     scratch, whatever L. Read from the code object's own metadata, as tests/test_abi.py does for the hot kernels."""
-    import re
-    import shutil
-    import subprocess
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    seen = {}
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, scratch in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            if any(k in name for k in ("fsk_detect", "ask_detect", "bits_flags", "bits_pll")):
-                seen[name] = int(scratch)
+    seen = kernel_scratch(tmp_path, "fsk_detect|ask_detect|bits_flags|bits_pll")
     assert len(seen) == 4 and not any(seen.values()), seen

@@ -321,6 +321,34 @@ def test_setters_touch_one_row_and_refused_ones_nothing(ctx, t):
 
 
 @pytest.mark.parametrize("t", ["i16", "f32"])
+def test_every_setter_refuses_a_row_outside_the_bank(ctx, t):
+    """The smallest bank that has two rows to tell apart: 2 rows, max_in 64, one call each. Rows -1 and 2 are refused by every
+    setter with the range in the message and nothing changed; a set_channel that succeeds leaves the other row as it is in a
+    bank that was never touched."""
+    dtype, C, n = DT[t], 2, 64
+    x = seeded_rows(dtype, C, 2 * n, seed=55)
+    bank, ref = make_pair(ctx, dtype, C, seed=21, max_in=n)
+    twin, _ = make_pair(ctx, dtype, C, seed=21, max_in=n)
+    for c in (-1, C):
+        for call in (lambda: bank.set_channel(c, LAMS[0], 1.0), lambda: bank.set_lambda(c, LAMS[0]), lambda: bank.set_enabled(c, False),
+                     lambda: bank.set_gain(c, 2.0)):
+            with pytest.raises(sa.SdrHipError) as e:
+                call()
+            assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), (c, str(e.value))
+    got, und, want = bank.process(x[:, :n]), twin.process(x[:, :n]), ref.process(x[:, :n])
+    assert not np.isnan(want.astype(np.float64)).any()
+    assert R.same(got, want) and R.same(got, und) and same_state(bank, ref)
+    new_target = 777.0 if t == "i16" else 0.125
+    bank.set_channel(1, LAMS[2], new_target)
+    ref.set_channel(1, LAMS[2], new_target)
+    got, und, want = bank.process(x[:, n:]), twin.process(x[:, n:]), ref.process(x[:, n:])
+    assert not np.isnan(want.astype(np.float64)).any()
+    assert R.same(got, want) and R.same(got[:1], und[:1]) and same_state(bank, ref)
+    for a, b in zip(bank.get_state(), twin.get_state()):
+        assert R.same(a[:1], b[:1])
+
+
+@pytest.mark.parametrize("t", ["i16", "f32"])
 def test_pass_through_rows_copy_and_held_rows_follow(ctx, t):
     dtype = DT[t]
     C, n = 9, 300

@@ -127,6 +127,7 @@ def test_handle_types_and_channel_range(ctx):
     bank = sa.FMDeemphBankI16(ctx, 2, [True, False, True], max_in=64)
     for c in (-1, 3):
         assert L.sdrhip_deemphbank_i16_set_enabled(bank._h, c, 1) == sa.abi.E_INVALID
+        assert "outside [0,3)" in L.sdrhip_last_error().decode()
     assert L.sdrhip_deemphbank_i16_get_enabled(bank._h, e, 2) == sa.abi.E_SIZE
     assert bank.enabled() == [True, False, True]
     bank.close()

@@ -196,6 +196,42 @@ def test_reset_channel_leaves_the_others_and_reset_keeps_the_flags(ctx):
         bank.close()
 
 
+def test_the_row_calls_refuse_a_row_outside_the_bank(ctx):
+    """The smallest bank that has two rows to tell apart: 2 rows of 64 bits, one call each. Rows -1 and 2 are refused by
+    set_enabled, reset_channel and channel_state with the range in the message and nothing changed; a set_enabled and a
+    reset_channel that succeed leave row 0 as it is in a bank never touched."""
+    rows, n, at = [ROWS[0], ROWS[1]], 64, 560   # (bits 560 ... 688: the sync word in the first call, two words in the second)
+    bank, twin, dev = sa.POCSAGBank(ctx, 2, n), sa.POCSAGBank(ctx, 2, n), Dev(ctx, 2)
+    try:
+        for c in (-1, 2):
+            for call in (lambda: bank.set_enabled(c, False), lambda: bank.reset_channel(c), lambda: bank.channel_state(c)):
+                with pytest.raises(sa.SdrHipError) as e:
+                    call()
+                assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), (c, str(e.value))
+        assert bank.enabled() == [True, True]
+        dec = [P.Decoder(), P.Decoder()]
+        got = dev.call(bank, rows, [at, at], [n, n])
+        check_call(0, got, [d.process(r[at:at + n]) for d, r in zip(dec, rows)], bank, [d.state() for d in dec])
+        check_call(0, dev.call(twin, rows, [at, at], [n, n]), got_events(got), twin, [d.state() for d in dec])
+        assert dec[1].state()[0] == P.RECEIVE   # (the call did move row 1: the reset below is seen)
+        bank.reset_channel(1)
+        bank.set_enabled(1, False)
+        got = dev.call(bank, rows, [at + n, at + n], [n, n])
+        check_call(1, got, [dec[0].process(rows[0][at + n:at + 2 * n]), []], bank, [dec[0].state(), (P.WAIT, 0, 0, 0)])
+        und = dev.call(twin, rows, [at + n, at + n], [n, n])
+        assert got_events(got)[0] == got_events(und)[0] != [] and bank.channel_state(0) == twin.channel_state(0)
+    finally:
+        dev.close()
+        bank.close()
+        twin.close()
+
+
+def got_events(got):
+    """A call's events per row, as lists of pairs."""
+    ev, evc, _ = got
+    return [[tuple(e) for e in ev[c, :int(evc[c])].tolist()] for c in range(ev.shape[0])]
+
+
 def test_host_pointer_process_equals_process_dev(ctx):
     rows = ROWS[:7]
     calls = schedule(rows, False)

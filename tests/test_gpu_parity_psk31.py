@@ -146,6 +146,30 @@ def test_set_channel_and_reset_between_calls(ctx):
     node.close()
 
 
+def test_set_channel_refuses_a_row_outside_the_bank(ctx):
+    """The smallest bank that has two rows to tell apart: 2 rows, max_in 64, one call each. Rows -1 and 2 are refused with the
+    range in the message and nothing changed; a set_channel that succeeds leaves row 0 as it is in a bank never touched."""
+    import libsdr_amd as sa
+    n, dF = 64, [0.1, 0.05]
+    x = _signal("cs16", 8000.0, 2 * n, 2, 17)
+    ref = R.Bank(8000.0, dF, R.table())
+    node, twin = (sa.BPSK31Bank(ctx, np.int16, 8000.0, dF, table=R.table(), max_in=n) for _ in range(2))
+    for c in (-1, 2):
+        with pytest.raises(sa.SdrHipError) as e:
+            node.set_channel(c, 0.02)
+        assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), (c, str(e.value))
+    ops = {1: lambda b: b.set_channel(1, 0.02)}
+    got, states = _run(node, x, [n, n], ops)
+    und, und_states = _run(twin, x, [n, n])
+    want, want_states = _run_ref(ref, x, [n, n], {1: lambda b: b.reset_row(1, 0.02)})
+    _same(got, want, states, want_states)
+    assert np.array_equal(states[0], und_states[0])                                           # the refused calls changed nothing
+    assert np.array_equal(got[1][0], und[1][0]) and np.array_equal(states[1][0], und_states[1][0])   # row 0 streamed on
+    assert not np.array_equal(states[1][1], und_states[1][1])                                 # and row 1 is a fresh node
+    node.close()
+    twin.close()
+
+
 @functools.lru_cache(maxsize=None)
 def _fixture_ref(Fs):
     """the fixtures of one sample rate side by side in the restatement (defined sincos): names, per-call bits, states"""

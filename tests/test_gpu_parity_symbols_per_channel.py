@@ -347,10 +347,12 @@ def test_kernel_names_and_one_parameter_handles(ctx):
     # a per-channel handle: a refused set_channel changes nothing
     bank = sa.SymbolDetectorBank(ctx, [("fsk", lm, ls), ("ask", False)], max_in=64, max_corr_len=20)
     big = sa.design_fsk_lut(FS, 1000.0, 1200.0)          # L = 22 > max_corr_len
-    for bad in (lambda: bank.set_channel(2, ("ask", False)), lambda: bank.set_channel(-1, ("ask", False)),
-                lambda: bank.set_channel(0, ("fsk", big, big))):
-        with pytest.raises(sa.SdrHipError):
+    for bad in (lambda: bank.set_channel(2, ("ask", False)), lambda: bank.set_channel(-1, ("ask", False))):
+        with pytest.raises(sa.SdrHipError) as e:
             bad()
+        assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), str(e.value)
+    with pytest.raises(sa.SdrHipError):
+        bank.set_channel(0, ("fsk", big, big))
     assert L.sdrhip_detectorbank_set_channel(bank._h, 0, 7, p, p, 18, 0) == sa.abi.E_INVALID
     assert L.sdrhip_detectorbank_set_channel(bank._h, 0, sa.DET_FSK, p, p, 0, 0) == sa.abi.E_INVALID
     assert L.sdrhip_detectorbank_set_channel(bank._h, 0, sa.DET_FSK, p, p, 21, 0) == sa.abi.E_UNSUPPORTED
@@ -366,6 +368,39 @@ def test_kernel_names_and_one_parameter_handles(ctx):
     want = [fr.FSKDetector(lm, ls).process(x[:1])[0], fr.ask_detect(x[1], False)]
     s = bank.process(x)
     assert np.array_equal(s[0], want[0]) and np.array_equal(s[1], want[1])
+
+
+@pytest.mark.hostptr_only
+def test_the_bitstream_banks_row_calls_refuse_a_row_outside_the_bank(ctx, symbols):
+    """The smallest bank that has two rows to tell apart: 2 rows, max_in 64, one call each. Rows -1 and 2 are refused by
+    set_channel and channel_info with the range in the message and nothing changed; a set_channel that succeeds leaves row 0
+    as it is in a bank never touched."""
+    n, cfgs = 64, [(1200.0, N), (2400.0, T)]
+    bank, twin = (sa.BitStreamBank(ctx, FS, [b for b, _ in cfgs], [m for _, m in cfgs], max_in=n) for _ in range(2))
+    before = [bank.channel_info(c, n) for c in range(2)]
+    for c in (-1, 2):
+        for call in (lambda: bank.set_channel(c, 1200.0, N), lambda: bank.channel_info(c, n)):
+            with pytest.raises(sa.SdrHipError) as e:
+                call()
+            assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), (c, str(e.value))
+    assert [bank.channel_info(c, n) for c in range(2)] == before
+    sym = symbols[[0, 4]]
+    calls = [sym[:, :n], sym[:, n:2 * n]]
+    sched = [[(0, cfgs[0])], [(0, cfgs[1]), (1, (1200.0, T))]]
+    got, und = [], []
+    for k, x in enumerate(calls):
+        if k == 1:
+            bank.set_channel(1, 1200.0, T)
+        for node, rows in ((bank, got), (twin, und)):
+            out, cnt = node.process_raw(x)
+            rows.append([out[c, :cnt[c]].copy() for c in range(2)])
+    for c in range(2):
+        _same([g[c] for g in got], _row(_ref_bits_node, sched[c], [x[c] for x in calls]), ("restatement", c))
+    _same(got[0], und[0], "the refused calls changed nothing")
+    _same([got[1][0]], [und[1][0]], "row 0 streamed on")
+    assert sum(g[0].size for g in got) > 0
+    bank.close()
+    twin.close()
 
 
 # ---- the chain on device pointers: modes bank -> detector bank -> BitStream bank -------------------------------------------------

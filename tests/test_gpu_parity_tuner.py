@@ -294,6 +294,32 @@ def test_tuner_retune_one_channel(ctx, orc, epi, form):
     assert not np.array_equal(y[17], ys[17])
 
 
+def test_tuner_setters_refuse_a_channel_outside_the_bank(ctx, orc, form):
+    """The smallest bank that has two rows to tell apart: 2 channels, max_in 64, one call each. Channels -1 and 2 are refused
+    by set_taps and set_shift with the range in the message and nothing changed; a retune of channel 1 that succeeds leaves
+    channel 0 as it is in a bank never retuned."""
+    C, order, D, n = 2, 21, 8, 64
+    tunes = bank_tunes(C, order, seed=9)
+    x = orc.IQSigGen(FS, [(100e3, 8000, 0.0), (-300e3, 6000, 0.3)]).next_cs16(2 * n)
+    bank, lut = make_bank(ctx, tunes, D, sa.EPI_NONE, n)
+    still, _ = make_bank(ctx, tunes, D, sa.EPI_NONE, n)
+    refs = make_refs(orc, tunes, lut, D, sa.EPI_NONE)
+    for c in (-1, C):
+        for call in (lambda: bank.set_taps(c, tunes[0][0]), lambda: bank.set_shift(c, 1, False)):
+            with pytest.raises(sa.SdrHipError) as e:
+                call()
+            assert e.value.code == sa.abi.E_INVALID and "outside [0,2)" in str(e.value), (c, str(e.value))
+    for k, chunk in enumerate(split(x, [n, n])):
+        if k == 1:
+            t = tune(-150e3, -150e3, 50e3, order)
+            bank.set_shift(1, t[1], t[2]); refs[1].bb.set_shift(t[1], t[2])
+            bank.set_taps(1, t[0]); refs[1].bb.set_taps(t[0])
+        y, ys = bank.process(chunk), still.process(chunk)
+        for c in range(C):
+            assert np.array_equal(y[c], refs[c].process(chunk)), (k, c)
+        assert np.array_equal(y[0], ys[0]) and (k == 0) == np.array_equal(y[1], ys[1]), k
+
+
 class _RowRetune:
     """One row of a bank driven by test_oracle_golden.replay_retune; the other rows keep their tunes."""
 

@@ -296,6 +296,7 @@ def test_mode_errors(ctx, orc, form):
         with pytest.raises(sa.SdrHipError) as e:
             bank.set_mode(c, m)
         assert e.value.code == sa.abi.E_INVALID, (c, m)
+        assert ("outside [0,%d)" % Cn in str(e.value)) == (c in (-1, Cn)), (c, m, str(e.value))
     few = (C.c_int * (Cn - 1))()
     assert sa.abi.lib().sdrhip_tunermodes_i16_get_modes(bank._h, few, Cn - 1) == sa.abi.E_INVALID
     assert bank.modes() == modes

@@ -55,23 +55,34 @@ def R(v):
 
 
 class FakeLib:
-    def __init__(self):
+    """signatures: the names the fake answers (default: abi.SIGNATURES; a side header's test adds its own table). answers:
+    name -> function of args that fills the call's outputs in place of _fill. scalars_only: arguments other than ints and
+    floats are recorded as None, not in their normal form."""
+
+    def __init__(self, signatures=None, answers=None, scalars_only=False):
         self.calls, self.reached, self.handles, self.mallocs = [], set(), {}, 0
+        self.signatures, self.answers, self.scalars_only = signatures or abi.SIGNATURES, answers or {}, scalars_only
 
     def __getattr__(self, name):
-        if name not in abi.SIGNATURES:
+        if name not in self.signatures:
             raise AttributeError(name)
         self.reached.add(name)
         return lambda *args: self._call(name, args)
 
     def _call(self, name, args):
-        argtypes = abi.SIGNATURES[name][1]
+        argtypes = self.signatures[name][1]
         assert len(args) == len(argtypes), (name, len(args), len(argtypes))
         for a, t in zip(args, argtypes):
             t.from_param(a)
         config = name.endswith(("_create", "_create_bank")) or "_set_" in name or "_design_" in name
-        self.calls.append((name,) + tuple(self._norm(a, config) for a in args))
-        self._fill(name, args)
+        if self.scalars_only:
+            self.calls.append((name,) + tuple(a if isinstance(a, (int, float)) else None for a in args))
+        else:
+            self.calls.append((name,) + tuple(self._norm(a, config) for a in args))
+        if name in self.answers:
+            self.answers[name](args)
+        else:
+            self._fill(name, args)
         return abi.OK
 
     def _norm(self, a, config):
@@ -120,12 +131,12 @@ class FakeLib:
 
 
 class Run:
-    """One case's fake library, recording router and close hook."""
+    """One case's fake library (default: a FakeLib of abi.SIGNATURES), recording router and — unless hook is False — close hook."""
 
-    def __init__(self, monkeypatch):
-        self.fake, self.mp = FakeLib(), monkeypatch
+    def __init__(self, monkeypatch, fake=None, hook=True):
+        self.fake, self.mp = fake or FakeLib(), monkeypatch
         monkeypatch.setattr(abi, "_lib", self.fake)
-        monkeypatch.setattr(nodes, "close_hooks", [lambda ctx: self.fake.calls.append(("hook", self.h(ctx)))])
+        monkeypatch.setattr(nodes, "close_hooks", [lambda ctx: self.fake.calls.append(("hook", self.h(ctx)))] if hook else [])
         self.route(False)
 
     def h(self, obj):

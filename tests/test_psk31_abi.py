@@ -1,62 +1,33 @@
 """The BPSK31 bank's C calls (include/sdrhip_psk31.h), what can be checked without a GPU: every function of the header is exported
-by libsdrhip.so and has a prototype in libsdr_amd/abi_psk31.py, and nothing else of the family is exported; the other headers'
-bindings are what they were; every argument rule of the two create calls answers BEFORE the context is looked at, in the header's
+by libsdrhip.so and has a prototype in libsdr_amd/abi_psk31.py, and nothing else of the family is exported (tests/test_side_headers.py
+holds what the headers' bindings owe each other); every argument rule of the two create calls answers BEFORE the context is looked at, in the header's
 order; the calls on a handle refuse a NULL one; both kernels exist for gfx950 and use no scratch; and the Python wrappers, driven
 against the fake library of tests/test_nodes_calls.py, make the calls they should."""
 import ctypes as C
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import psk31_restatement as R
+from abi_checks import assert_header_binding, kernel_scratch, last_error, no_ctx_code
 from libsdr_amd import abi, nodes
 from test_nodes_calls import FakeLib, NAMES, Run, ramp
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 NEW = ["sdrhip_design_inpol_taps", "sdrhip_psk31_create", "sdrhip_psk31_destroy", "sdrhip_psk31_get_state", "sdrhip_psk31_kernel_names",
        "sdrhip_psk31_out_capacity", "sdrhip_psk31_plan_info", "sdrhip_psk31_process", "sdrhip_psk31_process_dev", "sdrhip_psk31_reset",
        "sdrhip_psk31_set_channel", "sdrhip_psk31bank_create"]
 fp = C.POINTER(C.c_float)
-NO_CTX = lambda: abi.E_NODEVICE if nodes.device_count() == 0 else abi.E_INVALID
 INF, NAN = float("inf"), float("nan")
-
-
-def _text():
-    return abi.lib().sdrhip_last_error().decode()
 
 
 def test_header_binding_and_exports_agree():
     from libsdr_amd import abi_psk31
-    declared = abi_psk31.header_functions()
-    assert declared == sorted(NEW)
-    assert sorted(abi_psk31.SIGNATURES) == declared
-    fresh = C.CDLL(abi.SO_PATH)   # (looked up by name in the library's own export table, not through the binding)
-    for f in declared:
-        assert C.cast(getattr(fresh, f), C.c_void_p).value, f
-    L = abi_psk31.lib()
-    assert L is abi.lib()
-    for f, (res, args) in abi_psk31.SIGNATURES.items():
-        fn = getattr(L, f)
-        assert fn.restype is res and list(fn.argtypes) == args, f
-    syms = subprocess.run([LLVM + "llvm-readelf", "--dyn-syms", "-W", abi.SO_PATH], capture_output=True, text=True, check=True).stdout
-    got = sorted(set(re.findall(r"\b(sdrhip_(?:psk31[a-z0-9_]*|design_inpol[a-z0-9_]*))\b", syms)))
-    assert got == declared
+    assert_header_binding(abi_psk31, NEW, r"\b(sdrhip_(?:psk31[a-z0-9_]*|design_inpol[a-z0-9_]*))\b")
 
 
-def test_the_other_headers_bindings_are_unchanged_by_this_module():
-    from libsdr_amd import abi_agc, abi_pocsag, abi_rx
-    before = dict(abi.SIGNATURES), dict(abi_rx.SIGNATURES), dict(abi_pocsag.SIGNATURES), dict(abi_agc.SIGNATURES), list(abi.lib()._declared)
-    wrappers = sorted(k for k, v in vars(nodes).items() if isinstance(v, type))
-    from libsdr_amd import abi_psk31, psk31
-    abi_psk31.lib()
-    assert (dict(abi.SIGNATURES), dict(abi_rx.SIGNATURES), dict(abi_pocsag.SIGNATURES), dict(abi_agc.SIGNATURES), list(abi.lib()._declared)) == before
-    for other in (abi.header_functions(), abi_rx.header_functions(), abi_pocsag.header_functions(), abi_agc.header_functions()):
-        assert not set(NEW) & set(other)
-    assert sorted(k for k, v in vars(nodes).items() if isinstance(v, type)) == wrappers
+def test_the_package_exports_this_modules_classes():
     import libsdr_amd
+    from libsdr_amd import psk31
     assert libsdr_amd.BPSK31 is psk31.BPSK31 and libsdr_amd.BPSK31Bank is psk31.BPSK31Bank and libsdr_amd.Varicode is psk31.Varicode
     assert issubclass(psk31.BPSK31, psk31.BPSK31Bank) and issubclass(psk31.BPSK31Bank, nodes._Node)
 
@@ -85,9 +56,9 @@ def _one(dtype=0, Fs=8000.0, dF=0.1, table=None, channels=3, max_in=1024, null=(
 def test_create_without_a_context():
     for code, h in (_bank(), _one(), _bank(dtype=1), _one(dtype=1), _one(Fs=2000.0), _one(dF=np.pi), _one(channels=1), _one(channels=65535),
                     _one(max_in=1), _one(max_in=(1 << 30) - 1), _one(Fs=1e6)):
-        assert code == NO_CTX() and h is None
+        assert code == no_ctx_code() and h is None
     if nodes.device_count() == 0:
-        assert "no CPU fallback" in _text()
+        assert "no CPU fallback" in last_error()
 
 
 def _bad_table(v):
@@ -124,14 +95,14 @@ ONE_RULES = RULES + [
 def test_bank_create_argument_rules_come_before_the_context(kw, want, text):
     code, h = _bank(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 @pytest.mark.parametrize("kw,want,text", ONE_RULES, ids=[str(i) for i in range(len(ONE_RULES))])
 def test_create_argument_rules_come_before_the_context(kw, want, text):
     code, h = _one(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 def test_calls_on_a_null_handle():
@@ -139,12 +110,12 @@ def test_calls_on_a_null_handle():
     L = abi_psk31.lib()
     g, e, t, sz = (C.c_float * 4)(), (C.c_int * 4)(), C.c_int(7), C.c_size_t(9)
     buf = C.create_string_buffer(64)
-    assert L.sdrhip_psk31_process_dev(None, None, 0, 0, None, 0, None) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_psk31_process(None, None, 0, 0, None, 0, None) == abi.E_INVALID and "NULL" in _text()
+    assert L.sdrhip_psk31_process_dev(None, None, 0, 0, None, 0, None) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_psk31_process(None, None, 0, 0, None, 0, None) == abi.E_INVALID and "NULL" in last_error()
     for call in (lambda: L.sdrhip_psk31_set_channel(None, 0, 0.1), lambda: L.sdrhip_psk31_get_state(None, g, g, g, g, e, e, 4),
                  lambda: L.sdrhip_psk31_reset(None), lambda: L.sdrhip_psk31_kernel_names(None, buf, 64),
                  lambda: L.sdrhip_psk31_out_capacity(None, 16, C.byref(sz))):
-        assert call() == abi.E_INVALID and "NULL" in _text()
+        assert call() == abi.E_INVALID and "NULL" in last_error()
     assert sz.value == 9
     assert L.sdrhip_psk31_plan_info(None, 16, C.byref(t), None) == abi.E_INVALID and t.value == 7
     assert L.sdrhip_psk31_destroy(None) == abi.OK
@@ -152,61 +123,37 @@ def test_calls_on_a_null_handle():
 
 
 def test_both_kernels_exist_for_gfx950_without_scratch(tmp_path):
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    seen = {}
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, b in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            m = re.search(r"\d(psk31_[a-z0-9_]+_kernel)", name)
-            if m:
-                seen[m.group(1)] = int(b)
+    seen = kernel_scratch(tmp_path, r"\d(psk31_[a-z0-9_]+_kernel)")
     assert seen == {"psk31_cs16_kernel": 0, "psk31_cf32_kernel": 0}, seen
 
 
 # ---- the Python wrappers against a fake library --------------------------------------------------------------------------------
 
-def _sigs():
+def _plan_info(args):
+    args[2]._obj.value, args[3]._obj.value = 256, 4
+
+
+def _get_state(args):
+    for a, v in zip(args[1:7], (1.0, 2.0, 3.0, 4.0, 5, -1)):
+        a._arr[...] = v
+
+
+def _process(args):
+    args[6]._arr[...] = (2, 1)   # counts
+    args[4]._arr[...] = 1        # bits
+
+
+def _taps(args):
+    args[0]._arr[...] = 0.5
+
+
+def _run(monkeypatch):
+    """The fake of test_nodes_calls.py, answering include/sdrhip_psk31.h's names as well (out_capacity(n) answers n // 4); it
+    records scalar arguments only, and no close hook."""
     from libsdr_amd import abi_psk31
-    return dict(abi.SIGNATURES, **abi_psk31.SIGNATURES)
-
-
-class PskFake(FakeLib):
-    """The fake of test_nodes_calls.py, answering include/sdrhip_psk31.h's names as well (out_capacity(n) answers n // 4)."""
-
-    def __getattr__(self, name):
-        if name not in _sigs():
-            raise AttributeError(name)
-        self.reached.add(name)
-        return lambda *args: self._call(name, args)
-
-    def _call(self, name, args):
-        argtypes = _sigs()[name][1]
-        assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-        for a, t in zip(args, argtypes):
-            t.from_param(a)
-        self.calls.append((name,) + tuple(a if isinstance(a, (int, float)) else None for a in args))
-        if name == "sdrhip_psk31_plan_info":
-            args[2]._obj.value, args[3]._obj.value = 256, 4
-        elif name == "sdrhip_psk31_get_state":
-            for a, v in zip(args[1:7], (1.0, 2.0, 3.0, 4.0, 5, -1)):
-                a._arr[...] = v
-        elif name == "sdrhip_psk31_process":
-            args[6]._arr[...] = (2, 1)   # counts
-            args[4]._arr[...] = 1        # bits
-        elif name == "sdrhip_design_inpol_taps":
-            args[0]._arr[...] = 0.5
-        else:
-            self._fill(name, args)
-        return abi.OK
-
-
-class PskRun(Run):
-    def __init__(self, monkeypatch):
-        super().__init__(monkeypatch)
-        self.fake = PskFake()
-        monkeypatch.setattr(abi, "_lib", self.fake)
-        monkeypatch.setattr(nodes, "close_hooks", [])
+    answers = {"sdrhip_psk31_plan_info": _plan_info, "sdrhip_psk31_get_state": _get_state, "sdrhip_psk31_process": _process,
+               "sdrhip_design_inpol_taps": _taps}
+    return Run(monkeypatch, FakeLib(signatures=dict(abi.SIGNATURES, **abi_psk31.SIGNATURES), answers=answers, scalars_only=True), hook=False)
 
 
 def _drive(r):
@@ -238,7 +185,7 @@ def _drive(r):
 
 
 def test_wrapper_calls_against_the_fake_library(monkeypatch):
-    r = PskRun(monkeypatch)
+    r = _run(monkeypatch)
     _drive(r)
     names = [c[0] for c in r.fake.calls]
     assert names == [
@@ -267,7 +214,7 @@ def test_wrapper_calls_against_the_fake_library(monkeypatch):
 
 def test_a_mistyped_entry_point_fails_construction(monkeypatch):
     from libsdr_amd import psk31
-    r = PskRun(monkeypatch)
+    r = _run(monkeypatch)
     ctx = r.ctx()
     monkeypatch.setattr(psk31.BPSK31Bank, "_calls", psk31.BPSK31Bank._calls + " get_sttae")
     with pytest.raises(AttributeError, match="sdrhip_psk31_get_sttae"):

@@ -1,57 +1,30 @@
 """The receiver bank's C calls (include/sdrhip_rx.h), what can be checked without a GPU: every function of the header is
 exported by libsdrhip.so and has a prototype in libsdr_amd/abi_rx.py, and nothing else has; the argument rules of the two new
 create calls that answer BEFORE the context is looked at, so on a machine without a device too; the calls that exist for a bank
-only refuse a NULL handle; sdrhip.h's declared set and abi.SIGNATURES are what they were — the new surface lives in files of its
-own; the de-emphasis kernels exist in both instances and none uses scratch."""
+only refuse a NULL handle; the wrappers live in a module of their own (what the headers' bindings owe each other:
+tests/test_side_headers.py); the de-emphasis kernels exist in both instances and none uses scratch."""
 import ctypes as C
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_checks import assert_header_binding, kernel_scratch, last_error, no_ctx_code
 from libsdr_amd import abi, nodes
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 NEW = ["sdrhip_deemphbank_i16_create", "sdrhip_deemphbank_i16_get_enabled", "sdrhip_deemphbank_i16_set_enabled", "sdrhip_rxbank_create",
        "sdrhip_rxbank_destroy", "sdrhip_rxbank_process", "sdrhip_rxbank_process_dev", "sdrhip_rxbank_sizes"]
 ip = C.POINTER(C.c_int)
-NO_CTX = lambda: abi.E_NODEVICE if nodes.device_count() == 0 else abi.E_INVALID
-
-
-def _text():
-    return abi.lib().sdrhip_last_error().decode()
 
 
 def test_header_binding_and_exports_agree():
     from libsdr_amd import abi_rx
-    declared = abi_rx.header_functions()
-    assert declared == sorted(NEW)
-    assert sorted(abi_rx.SIGNATURES) == declared
-    fresh = C.CDLL(abi.SO_PATH)   # (looked up by name in the library's own export table, not through the binding)
-    for f in declared:
-        assert C.cast(getattr(fresh, f), C.c_void_p).value, f
-    L = abi_rx.lib()
-    assert L is abi.lib()
-    for f, (res, args) in abi_rx.SIGNATURES.items():
-        fn = getattr(L, f)
-        assert fn.restype is res and list(fn.argtypes) == args, f
-    # nothing else of the new families is exported: the library's dynamic symbols of these prefixes are the header's
-    syms = subprocess.run([LLVM + "llvm-readelf", "--dyn-syms", "-W", abi.SO_PATH], capture_output=True, text=True, check=True).stdout
-    got = sorted(set(re.findall(r"\b(sdrhip_(?:rxbank|deemphbank)_[a-z0-9_]+)\b", syms)))
-    assert got == declared
+    assert_header_binding(abi_rx, NEW, r"\b(sdrhip_(?:rxbank|deemphbank)_[a-z0-9_]+)\b")
 
 
-def test_the_frozen_surface_is_unchanged_by_this_module():
-    before_sig, before_decl = dict(abi.SIGNATURES), list(abi.lib()._declared)
-    from libsdr_amd import abi_rx, receiver
-    abi_rx.lib()
-    assert abi.SIGNATURES == before_sig and abi.lib()._declared == before_decl
-    assert sorted(abi.lib()._declared) == abi.header_functions()
-    assert not set(NEW) & set(abi.header_functions()) and not set(NEW) & set(abi.SIGNATURES)
-    assert not hasattr(nodes, "ReceiverBank") and not hasattr(nodes, "FMDeemphBankI16")
+def test_the_wrappers_live_in_a_module_of_their_own():
     import libsdr_amd
+    from libsdr_amd import receiver
+    assert not hasattr(nodes, "ReceiverBank") and not hasattr(nodes, "FMDeemphBankI16")
     assert libsdr_amd.ReceiverBank is receiver.ReceiverBank and libsdr_amd.FMDeemphBankI16 is receiver.FMDeemphBankI16
     assert issubclass(receiver.FMDeemphBankI16, nodes.FMDeemphI16)
 
@@ -69,12 +42,12 @@ def _deemph(alpha=2, enabled=(1, 0, 1), channels=None, max_in=4096, null=()):
 
 def test_deemph_bank_without_a_context():
     code, h = _deemph()
-    assert code == NO_CTX() and h is None
+    assert code == no_ctx_code() and h is None
     if nodes.device_count() == 0:
-        assert "no CPU fallback" in _text()
+        assert "no CPU fallback" in last_error()
     # the limits are valid: alpha 1 and 32767, 8192 channels
-    assert _deemph(alpha=1)[0] == NO_CTX() and _deemph(alpha=32767)[0] == NO_CTX()
-    assert _deemph(enabled=(1,) * 8192)[0] == NO_CTX()
+    assert _deemph(alpha=1)[0] == no_ctx_code() and _deemph(alpha=32767)[0] == no_ctx_code()
+    assert _deemph(enabled=(1,) * 8192)[0] == no_ctx_code()
 
 
 DEEMPH_RULES = [
@@ -92,7 +65,7 @@ DEEMPH_RULES = [
 def test_deemph_bank_argument_rules_come_before_the_context(kw, want, text):
     code, h = _deemph(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 def test_receiver_bank_create_rules_without_a_device():
@@ -104,10 +77,10 @@ def test_receiver_bank_create_rules_without_a_device():
     out = C.c_void_p(0x1)
     for t, d, b, o in ((None, fake, fake, C.byref(out)), (fake, None, fake, C.byref(out)), (fake, fake, None, C.byref(out)),
                        (fake, fake, fake, None)):
-        assert L.sdrhip_rxbank_create(None, t, None, d, b, o) == abi.E_INVALID and "NULL" in _text()
+        assert L.sdrhip_rxbank_create(None, t, None, d, b, o) == abi.E_INVALID and "NULL" in last_error()
     assert out.value is None
     out = C.c_void_p(0x1)
-    assert L.sdrhip_rxbank_create(None, fake, None, fake, fake, C.byref(out)) == NO_CTX() and out.value is None
+    assert L.sdrhip_rxbank_create(None, fake, None, fake, fake, C.byref(out)) == no_ctx_code() and out.value is None
 
 
 def test_calls_on_a_null_handle():
@@ -115,9 +88,9 @@ def test_calls_on_a_null_handle():
     L = abi_rx.lib()
     e = (C.c_int * 4)()
     n = C.c_size_t(7)
-    assert L.sdrhip_deemphbank_i16_set_enabled(None, 0, 1) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_deemphbank_i16_get_enabled(None, e, 4) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_rxbank_sizes(None, 16, C.byref(n), None) == abi.E_INVALID and "NULL" in _text()
+    assert L.sdrhip_deemphbank_i16_set_enabled(None, 0, 1) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_deemphbank_i16_get_enabled(None, e, 4) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_rxbank_sizes(None, 16, C.byref(n), None) == abi.E_INVALID and "NULL" in last_error()
     assert L.sdrhip_rxbank_process_dev(None, None, 0, None, 0, None, None, 0, None) == abi.E_INVALID
     assert L.sdrhip_rxbank_process(None, None, 0, None, 0, None, None, 0, None) == abi.E_INVALID
     assert L.sdrhip_rxbank_destroy(None) == abi.OK
@@ -125,14 +98,7 @@ def test_calls_on_a_null_handle():
 
 def test_deemph_kernels_exist_in_both_instances_without_scratch(tmp_path):
     """One body, two instances: deemph_i16_{seq,spec,copy}_kernel<false> (the one-parameter handle's) and <true> (the bank's)."""
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    seen = {}
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, b in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            m = re.search(r"\d(deemph_i16_(?:seq|spec|copy)_kernel)ILb([01])E", name)
-            if m:
-                seen[m.group(1), int(m.group(2))] = int(b)
+    seen = kernel_scratch(tmp_path, r"\d(deemph_i16_(?:seq|spec|copy)_kernel)ILb([01])E")
+    seen = {(k, int(b)): v for (k, b), v in seen.items()}
     assert sorted(seen) == [("deemph_i16_%s_kernel" % k, b) for k in ("copy", "seq", "spec") for b in (0, 1)], sorted(seen)
     assert not any(seen.values()), seen

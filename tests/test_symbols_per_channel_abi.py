@@ -5,19 +5,16 @@ BEFORE the context is looked at, so on a machine without a device too; the no-de
 new kernels exist for gfx950 under names of their own, beside the one-parameter kernels, and none uses scratch."""
 import ctypes as C
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_checks import kernel_scratch, last_error, no_ctx_code
 from libsdr_amd import abi, nodes
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 NEW = ["sdrhip_detectorbank_create", "sdrhip_detectorbank_set_channel", "sdrhip_bitsbank_create",
        "sdrhip_bitsbank_set_channel", "sdrhip_bitsbank_channel_info"]
 ip, f32p = C.POINTER(C.c_int), C.POINTER(C.c_float)
-NO_CTX = lambda: abi.E_NODEVICE if nodes.device_count() == 0 else abi.E_INVALID
 
 
 def test_new_calls_are_declared_bound_and_exported():
@@ -33,10 +30,6 @@ def test_new_calls_are_declared_bound_and_exported():
     import libsdr_amd
     assert libsdr_amd.SymbolDetectorBank is nodes.SymbolDetectorBank and libsdr_amd.BitStreamBank is nodes.BitStreamBank
     assert callable(nodes.SymbolDetectorBank.set_channel) and callable(nodes.BitStreamBank.set_channel)
-
-
-def _text():
-    return abi.lib().sdrhip_last_error().decode()
 
 
 def _det(kinds=(abi.DET_FSK, abi.DET_ASK, abi.DET_FSK), lens=(18, 0, 5), max_corr_len=0, channels=None, max_in=4096, null=()):
@@ -71,17 +64,17 @@ def test_null_context():
     argument it is in every create call elsewhere; *out is NULL."""
     for make in (_det, _bits):
         code, h = make()
-        assert code == NO_CTX() and h is None, make
+        assert code == no_ctx_code() and h is None, make
         if nodes.device_count() == 0:
-            assert "no CPU fallback" in _text()
+            assert "no CPU fallback" in last_error()
     # an ASK-only bank needs no LUTs
     code, h = _det(kinds=(abi.DET_ASK, abi.DET_ASK), lens=(0, 0), null=("mark", "space"))
-    assert code == NO_CTX() and h is None
+    assert code == no_ctx_code() and h is None
     # max_corr_len = 2048 and corr_len = 2048 are the limits
-    assert _det(kinds=(abi.DET_FSK,), lens=(2048,), max_corr_len=2048)[0] == NO_CTX()
-    assert _bits(bauds=(22050.0 / 2048,), modes=(0,), max_corr_len=2048)[0] == NO_CTX()
+    assert _det(kinds=(abi.DET_FSK,), lens=(2048,), max_corr_len=2048)[0] == no_ctx_code()
+    assert _bits(bauds=(22050.0 / 2048,), modes=(0,), max_corr_len=2048)[0] == no_ctx_code()
     # 8192 channels x 2048 entries = 2^24: the largest LUT buffer a detector bank may ask for
-    assert _det(kinds=(abi.DET_ASK,) * 8192, lens=(0,) * 8192, max_corr_len=2048, null=("mark", "space"))[0] == NO_CTX()
+    assert _det(kinds=(abi.DET_ASK,) * 8192, lens=(0,) * 8192, max_corr_len=2048, null=("mark", "space"))[0] == no_ctx_code()
 
 
 DET_RULES = [
@@ -107,7 +100,7 @@ DET_RULES = [
 def test_detector_argument_rules_come_before_the_context(kw, want, text):
     code, h = _det(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 BITS_RULES = [
@@ -129,30 +122,24 @@ BITS_RULES = [
 def test_bits_argument_rules_come_before_the_context(kw, want, text):
     code, h = _bits(**kw)
     assert code == want and (h is None or "out" in kw.get("null", ())), (kw, code)
-    assert text in _text(), (kw, _text())
+    assert text in last_error(), (kw, last_error())
 
 
 def test_calls_on_a_null_handle():
     L = abi.lib()
     lut = np.ones((18, 2), np.float32).ctypes.data_as(f32p)
-    assert L.sdrhip_detectorbank_set_channel(None, 0, abi.DET_FSK, lut, lut, 18, 0) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_detectorbank_set_channel(None, 0, abi.DET_ASK, None, None, 0, 1) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_bitsbank_set_channel(None, 0, 1200.0, abi.BITS_NORMAL) == abi.E_INVALID and "NULL" in _text()
-    assert L.sdrhip_bitsbank_channel_info(None, 0, 16, None, None, None, None) == abi.E_INVALID and "NULL" in _text()
+    assert L.sdrhip_detectorbank_set_channel(None, 0, abi.DET_FSK, lut, lut, 18, 0) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_detectorbank_set_channel(None, 0, abi.DET_ASK, None, None, 0, 1) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_bitsbank_set_channel(None, 0, 1200.0, abi.BITS_NORMAL) == abi.E_INVALID and "NULL" in last_error()
+    assert L.sdrhip_bitsbank_channel_info(None, 0, 16, None, None, None, None) == abi.E_INVALID and "NULL" in last_error()
 
 
 def test_per_channel_kernels_exist_beside_the_one_parameter_kernels(tmp_path):
     """Entry points of their own, the parent's kernels under their names, and no scratch in any of them."""
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
     scratch = {}
     want = ["detectorbank_kernel", "bitsbank_flags_kernel", "bitsbank_pll_kernel", "bitsbank_fill_kernel",
             "fsk_detect_kernel", "ask_detect_kernel", "bits_flags_kernel", "bits_pll_kernel", "bits_fill_kernel"]
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, b in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            for k in want:
-                if re.search(r"\d%s[A-Z]" % k, name):   # (the mangled name: <length><name>E...)
-                    scratch.setdefault(k, []).append(int(b))
+    for name, b in kernel_scratch(tmp_path, r"\d(?:%s)[A-Z]" % "|".join(want)).items():   # (the mangled name: <length><name>E...)
+        scratch.setdefault(re.search("|".join(want), name).group(0), []).append(b)
     assert sorted(scratch) == sorted(want), sorted(scratch)
     assert all(v == [0] for v in scratch.values()), scratch

@@ -2,14 +2,14 @@
 and exported; the kernels exist for gfx950, keep out of scratch, and the hot form is matrix code."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import abi_checks
+from abi_checks import LLVM
 from libsdr_amd import abi, nodes
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 TUNER_FUNCTIONS = ["sdrhip_tuner_i16_create", "sdrhip_tuner_i16_destroy", "sdrhip_tuner_i16_kernel_names", "sdrhip_tuner_i16_out_count",
                    "sdrhip_tuner_i16_plan_info", "sdrhip_tuner_i16_process", "sdrhip_tuner_i16_process_dev", "sdrhip_tuner_i16_reset", "sdrhip_tuner_i16_set_input_format",
                    "sdrhip_tuner_i16_set_shift", "sdrhip_tuner_i16_set_taps"]
@@ -29,23 +29,14 @@ def test_tuner_abi_is_declared_bound_and_exported():
 
 @pytest.fixture(scope="module")
 def code_objects(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tuner_co")
-    so = shutil.copy(abi.SO_PATH, d / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=d)
-    objs = sorted(d.glob("lib.so.*gfx950"))
+    objs = abi_checks.code_objects(tmp_path_factory.mktemp("tuner_co"))
     assert objs, "no gfx950 code object in the library"
     return objs
 
 
 def _tuner_kernels(objs):
     """{kernel name: (code object, scratch bytes)} of every tuner_ kernel."""
-    found = {}
-    for o in objs:
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        for name, scratch in re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)", notes):
-            if "tuner_" in name:
-                found[name] = (o, int(scratch))
-    return found
+    return {name: (o, scratch) for o, name, scratch in abi_checks.kernels(objs) if "tuner_" in name}
 
 
 def test_tuner_kernels_keep_out_of_scratch(code_objects):

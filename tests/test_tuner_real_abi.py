@@ -6,15 +6,13 @@ their own; nodes.TunerBankI16 has the real form."""
 import ctypes as C
 import inspect
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_checks import kernel_scratch, no_ctx_code
 from libsdr_amd import abi, nodes
 
-LLVM = "/opt/rocm/lib/llvm/bin/"
 REAL_FUNCTIONS = {"sdrhip_tunerbb_i16_create": "sdrhip_tuner_i16_create", "sdrhip_tunermodes_bb_i16_create": "sdrhip_tunermodes_i16_create"}
 
 ORDER, CHANNELS = 21, 3
@@ -73,7 +71,6 @@ def _create(a, epilogue=abi.EPI_NONE, modes=None, null=()):
 
 
 MODES = [abi.EPI_FM, abi.EPI_AM, abi.EPI_USB]
-NO_CTX = lambda: abi.E_NODEVICE if nodes.device_count() == 0 else abi.E_INVALID
 
 
 @pytest.mark.parametrize("per_channel", [False, True], ids=["one_epilogue", "modes"])
@@ -81,7 +78,7 @@ def test_null_context(per_channel):
     """Valid arguments and no context: SDRHIP_E_NODEVICE where no device exists (there is no CPU fallback), the invalid argument
     it is in every create call elsewhere; *out is NULL."""
     code, h = _create(_args(), modes=MODES if per_channel else None)
-    assert code == NO_CTX() and h is None
+    assert code == no_ctx_code() and h is None
     if nodes.device_count() == 0:
         assert b"no CPU fallback" in abi.lib().sdrhip_last_error()
 
@@ -106,7 +103,7 @@ def test_argument_rules_come_before_the_context(per_channel):
             a = _args()
             a["taps"][CHANNELS - 1, ORDER - 1, comp] = v
             code, h = _create(a, modes=modes)
-            assert code == (NO_CTX() if ok else abi.E_UNSUPPORTED) and h is None, (v, comp, code)
+            assert code == (no_ctx_code() if ok else abi.E_UNSUPPORTED) and h is None, (v, comp, code)
     if per_channel:
         for bad in ([abi.EPI_NONE] + MODES[1:], MODES[:2] + [7], MODES[:2] + [-1]):
             code, h = _create(_args(), modes=bad)
@@ -120,12 +117,7 @@ def test_argument_rules_come_before_the_context(per_channel):
 def test_real_bank_kernels_exist_under_their_own_names(tmp_path):
     """Both forms x four epilogues, and one instance per form that reads the demodulator per channel: tuner_bb_i16_* — no name
     of the complex bank's set (tests/test_tuner_cpu.py, tests/test_tuner_modes_abi.py count those)."""
-    so = shutil.copy(abi.SO_PATH, tmp_path / "lib.so")
-    subprocess.run([LLVM + "llvm-objdump", "--offloading", str(so)], capture_output=True, text=True, check=True, cwd=tmp_path)
-    names = set()
-    for o in sorted(tmp_path.glob("lib.so.*gfx950")):
-        notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(o)], capture_output=True, text=True).stdout
-        names |= {n for n in re.findall(r"\.name:\s+(\S+)", notes) if "tuner_bb_i16_" in n}
+    names = set(kernel_scratch(tmp_path, "tuner_bb_i16_"))
     for form in ("valu", "mfma"):
         assert sum("tuner_bb_i16_%s_kernel" % form in n for n in names) == 4, sorted(names)
         assert sum("tuner_bb_i16_modes_%s_kernel" % form in n for n in names) == 1, sorted(names)
