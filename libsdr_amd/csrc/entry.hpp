@@ -108,26 +108,26 @@ static inline void run_staged(sdrhip_ctx *ctx, Staging &st, size_t in_cap_b, siz
   SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
-// The host-pointer call of a node that writes up to capacity(n) bytes per row and says in counts[c] how many: the head
+// The host-pointer call of a node that writes up to capacity(n) elements per row and says in counts[c] how many: the head
 // checks the counts pointer with the handle, an empty call still zeroes the caller's counts, the staged output is zeroed
-// first (the bytes of a row behind counts[c] reach the caller as zeros) and the counts come back with the rows. H also has
-// `int C`, `capacity(n)`, `DevBuf<uint32_t> counts` and `Staging stage`; launch(in_dev, out_dev, cap) runs the node on
-// packed rows with h->counts.p. in_elem_b: the bytes of one input element.
+// first (the elements of a row behind counts[c] reach the caller as zeros) and the counts come back with the rows. H also
+// has `int C`, `capacity(n)`, `DevBuf<uint32_t> counts` and `Staging stage`; launch(in_dev, out_dev, cap) runs the node on
+// packed rows with h->counts.p. in_elem_b, out_elem_b: the bytes of one input / output element (the strides count elements).
 template <class H, class Launch>
 static inline void process_counted(H *h, const void *in_host, size_t n, size_t in_stride, size_t in_elem_b, uint8_t *out_host,
-                                   size_t out_stride, uint32_t *counts_host, Launch &&launch) {
+                                   size_t out_stride, uint32_t *counts_host, Launch &&launch, size_t out_elem_b = 1) {
   SDRHIP_REQUIRE(h && counts_host, SDRHIP_E_INVALID, "NULL argument");
   if (!call_begin(h, "n", n, in_host, out_host)) { memset(counts_host, 0, (size_t)h->C * sizeof(uint32_t)); return; }
-  const size_t cap = h->capacity(n), C = (size_t)h->C, eb = in_elem_b, out_cap_b = C * h->capacity(h->max_in);
+  const size_t cap = h->capacity(n), C = (size_t)h->C, eb = in_elem_b, ob = out_elem_b, out_cap_b = C * h->capacity(h->max_in) * ob;
   const Strides s = call_strides("n", n, in_stride, cap, out_stride, STRIDE_IN | STRIDE_OUT, "capacity");
   // (where a set_channel can raise the capacity of max_in, the staged rows grow with it)
   if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
-  run_staged(h->ctx, h->stage, C * h->max_in * eb, out_cap_b, {in_host, s.in * eb, n * eb, C}, {out_host, s.out, cap, C},
+  run_staged(h->ctx, h->stage, C * h->max_in * eb, out_cap_b, {in_host, s.in * eb, n * eb, C}, {out_host, s.out * ob, cap * ob, C},
              [&](void *in, void *out) {
                h->stage.out.zero(h->ctx->stream);
                launch(in, static_cast<uint8_t *>(out), cap);
                SDRHIP_CHECK_HIP(hipMemcpyAsync(counts_host, h->counts.p, C * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream));
-               return cap;
+               return cap * ob;
              });
 }
 
