@@ -254,7 +254,7 @@ def lib():
 # what bind_header returned. SIGNATURES above and the library's `_declared` list stay the binding of sdrhip.h alone, and no
 # side module's table is touched by another's.
 SIDE_HEADERS = {}
-# The same for the headers added since tests/test_side_headers.py pinned the table above to its four (abi_resample): a second
+# The same for the headers added since tests/test_side_headers.py pinned the table above to its four (abi_resample, abi_channelizer): a second
 # table, so that test stays as it is. build() checks both for missing symbols.
 LATER_SIDE_HEADERS = {}
 

@@ -1,0 +1,86 @@
+"""numpy-facing wrapper over include/sdrhip_channelizer.h (libsdr_amd.abi_channelizer): the polyphase channelizer — ONE antenna
+row to M uniform channels, each 1 / M of the band wide and decimated by D, in one pass; complex float rows out, one per selected
+channel, as the resampler, BPSK31 and AGC banks take them through process_dev."""
+import ctypes as C
+
+import numpy as np
+
+from . import abi_channelizer
+from .abi import check
+from .abi_channelizer import CHAN_CS16, CHAN_CF32
+from .nodes import _Counted, _out, _p, _scalar_dtype, _text
+
+__all__ = ["Channelizer", "CHAN_CS16", "CHAN_CF32"]
+
+
+class Channelizer(_Counted):
+    """y_k[m] = sum_l h[l] x[t_m - l] exp(-2 pi i k (t_m - l) / M), t_m = (m + 1) D - 1 (sdrhip_channelizer.h has the contract).
+    dtype: np.int16 or np.float32, the scalar of the complex input row [n, 2]; taps: the prototype low-pass as doubles (rounded
+    once to float32); channels: the channels to write, any order, no duplicates (None: all M in order). process(x) returns
+    [rows, n_out, 2] float32, row i holding channel selected[i]; process_dev takes device pointers."""
+    _prefix = "sdrhip_channelizer"
+    _calls = "out_count process process_dev set_channels set_taps reset get_state plan_info kernel_names"
+    _out_dtype = np.float32
+
+    def __init__(self, ctx, dtype, M, D, taps, channels=None, max_in=65536):
+        abi_channelizer.lib()
+        super().__init__()
+        self.dtype = _scalar_dtype(dtype, CHAN_CS16, CHAN_CF32)
+        self._in = (np.int16 if self.dtype == CHAN_CS16 else np.float32, 2)
+        taps = np.ascontiguousarray(taps, np.float64).ravel()
+        self.ctx, self.M, self.D, self.n_taps, self.max_in = ctx, int(M), int(D), int(taps.size), int(max_in)
+        self.selected, self.channels = list(range(self.M)), self.M
+        check(abi_channelizer.lib().sdrhip_channelizer_create(ctx.handle, self.dtype, self.M, self.D, _p(taps, True), self.n_taps, self.max_in,
+                                                              C.byref(self._h)))
+        if channels is not None:
+            self.set_channels(channels)
+
+    # process(x) — x: ONE row [n, 2]; the router sees it as x[None]; the node's calls take no input stride
+    def _rows(self, x):
+        x = np.ascontiguousarray(x, self._in[0])
+        assert x.ndim == 2 and x.shape[1] == 2, x.shape
+        return x[None]
+
+    def _host_in(self, x, n_in):
+        return _p(x[0]), n_in
+
+    def _dev_checked(self, i, n_in, si, o, so, no):
+        assert self.process_dev(i, n_in, o, so) == no
+
+    def process_dev(self, in_ptr, n, out_ptr, out_stride):
+        """Device pointers, out_stride in complex elements; one launch, nothing is synchronised -> the outputs per row."""
+        return _out(C.c_size_t, self._c_process_dev, self._h, C.c_void_p(in_ptr), n, C.c_void_p(out_ptr), out_stride)
+
+    def set_channels(self, channels):
+        """Row i of the later calls holds channels[i] (None: all M in order); the stream itself goes on."""
+        if channels is None:
+            check(self._c_set_channels(self._h, None, 0))
+            self.selected = list(range(self.M))
+        else:
+            idx = np.ascontiguousarray(channels, np.intc).ravel()
+            check(self._c_set_channels(self._h, _p(idx, True), int(idx.size)))
+            self.selected = [int(k) for k in idx]
+        self.channels = len(self.selected)
+
+    def set_taps(self, taps):
+        """A new prototype of the same length; the count and the tail are kept."""
+        taps = np.ascontiguousarray(taps, np.float64).ravel()
+        assert taps.size == self.n_taps, (taps.size, self.n_taps)
+        check(self._c_set_taps(self._h, _p(taps, True)))
+
+    def get_state(self):
+        """-> {consumed: samples taken since create or reset, tail: the last n_taps - 1 samples [n_taps - 1, 2] float32, oldest
+        first} behind the calls enqueued so far"""
+        consumed, tail = C.c_uint64(0), np.zeros((self.n_taps - 1, 2), np.float32)
+        check(self._c_get_state(self._h, C.byref(consumed), _p(tail, True), self.n_taps - 1))
+        return {"consumed": consumed.value, "tail": tail}
+
+    def plan_info(self):
+        """{tile_times, branch_taps, lds_bytes, rows} of a launch (sdrhip_channelizer_plan_info)"""
+        v = [C.c_int(0) for _ in range(4)]
+        check(self._c_plan_info(self._h, *[C.byref(c) for c in v]))
+        return dict(zip(("tile_times", "branch_taps", "lds_bytes", "rows"), [c.value for c in v]))
+
+    @property
+    def kernel_names(self):
+        return _text(self._c_kernel_names, self._h, size=256).split(",")
