@@ -16,5 +16,7 @@ from .resample import InpolSubSampler, InpolSubSamplerBank  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from . import baudot  # noqa: F401
 from .baudot import Baudot, BaudotBank  # noqa: F401
+from . import ax25  # noqa: F401
+from .ax25 import AX25, AX25Bank  # noqa: F401   (ax25.Address and ax25.Message stay in their module: Message is POCSAG's here)
 
 __version__ = "0.1.0"
