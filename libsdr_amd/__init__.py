@@ -14,6 +14,7 @@ from .agc import AGC, AGCBank, design_agc_lambda, design_agc_target  # noqa: F40
 from .psk31 import BPSK31, BPSK31Bank, Varicode, design_inpol_taps  # noqa: F401
 from .resample import InpolSubSampler, InpolSubSamplerBank  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
+from .chanaudio import AudioChannelizer  # noqa: F401
 from . import baudot  # noqa: F401
 from .baudot import Baudot, BaudotBank  # noqa: F401
 from . import ax25  # noqa: F401

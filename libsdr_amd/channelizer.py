@@ -21,17 +21,19 @@ class Channelizer(_Counted):
     _prefix = "sdrhip_channelizer"
     _calls = "out_count process process_dev set_channels set_taps reset get_state plan_info kernel_names"
     _out_dtype = np.float32
+    _abi = abi_channelizer   # the side header's binding module (libsdr_amd.chanaudio has another)
 
-    def __init__(self, ctx, dtype, M, D, taps, channels=None, max_in=65536):
-        abi_channelizer.lib()
+    def __init__(self, ctx, dtype, M, D, taps, channels=None, max_in=65536, _more=()):
+        """_more: what a subclass's create takes between max_in and the handle"""
+        self._abi.lib()
         super().__init__()
         self.dtype = _scalar_dtype(dtype, CHAN_CS16, CHAN_CF32)
         self._in = (np.int16 if self.dtype == CHAN_CS16 else np.float32, 2)
         taps = np.ascontiguousarray(taps, np.float64).ravel()
         self.ctx, self.M, self.D, self.n_taps, self.max_in = ctx, int(M), int(D), int(taps.size), int(max_in)
         self.selected, self.channels = list(range(self.M)), self.M
-        check(abi_channelizer.lib().sdrhip_channelizer_create(ctx.handle, self.dtype, self.M, self.D, _p(taps, True), self.n_taps, self.max_in,
-                                                              C.byref(self._h)))
+        check(getattr(self._abi.lib(), self._prefix + "_create")(ctx.handle, self.dtype, self.M, self.D, _p(taps, True), self.n_taps, self.max_in,
+                                                                 *_more, C.byref(self._h)))
         if channels is not None:
             self.set_channels(channels)
 

@@ -1,0 +1,300 @@
+// chanaudio.hip — the audio channelizer (sdrhip_chanaudio.h): the polyphase channelizer with a demodulator per channel in the
+// same launch, int16 audio rows out. Phases 1 and 2 are channelizer_body.hpp's, shared with channelizer.hip, so the spectra have
+// the plain channelizer's bits; this file's epilogue is
+//   3  all lanes: element (row i, time tt) — the spectrum's bin sel[i] of image halo + tt, times the channel's gain, rounded and
+//      clamped to complex<int16>, through the channel's demodulator (fm_phi.hpp), stored as row i's int16 at j0 + tt: Tc
+//      contiguous outputs per row. An FM output at call index j >= 2 differences against the angle of the image before it —
+//      the tile's own, or the halo image a tile behind the call's first computes for time j0 - 1 when a selected row is FM;
+//      j = 1 differences against the channel's `last`, j = 0 is q.re.
+// `last` is per channel and double-buffered like the tail: the workgroup holding output n_out - 1 (n_out >= 2) writes every FM
+// channel's angle there — selected or not, its image has all M bins — and block 0 copies every other entry.
+#include "sdrhip_internal.hpp"
+#include "sdrhip_chanaudio.h"
+#include "entry.hpp"
+#include "channelizer_body.hpp"
+#include "fm_phi.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace sdrhip;
+
+namespace {
+
+struct ChAudioArgs {
+  ChArgs c;
+  const int *mode;      // [M] SDRHIP_EPI_FM | _AM | _USB
+  const float *gain;    // [M]
+  const int *last;      // [M] the angles before the call
+  int *last_new;        // [M] behind it
+  int fm_rows;          // selected rows that are FM
+};
+
+// one float32 multiply, round to nearest even, NaN -> 0, clamp
+__device__ __forceinline__ int ca_conv(float g, float v) {
+  const float p = g * v;
+  const float r = p != p ? 0.f : __builtin_rintf(p);
+  return (int)__builtin_fminf(__builtin_fmaxf(r, -32768.f), 32767.f);
+}
+__device__ __forceinline__ int ca_phi(float g, float2 y) { return fm_phi(ca_conv(g, y.x), ca_conv(g, y.y)); }
+
+struct ChStoreAudio {
+  const ChAudioArgs &x;
+  __device__ __forceinline__ int halo(const ChArgs &, int j0) const { return j0 >= 1 && x.fm_rows > 0 ? 1 : 0; }
+  __device__ __forceinline__ void store(const ChArgs &a, const float2 *img, int j0, int Tc, int halo, int tid) const {
+    short *out = static_cast<short *>(a.out);
+    for (int e = tid; e < a.n_sel * Tc; e += CH_THREADS) {
+      const int i = e / Tc, tt = e - i * Tc, j = j0 + tt, k = a.sel[i], mode = x.mode[k];
+      const float g = x.gain[k];
+      const float2 *y = img + (halo + tt) * a.ld + k;
+      const int re = ca_conv(g, y->x), im = ca_conv(g, y->y);
+      short o;
+      if (mode == SDRHIP_EPI_AM) o = am_i16(re, im);
+      else if (mode == SDRHIP_EPI_USB) o = usb_i16(re, im);
+      else if (j == 0) o = (short)re;
+      else {
+        // (halo + tt >= 1 wherever j >= 2: tt >= 1, or the tile has its halo image because this row is FM — the test keeps a
+        // wrong count from becoming a read before the images)
+        const int prev = j == 1 || halo + tt == 0 ? x.last[k] : ca_phi(g, y[-a.ld]);
+        o = (short)(prev - fm_phi(re, im));
+      }
+      out[(long)i * a.out_stride + j] = o;
+    }
+    // the angles behind the call: the last output's, of every FM channel
+    if (a.n_out >= 2 && j0 + Tc == a.n_out) {
+      const float2 *y = img + (halo + Tc - 1) * a.ld;
+      for (int k = tid; k < a.M; k += CH_THREADS)
+        if (x.mode[k] == SDRHIP_EPI_FM) x.last_new[k] = ca_phi(x.gain[k], y[k]);
+    }
+  }
+  template <class I>
+  __device__ __forceinline__ void roll(const ChArgs &a, int tid) const {
+    ch_roll_tail<I>(a, tid);
+    if (blockIdx.x == 0)
+      for (int k = tid; k < a.M; k += CH_THREADS)
+        if (!(a.n_out >= 2 && x.mode[k] == SDRHIP_EPI_FM)) x.last_new[k] = x.last[k];
+  }
+};
+
+__global__ __launch_bounds__(CH_THREADS) void chanaudio_cs16_kernel(const ChAudioArgs a) { ch_body<short2>(a.c, ChStoreAudio{a}); }
+__global__ __launch_bounds__(CH_THREADS) void chanaudio_cf32_kernel(const ChAudioArgs a) { ch_body<float2>(a.c, ChStoreAudio{a}); }
+
+// SDRHIP_EPI_NONE has a code of its own: its rows would have another element size
+void require_mode(int mode, const char *what, int index) {
+  SDRHIP_REQUIRE(mode != SDRHIP_EPI_NONE, SDRHIP_E_UNSUPPORTED, "mode of %s %d is SDRHIP_EPI_NONE: the node makes audio rows, not complex<int16> ones",
+                 what, index);
+  SDRHIP_REQUIRE(mode == SDRHIP_EPI_FM || mode == SDRHIP_EPI_AM || mode == SDRHIP_EPI_USB, SDRHIP_E_INVALID,
+                 "mode %d of %s %d is none of SDRHIP_EPI_FM, _AM, _USB", mode, what, index);
+}
+void require_gain(float gain, const char *what, int index) {
+  SDRHIP_REQUIRE(std::isfinite(gain), SDRHIP_E_INVALID, "gain of %s %d is not finite", what, index);
+}
+
+}  // namespace
+
+struct sdrhip_chanaudio : ChPlan {
+  std::vector<int> mode_host;      // [M]
+  std::vector<float> gain_host;    // [M]
+  DevBuf<int> mode, last[2];       // [M] each; last[cur] holds the state (the buffers flip with the tail's)
+  DevBuf<float> gain;              // [M]
+  size_t lds_bytes() const { return (size_t)(T + 1) * (size_t)ld * sizeof(float2); }
+  int fm_rows() const {
+    int n = 0;
+    for (int k : sel_host) n += mode_host[(size_t)k] == SDRHIP_EPI_FM;
+    return n;
+  }
+  void fresh_state() {
+    SDRHIP_CHECK_HIP(hipMemsetAsync(last[0].p, 0, (size_t)M * sizeof(int), ctx->stream));
+    fresh_tail();   // (synchronises, and cur = 0)
+  }
+  void require_row(int row) const { SDRHIP_REQUIRE(row >= 0 && row < n_sel, SDRHIP_E_INVALID, "row %d outside [0,%d)", row, n_sel); }
+  // n >= 1
+  void launch(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) {
+    ctx->use();
+    ChAudioArgs a;
+    a.c = args(in_dev, n, out_dev, out_stride, n_out);
+    a.mode = mode.p; a.gain = gain.p; a.last = last[cur].p; a.last_new = last[cur ^ 1].p;
+    a.fm_rows = fm_rows();
+    const dim3 grid((unsigned)std::max(a.c.tiles, 1)), block(CH_THREADS);
+    const size_t lds = lds_bytes();
+    (void)hipGetLastError();
+    if (dtype == SDRHIP_CHAN_CS16) hipLaunchKernelGGL(chanaudio_cs16_kernel, grid, block, lds, ctx->stream, a);
+    else hipLaunchKernelGGL(chanaudio_cf32_kernel, grid, block, lds, ctx->stream, a);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    advance(n);
+  }
+};
+
+extern "C" {
+
+int sdrhip_chanaudio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes,
+                            const float *gains, sdrhip_chanaudio **out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
+    std::vector<float> h32;
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32);
+    for (int k = 0; modes && k < M; k++) require_mode(modes[k], "channel", k);
+    for (int k = 0; gains && k < M; k++) require_gain(gains[k], "channel", k);
+    require_device_for_null_ctx(ctx);
+    make_handle(ctx, out, true, [&](sdrhip_chanaudio *h) {
+      h->build(ctx, dtype, M, D, h32, max_in);
+      h->mode_host.assign((size_t)M, SDRHIP_EPI_FM);
+      h->gain_host.assign((size_t)M, 1.0f);
+      if (modes) h->mode_host.assign(modes, modes + M);
+      if (gains) h->gain_host.assign(gains, gains + M);
+      h->mode.alloc((size_t)M);
+      h->mode.upload(h->mode_host.data(), (size_t)M, ctx->stream);
+      h->gain.alloc((size_t)M);
+      h->gain.upload(h->gain_host.data(), (size_t)M, ctx->stream);
+      for (auto &b : h->last) { b.alloc((size_t)M); b.zero(ctx->stream); }
+      allow_lds_max(dtype == SDRHIP_CHAN_CS16 ? chanaudio_cs16_kernel : chanaudio_cf32_kernel, h->lds_bytes());
+      h->fresh_state();
+    });
+  });
+}
+
+int sdrhip_chanaudio_out_count(sdrhip_chanaudio *h, size_t n, size_t *n_out) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
+    *n_out = h->out_count(n);
+  });
+}
+
+int sdrhip_chanaudio_process_dev(sdrhip_chanaudio *h, const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_chanaudio_process_dev");
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_dev, out_dev)) return;
+    const size_t no = h->out_count(n);
+    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
+    require_disjoint(in_dev, n, n, h->in_elem(), out_dev, s.out, no, sizeof(short), 1, (size_t)h->n_sel);
+    h->launch(in_dev, n, out_dev, s.out, no);
+    if (n_out) *n_out = no;
+  });
+}
+
+int sdrhip_chanaudio_process(sdrhip_chanaudio *h, const void *in_host, size_t n, void *out_host, size_t out_stride, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_chanaudio_process");
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_host, out_host)) return;
+    const size_t no = h->out_count(n), rows = (size_t)h->n_sel, eb = h->in_elem(), ob = sizeof(short);
+    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
+    // (the staged rows follow the selection: a set_channels can raise them)
+    const size_t out_cap_b = rows * h->out_count_max(h->max_in) * ob;
+    if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
+    run_staged(h->ctx, h->stage, h->max_in * eb, out_cap_b, {in_host, n * eb, n * eb, 1}, {out_host, s.out * ob, no * ob, rows},
+               [&](void *in, void *out) {
+                 h->launch(in, n, out, no, no);
+                 return no * ob;
+               });
+    if (n_out) *n_out = no;
+  });
+}
+
+int sdrhip_chanaudio_set_channels(sdrhip_chanaudio *h, const int *idx, int n_sel) {
+  return guarded([&] {
+    use_handle(h);
+    h->select(idx, n_sel);
+  });
+}
+
+int sdrhip_chanaudio_set_mode(sdrhip_chanaudio *h, int row, int mode) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    h->require_row(row);
+    require_mode(mode, "row", row);
+    h->ctx->use();
+    hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued
+    const int k = h->sel_host[(size_t)row];
+    h->mode_host[(size_t)k] = mode;
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->mode.p + k, &h->mode_host[(size_t)k], sizeof(int), hipMemcpyHostToDevice, st));
+    SDRHIP_CHECK_HIP(hipMemsetAsync(h->last[h->cur].p + k, 0, sizeof(int), st));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int sdrhip_chanaudio_get_modes(sdrhip_chanaudio *h, int *modes, int n) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && modes, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(n >= h->n_sel, SDRHIP_E_INVALID, "modes holds %d entries, the node writes %d rows", n, h->n_sel);
+    for (int i = 0; i < h->n_sel; i++) modes[i] = h->mode_host[(size_t)h->sel_host[(size_t)i]];
+  });
+}
+
+int sdrhip_chanaudio_set_gain(sdrhip_chanaudio *h, int row, float gain) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    h->require_row(row);
+    require_gain(gain, "row", row);
+    h->ctx->use();
+    const int k = h->sel_host[(size_t)row];
+    put_sync(h->ctx, h->gain.p + k, &gain, sizeof(float));
+    h->gain_host[(size_t)k] = gain;
+  });
+}
+
+int sdrhip_chanaudio_get_gains(sdrhip_chanaudio *h, float *gains, int n) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && gains, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(n >= h->n_sel, SDRHIP_E_INVALID, "gains holds %d entries, the node writes %d rows", n, h->n_sel);
+    for (int i = 0; i < h->n_sel; i++) gains[i] = h->gain_host[(size_t)h->sel_host[(size_t)i]];
+  });
+}
+
+int sdrhip_chanaudio_set_taps(sdrhip_chanaudio *h, const double *taps) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
+    h->ctx->use();
+    h->set_taps(taps);
+  });
+}
+
+int sdrhip_chanaudio_reset(sdrhip_chanaudio *h) {
+  return guarded([&] {
+    use_handle(h);
+    h->fresh_state();
+  });
+}
+
+int sdrhip_chanaudio_get_state(sdrhip_chanaudio *h, uint64_t *consumed, float *tail, size_t tail_len, int *last, size_t n_last) {
+  return guarded([&] {
+    use_handle(h);
+    SDRHIP_REQUIRE(!last || n_last >= (size_t)h->n_sel, SDRHIP_E_SIZE, "n_last %zu < rows = %d", n_last, h->n_sel);
+    h->get_tail(consumed, tail, tail_len);
+    if (last) {
+      std::vector<int> all((size_t)h->M);
+      get_sync(h->ctx, all.data(), h->last[h->cur].p, all.size() * sizeof(int));
+      for (int i = 0; i < h->n_sel; i++) last[i] = all[(size_t)h->sel_host[(size_t)i]];
+    }
+  });
+}
+
+int sdrhip_chanaudio_plan_info(sdrhip_chanaudio *h, int *tile_times, int *branch_taps, int *lds_bytes, int *rows, int *fm_rows,
+                               int *halo_tiles) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    if (tile_times) *tile_times = h->T;
+    if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
+    if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+    if (rows) *rows = h->n_sel;
+    if (fm_rows) *fm_rows = h->fm_rows();
+    if (halo_tiles) {
+      const size_t tiles = ceil_div(h->out_count(h->max_in), (size_t)h->T);
+      *halo_tiles = h->fm_rows() > 0 && tiles > 0 ? (int)(tiles - 1) : 0;
+    }
+  });
+}
+
+int sdrhip_chanaudio_kernel_names(sdrhip_chanaudio *h, char *buf, size_t len) {
+  return guarded([&] {
+    write_names(h, buf, len, [&] { return h->dtype == SDRHIP_CHAN_CS16 ? "chanaudio_cs16_kernel" : "chanaudio_cf32_kernel"; });
+  });
+}
+
+int sdrhip_chanaudio_destroy(sdrhip_chanaudio *h) {
+  return guarded([&] { destroy_handle(h); });
+}
+
+}  // extern "C"

@@ -1,0 +1,243 @@
+// channelizer_body.hpp — the polyphase channelizer's kernel body, shared by channelizer.hip (complex float rows out) and
+// chanaudio.hip (demodulated int16 rows out). One form serves every M: a workgroup of CH_THREADS lanes takes a tile of T
+// consecutive output times (and, where the epilogue asks for it, `halo` output times before them),
+//   1  all lanes: element (tt, r) of the tile, r fastest — the branch sum u[r] = sum_p h[p M + r] x[t - p M - r] as a float fma
+//      chain over global reads (taps and input are contiguous in r; the row is re-read P times per output time, from L1 / L2) —
+//      written into image tt at the digit-reversed position of (r - t) mod M: the circular shift by the absolute time costs
+//      an index, and inverse_dit's input order another;
+//   2  all lanes: the backward decimation-in-time passes of fftgen.hpp over the images at once — its butterflies (dft_small,
+//      gmulc) and its plan's roots, a pass's lane loop running over (image, butterfly) so that a workgroup is busy on an 8-point
+//      transform as well;
+//   3  the epilogue policy: what becomes of the spectra in LDS (image tt is at img + tt * ld, natural order), and what of the
+//      handle's state is rolled. A policy E has
+//        int  halo(const ChArgs &, int j0)                           images wanted before output time j0 (0 or 1, uniform)
+//        void store(const ChArgs &, const float2 *img, int j0, int Tc, int halo, int tid)   the tile's outputs; image halo + tt
+//                                                                    holds output time j0 + tt
+//        void roll<I>(const ChArgs &, int tid)                       every block, behind the tile (ch_roll_tail at least)
+// An output time is computed with the same operations in the same order whichever policy asks and wherever it lies in a tile
+// (the library is built with -ffp-contract=off, and the one fused operation is written as such), so the two kernel families
+// agree bit for bit on the spectra.
+// The input is read at [0, n) and the tail at [0, n_taps - 1) only: the first output time of a call is not before its first
+// sample, the last not behind its last, and terms at l >= n_taps are skipped.
+#pragma once
+#include "sdrhip_internal.hpp"
+#include "sdrhip_channelizer.h"
+#include "entry.hpp"
+#include "fftgen.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace sdrhip {
+
+constexpr int CH_THREADS = fftgen::GT, CH_TMAX = 256;
+constexpr int CH_M_MIN = 2, CH_M_MAX = 4096, CH_BRANCH_MAX = 64;
+constexpr int CH_ELEMS_SMALL = 4096, CH_ELEMS_LARGE = 8192, CH_M_SMALL = 512;   // complex elements of LDS a workgroup's T images take
+
+struct ChArgs {
+  fftgen::GenDev<float2> fft;
+  const void *in;          // [n] of the input type
+  const float2 *hist;      // [HH] the tail before the call, oldest first
+  float2 *hist_new;        // [HH] the tail behind it
+  const float *taps;       // [n_taps]
+  const int *invperm;      // [M] natural index -> position in inverse_dit's input
+  const int *sel;          // [n_sel]
+  void *out;               // rows of the policy's element type
+  long out_stride;
+  int n, HH, M, D, n_taps, T, ld, n_out, n_sel, tiles;
+  int lead;                // the call-relative index of the first output's last sample, 0 <= lead < D
+  int tmod0;               // that sample's absolute time mod M
+};
+
+__device__ __forceinline__ float2 ch_sample(const short2 *p, int i) { const short2 v = p[i]; return make_float2((float)v.x, (float)v.y); }
+__device__ __forceinline__ float2 ch_sample(const float2 *p, int i) { return p[i]; }
+
+// one backward DIT pass of radix R over nimg images ld apart: pass_dit's arithmetic, the lane loop over (image, butterfly)
+template <int R>
+__device__ __forceinline__ void ch_pass(float2 *x, const fftgen::GenDev<float2> &p, int s, int nimg, int ld, int tid) {
+  const int n = s * R, tw = p.L / n, per = p.L / R, total = nimg * per;
+  for (int i = tid; i < total; i += CH_THREADS) {
+    const int im = i / per, b = i - im * per;
+    const int blk = b / s, j = b - blk * s, base = im * ld + blk * n + j;
+    float2 v[R];
+    v[0] = x[base];
+#pragma unroll
+    for (int k = 1; k < R; k++) v[k] = s > 1 ? fftgen::gmulc(x[base + k * s], p.W[j * tw * k]) : x[base + k * s];
+    fftgen::dft_small<float2, R, 1>(v, p);
+#pragma unroll
+    for (int m = 0; m < R; m++) x[base + m * s] = v[m];
+  }
+}
+
+// the tail behind the call: the last HH samples of (tail, in[0 ... n)), every block its share — the blocks of a launch read
+// the old buffer
+template <class I>
+__device__ __forceinline__ void ch_roll_tail(const ChArgs &a, int tid) {
+  const I *in = static_cast<const I *>(a.in);
+  for (int k = (int)blockIdx.x * CH_THREADS + tid; k < a.HH; k += (int)gridDim.x * CH_THREADS) {
+    const int q = a.n + k;   // n < 2^30, HH < 2^18
+    a.hist_new[k] = q < a.HH ? a.hist[q] : ch_sample(in, q - a.HH);
+  }
+}
+
+template <class I, class E>
+__device__ __forceinline__ void ch_body(const ChArgs &a, const E &epi) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float2 *img = reinterpret_cast<float2 *>(smem_raw);
+  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+  const int tid = (int)threadIdx.x, tile = (int)blockIdx.x, M = a.M;
+  const I *in = static_cast<const I *>(a.in);
+
+  if (tile < a.tiles) {
+    const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
+    for (int tt = tid; tt < Ti; tt += CH_THREADS) {
+      const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
+      tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
+      rel_s[tt] = a.lead + (int)jd;
+    }
+    __syncthreads();
+    // phase 1
+    for (int e = tid; e < Ti * M; e += CH_THREADS) {
+      const int tt = e / M, r = e - tt * M;
+      int rel = rel_s[tt] - r;
+      float re = 0.f, im = 0.f;
+#pragma unroll 4
+      for (int l = r; l < a.n_taps; l += M, rel -= M) {
+        // (the clamps never bind — see the head of the file; they keep a wrong count from becoming a wild read)
+        const float2 v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : a.hist[max(a.HH + rel, 0)];
+        const float hv = a.taps[l];
+        re = __builtin_fmaf(hv, v.x, re);
+        im = __builtin_fmaf(hv, v.y, im);
+      }
+      int jw = r - tmod_s[tt];
+      jw += jw < 0 ? M : 0;
+      img[tt * a.ld + a.invperm[jw]] = make_float2(re, im);
+    }
+    __syncthreads();
+    // phase 2
+    int s = 1;
+    for (int pass = a.fft.npass - 1; pass >= 0; pass--) {
+      const int r = a.fft.radix[pass];
+#define SDRHIP_CH_CALL(R_) ch_pass<R_>(img, a.fft, s, Ti, a.ld, tid)
+      SDRHIP_GEN_RADIX_SWITCH(r, SDRHIP_CH_CALL)
+#undef SDRHIP_CH_CALL
+      __syncthreads();
+      s *= r;
+    }
+    // phase 3
+    epi.store(a, img, j0, Tc, halo, tid);
+  }
+  epi.template roll<I>(a, tid);
+}
+
+// ---- host side: what both handle types hold and do ---------------------------------------------------------------------------
+// the argument rules of create, in the header's order (before the context: host rules); h32: the taps rounded once to float32
+static inline void ch_require_args(int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, std::vector<float> &h32) {
+  SDRHIP_REQUIRE(dtype == SDRHIP_CHAN_CS16 || dtype == SDRHIP_CHAN_CF32, SDRHIP_E_INVALID, "bad dtype %d", dtype);
+  SDRHIP_REQUIRE(M >= CH_M_MIN && M <= CH_M_MAX, SDRHIP_E_SIZE, "M %d outside [%d,%d] (one transform lives in one workgroup's LDS)", M,
+                 CH_M_MIN, CH_M_MAX);
+  std::vector<int> radix;
+  int bad = 1;
+  SDRHIP_REQUIRE(fftgen::GenPlan<float2>::factor(M, radix, &bad), SDRHIP_E_INVALID,
+                 "M %d has the prime factor %d: the device transforms sizes made of 2, 3, 5, 7, 11 and 13", M, bad);
+  SDRHIP_REQUIRE(D >= 1 && D <= M, SDRHIP_E_INVALID, "D %d outside [1,M = %d]", D, M);
+  SDRHIP_REQUIRE(n_taps >= 1 && n_taps <= CH_BRANCH_MAX * M, SDRHIP_E_SIZE, "n_taps %d outside [1,%d M = %d]", n_taps, CH_BRANCH_MAX,
+                 CH_BRANCH_MAX * M);
+  require_max_in(max_in);
+  h32.resize((size_t)n_taps);
+  for (int i = 0; i < n_taps; i++) {
+    h32[(size_t)i] = (float)taps[i];
+    SDRHIP_REQUIRE(std::isfinite(h32[(size_t)i]), SDRHIP_E_INVALID, "tap %d is not finite as a float", i);
+  }
+}
+
+struct ChPlan {
+  sdrhip_ctx *ctx = nullptr;
+  int dtype = SDRHIP_CHAN_CS16, M = 2, D = 1, n_taps = 1, T = 1, ld = 3, n_sel = 2;
+  size_t max_in = 0;
+  uint64_t consumed = 0;
+  int cur = 0;                     // which tail buffer holds the state
+  fftgen::GenPlan<float2> plan;
+  DevBuf<float> taps;
+  DevBuf<int> invperm, sel;
+  std::vector<int> sel_host;       // [n_sel]
+  DevBuf<float2> hist[2];          // [n_taps - 1] each (at least one element)
+  Staging stage;
+  size_t in_elem() const { return dtype == SDRHIP_CHAN_CS16 ? 4 : 8; }
+  int HH() const { return n_taps - 1; }
+  size_t out_count(size_t n) const { return (size_t)((consumed + n) / (uint64_t)D - consumed / (uint64_t)D); }
+  size_t out_count_max(size_t n) const { return ceil_div(n, (size_t)D); }   // whatever N is
+
+  // inside make_handle, behind ch_require_args; the caller ends with allow_lds_max and its fresh state
+  void build(sdrhip_ctx *c, int dtype_, int M_, int D_, const std::vector<float> &h32, size_t max_in_) {
+    dtype = dtype_; M = M_; D = D_; n_taps = (int)h32.size(); max_in = max_in_;
+    T = std::min(CH_TMAX, (M <= CH_M_SMALL ? CH_ELEMS_SMALL : CH_ELEMS_LARGE) / M);
+    ld = M + 1;
+    plan.build(c, M, CH_M_MAX);
+    std::vector<int> inv((size_t)M);
+    for (int pos = 0; pos < M; pos++) inv[(size_t)plan.perm[pos]] = pos;
+    invperm.alloc((size_t)M);
+    invperm.upload(inv.data(), inv.size(), c->stream);
+    taps.alloc((size_t)n_taps);
+    taps.upload(h32.data(), h32.size(), c->stream);
+    sel.alloc((size_t)M);
+    select(nullptr, 0);
+    for (auto &b : hist) { b.alloc((size_t)std::max(HH(), 1)); b.zero(c->stream); }
+  }
+  // set_channels: idx = NULL selects all M in order; a bad selection changes nothing
+  void select(const int *idx, int n) {
+    std::vector<int> s;
+    if (!idx) {
+      s.resize((size_t)M);
+      for (int k = 0; k < M; k++) s[(size_t)k] = k;
+    } else {
+      SDRHIP_REQUIRE(n >= 1 && n <= M, SDRHIP_E_INVALID, "n_sel %d outside [1,M = %d]", n, M);
+      std::vector<char> seen((size_t)M, 0);
+      for (int i = 0; i < n; i++) {
+        SDRHIP_REQUIRE(idx[i] >= 0 && idx[i] < M, SDRHIP_E_INVALID, "channel %d (row %d) outside [0,%d)", idx[i], i, M);
+        SDRHIP_REQUIRE(!seen[(size_t)idx[i]], SDRHIP_E_INVALID, "channel %d is selected twice (row %d)", idx[i], i);
+        seen[(size_t)idx[i]] = 1;
+      }
+      s.assign(idx, idx + n);
+    }
+    put_sync(ctx, sel.p, s.data(), s.size() * sizeof(int));
+    sel_host.swap(s);
+    n_sel = (int)sel_host.size();
+  }
+  void set_taps(const double *t) {
+    std::vector<float> h32((size_t)n_taps);
+    for (int i = 0; i < n_taps; i++) {
+      h32[(size_t)i] = (float)t[i];
+      SDRHIP_REQUIRE(std::isfinite(h32[(size_t)i]), SDRHIP_E_INVALID, "tap %d is not finite as a float", i);
+    }
+    put_sync(ctx, taps.p, h32.data(), h32.size() * sizeof(float));
+  }
+  void fresh_tail() {
+    SDRHIP_CHECK_HIP(hipMemsetAsync(hist[0].p, 0, hist[0].n * sizeof(float2), ctx->stream));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    cur = 0; consumed = 0;
+  }
+  void get_tail(uint64_t *consumed_out, float *tail, size_t tail_len) {
+    SDRHIP_REQUIRE(!tail || tail_len >= (size_t)HH(), SDRHIP_E_SIZE, "tail_len %zu < n_taps - 1 = %d", tail_len, HH());
+    if (tail && HH() > 0) get_sync(ctx, tail, hist[cur].p, (size_t)HH() * sizeof(float2));
+    if (consumed_out) *consumed_out = consumed;
+  }
+  // the arguments of a launch of n >= 1 samples from the current state; the grid is max(tiles, 1) blocks of CH_THREADS
+  ChArgs args(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) const {
+    ChArgs a;
+    a.fft = plan.dev;
+    a.in = in_dev; a.hist = hist[cur].p; a.hist_new = hist[cur ^ 1].p;
+    a.taps = taps.p; a.invperm = invperm.p; a.sel = sel.p;
+    a.out = out_dev; a.out_stride = (long)out_stride;
+    a.n = (int)n; a.HH = HH(); a.M = M; a.D = D; a.n_taps = n_taps; a.T = T; a.ld = ld; a.n_out = (int)n_out; a.n_sel = n_sel;
+    a.tiles = (int)ceil_div(n_out, (size_t)T);
+    a.lead = (int)((uint64_t)D - 1 - consumed % (uint64_t)D);
+    a.tmod0 = (int)((consumed + (uint64_t)a.lead) % (uint64_t)M);
+    return a;
+  }
+  // the state moves on only behind a launch that was accepted
+  void advance(size_t n) { consumed += n; cur ^= 1; }
+};
+
+}  // namespace sdrhip
