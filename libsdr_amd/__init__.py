@@ -15,6 +15,7 @@ from .psk31 import BPSK31, BPSK31Bank, Varicode, design_inpol_taps  # noqa: F401
 from .resample import InpolSubSampler, InpolSubSamplerBank  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from .chanaudio import AudioChannelizer  # noqa: F401
+from .chanpower import ChannelPower  # noqa: F401
 from . import baudot  # noqa: F401
 from .baudot import Baudot, BaudotBank  # noqa: F401
 from . import ax25  # noqa: F401

@@ -2,8 +2,6 @@
 channelizer with a demodulator (FM, AM or USB) and a gain per channel in the same launch; int16 audio rows out, one per selected
 channel, as the symbol path (FMDeemphBankI16 -> SymbolDetectorBank -> BitStreamBank -> the frame decoders) takes them through
 process_dev."""
-import ctypes as C
-
 import numpy as np
 
 from . import abi_chanaudio
@@ -52,12 +50,10 @@ class AudioChannelizer(Channelizer):
 
     def get_state(self):
         """-> {consumed, tail (as Channelizer.get_state), last: every row's FM angle [rows] int32} behind the calls enqueued so far"""
-        consumed, tail, last = C.c_uint64(0), np.zeros((self.n_taps - 1, 2), np.float32), np.zeros(self.channels, np.intc)
-        check(self._c_get_state(self._h, C.byref(consumed), _p(tail, True), self.n_taps - 1, _p(last, True), last.size))
-        return {"consumed": consumed.value, "tail": tail, "last": last}
+        last = np.zeros(self.channels, np.intc)
+        consumed, tail = self._tail_state(_p(last, True), last.size)
+        return {"consumed": consumed, "tail": tail, "last": last}
 
     def plan_info(self):
         """{tile_times, branch_taps, lds_bytes, rows, fm_rows, halo_tiles} of a launch (sdrhip_chanaudio_plan_info)"""
-        v = [C.c_int(0) for _ in range(6)]
-        check(self._c_plan_info(self._h, *[C.byref(c) for c in v]))
-        return dict(zip(("tile_times", "branch_taps", "lds_bytes", "rows", "fm_rows", "halo_tiles"), [c.value for c in v]))
+        return self._plan_info("tile_times", "branch_taps", "lds_bytes", "rows", "fm_rows", "halo_tiles")

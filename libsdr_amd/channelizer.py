@@ -13,7 +13,59 @@ from .nodes import _Counted, _out, _p, _scalar_dtype, _text
 __all__ = ["Channelizer", "CHAN_CS16", "CHAN_CF32"]
 
 
-class Channelizer(_Counted):
+class _Grid(_Counted):
+    """What the nodes on the channelizer's grid share (Channelizer, AudioChannelizer, libsdr_amd.chanpower.ChannelPower): the
+    create call's head (ctx, dtype, M, D, taps, n_taps, max_in, then the node's own arguments, then the handle), ONE input row
+    [n, 2] of the scalar type, set_taps and kernel_names. A class names `_prefix`, `_calls` and `_abi`, its side header's binding
+    module."""
+
+    def __init__(self, ctx, dtype, M, D, taps, max_in, _more=()):
+        """_more: what the node's create takes between max_in and the handle"""
+        self._abi.lib()
+        super().__init__()
+        self.dtype = _scalar_dtype(dtype, CHAN_CS16, CHAN_CF32)
+        self._in = (np.int16 if self.dtype == CHAN_CS16 else np.float32, 2)
+        taps = np.ascontiguousarray(taps, np.float64).ravel()
+        self.ctx, self.M, self.D, self.n_taps, self.max_in = ctx, int(M), int(D), int(taps.size), int(max_in)
+        self._created()
+        check(getattr(self._abi.lib(), self._prefix + "_create")(ctx.handle, self.dtype, self.M, self.D, _p(taps, True), self.n_taps, self.max_in,
+                                                                 *_more, C.byref(self._h)))
+
+    def _created(self):
+        """attributes a class sets before its create call"""
+
+    # process(x) — x: ONE row [n, 2]; the router sees it as x[None]; the node's calls take no input stride
+    def _rows(self, x):
+        x = np.ascontiguousarray(x, self._in[0])
+        assert x.ndim == 2 and x.shape[1] == 2, x.shape
+        return x[None]
+
+    def _host_in(self, x, n_in):
+        return _p(x[0]), n_in
+
+    def set_taps(self, taps):
+        """A new prototype of the same length; the node's state is kept."""
+        taps = np.ascontiguousarray(taps, np.float64).ravel()
+        assert taps.size == self.n_taps, (taps.size, self.n_taps)
+        check(self._c_set_taps(self._h, _p(taps, True)))
+
+    def _tail_state(self, *more):
+        """get_state's head: (consumed, tail [n_taps - 1, 2] float32) — `more`: the call's further arguments"""
+        consumed, tail = C.c_uint64(0), np.zeros((self.n_taps - 1, 2), np.float32)
+        check(self._c_get_state(self._h, C.byref(consumed), _p(tail, True), self.n_taps - 1, *more))
+        return consumed.value, tail
+
+    def _plan_info(self, *names):
+        v = [C.c_int(0) for _ in names]
+        check(self._c_plan_info(self._h, *[C.byref(c) for c in v]))
+        return dict(zip(names, [c.value for c in v]))
+
+    @property
+    def kernel_names(self):
+        return _text(self._c_kernel_names, self._h, size=256).split(",")
+
+
+class Channelizer(_Grid):
     """y_k[m] = sum_l h[l] x[t_m - l] exp(-2 pi i k (t_m - l) / M), t_m = (m + 1) D - 1 (sdrhip_channelizer.h has the contract).
     dtype: np.int16 or np.float32, the scalar of the complex input row [n, 2]; taps: the prototype low-pass as doubles (rounded
     once to float32); channels: the channels to write, any order, no duplicates (None: all M in order). process(x) returns
@@ -25,26 +77,12 @@ class Channelizer(_Counted):
 
     def __init__(self, ctx, dtype, M, D, taps, channels=None, max_in=65536, _more=()):
         """_more: what a subclass's create takes between max_in and the handle"""
-        self._abi.lib()
-        super().__init__()
-        self.dtype = _scalar_dtype(dtype, CHAN_CS16, CHAN_CF32)
-        self._in = (np.int16 if self.dtype == CHAN_CS16 else np.float32, 2)
-        taps = np.ascontiguousarray(taps, np.float64).ravel()
-        self.ctx, self.M, self.D, self.n_taps, self.max_in = ctx, int(M), int(D), int(taps.size), int(max_in)
-        self.selected, self.channels = list(range(self.M)), self.M
-        check(getattr(self._abi.lib(), self._prefix + "_create")(ctx.handle, self.dtype, self.M, self.D, _p(taps, True), self.n_taps, self.max_in,
-                                                                 *_more, C.byref(self._h)))
+        super().__init__(ctx, dtype, M, D, taps, max_in, _more)
         if channels is not None:
             self.set_channels(channels)
 
-    # process(x) — x: ONE row [n, 2]; the router sees it as x[None]; the node's calls take no input stride
-    def _rows(self, x):
-        x = np.ascontiguousarray(x, self._in[0])
-        assert x.ndim == 2 and x.shape[1] == 2, x.shape
-        return x[None]
-
-    def _host_in(self, x, n_in):
-        return _p(x[0]), n_in
+    def _created(self):
+        self.selected, self.channels = list(range(self.M)), self.M
 
     def _dev_checked(self, i, n_in, si, o, so, no):
         assert self.process_dev(i, n_in, o, so) == no
@@ -64,25 +102,12 @@ class Channelizer(_Counted):
             self.selected = [int(k) for k in idx]
         self.channels = len(self.selected)
 
-    def set_taps(self, taps):
-        """A new prototype of the same length; the count and the tail are kept."""
-        taps = np.ascontiguousarray(taps, np.float64).ravel()
-        assert taps.size == self.n_taps, (taps.size, self.n_taps)
-        check(self._c_set_taps(self._h, _p(taps, True)))
-
     def get_state(self):
         """-> {consumed: samples taken since create or reset, tail: the last n_taps - 1 samples [n_taps - 1, 2] float32, oldest
         first} behind the calls enqueued so far"""
-        consumed, tail = C.c_uint64(0), np.zeros((self.n_taps - 1, 2), np.float32)
-        check(self._c_get_state(self._h, C.byref(consumed), _p(tail, True), self.n_taps - 1))
-        return {"consumed": consumed.value, "tail": tail}
+        consumed, tail = self._tail_state()
+        return {"consumed": consumed, "tail": tail}
 
     def plan_info(self):
         """{tile_times, branch_taps, lds_bytes, rows} of a launch (sdrhip_channelizer_plan_info)"""
-        v = [C.c_int(0) for _ in range(4)]
-        check(self._c_plan_info(self._h, *[C.byref(c) for c in v]))
-        return dict(zip(("tile_times", "branch_taps", "lds_bytes", "rows"), [c.value for c in v]))
-
-    @property
-    def kernel_names(self):
-        return _text(self._c_kernel_names, self._h, size=256).split(",")
+        return self._plan_info("tile_times", "branch_taps", "lds_bytes", "rows")

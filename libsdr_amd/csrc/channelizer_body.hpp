@@ -1,6 +1,7 @@
-// channelizer_body.hpp — the polyphase channelizer's kernel body, shared by channelizer.hip (complex float rows out) and
-// chanaudio.hip (demodulated int16 rows out). One form serves every M: a workgroup of CH_THREADS lanes takes a tile of T
-// consecutive output times (and, where the epilogue asks for it, `halo` output times before them),
+// channelizer_body.hpp — the polyphase channelizer's kernel body, shared by channelizer.hip (complex float rows out),
+// chanaudio.hip (demodulated int16 rows out) and chanpower.hip (no rows out: per-channel sums of |y|^2). One form serves every
+// M: a workgroup of CH_THREADS lanes takes a tile of T consecutive output times (and, where the epilogue asks for it, `halo`
+// output times before them),
 //   1  all lanes: element (tt, r) of the tile, r fastest — the branch sum u[r] = sum_p h[p M + r] x[t - p M - r] as a float fma
 //      chain over global reads (taps and input are contiguous in r; the row is re-read P times per output time, from L1 / L2) —
 //      written into image tt at the digit-reversed position of (r - t) mod M: the circular shift by the absolute time costs
@@ -13,9 +14,10 @@
 //        int  halo(const ChArgs &, int j0)                           images wanted before output time j0 (0 or 1, uniform)
 //        void store(const ChArgs &, const float2 *img, int j0, int Tc, int halo, int tid)   the tile's outputs; image halo + tt
 //                                                                    holds output time j0 + tt
-//        void roll<I>(const ChArgs &, int tid)                       every block, behind the tile (ch_roll_tail at least)
+//        void roll<I>(const ChArgs &, int tid)                       every block, behind its tiles (ch_roll_tail at least)
+// ch_body gives a workgroup one tile; ch_body_strided walks a launch of fewer workgroups than tiles over them (chanpower.hip).
 // An output time is computed with the same operations in the same order whichever policy asks and wherever it lies in a tile
-// (the library is built with -ffp-contract=off, and the one fused operation is written as such), so the two kernel families
+// (the library is built with -ffp-contract=off, and the one fused operation is written as such), so the kernel families
 // agree bit for bit on the spectra.
 // The input is read at [0, n) and the tail at [0, n_taps - 1) only: the first output time of a call is not before its first
 // sample, the last not behind its last, and terms at l >= n_taps are skipped.
@@ -81,53 +83,72 @@ __device__ __forceinline__ void ch_roll_tail(const ChArgs &a, int tid) {
   }
 }
 
+// one tile: phases 1 to 3 for the output times [tile T, tile T + Tc). tmod_s, rel_s: the tile's time table, CH_TMAX + 1 entries
+// each. A workgroup that walks several tiles calls this in a loop with nothing in between: the barrier behind a tile's time table
+// also ends the store of the tile before (the images are written behind it), and the table itself is read in phase 1 only, which
+// two barriers separate from the next tile's.
+template <class I, class E>
+__device__ __forceinline__ void ch_tile(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
+  const int M = a.M;
+  const I *in = static_cast<const I *>(a.in);
+  const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
+  for (int tt = tid; tt < Ti; tt += CH_THREADS) {
+    const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
+    tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
+    rel_s[tt] = a.lead + (int)jd;
+  }
+  __syncthreads();
+  // phase 1
+  for (int e = tid; e < Ti * M; e += CH_THREADS) {
+    const int tt = e / M, r = e - tt * M;
+    int rel = rel_s[tt] - r;
+    float re = 0.f, im = 0.f;
+#pragma unroll 4
+    for (int l = r; l < a.n_taps; l += M, rel -= M) {
+      // (the clamps never bind — see the head of the file; they keep a wrong count from becoming a wild read)
+      const float2 v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : a.hist[max(a.HH + rel, 0)];
+      const float hv = a.taps[l];
+      re = __builtin_fmaf(hv, v.x, re);
+      im = __builtin_fmaf(hv, v.y, im);
+    }
+    int jw = r - tmod_s[tt];
+    jw += jw < 0 ? M : 0;
+    img[tt * a.ld + a.invperm[jw]] = make_float2(re, im);
+  }
+  __syncthreads();
+  // phase 2
+  int s = 1;
+  for (int pass = a.fft.npass - 1; pass >= 0; pass--) {
+    const int r = a.fft.radix[pass];
+#define SDRHIP_CH_CALL(R_) ch_pass<R_>(img, a.fft, s, Ti, a.ld, tid)
+    SDRHIP_GEN_RADIX_SWITCH(r, SDRHIP_CH_CALL)
+#undef SDRHIP_CH_CALL
+    __syncthreads();
+    s *= r;
+  }
+  // phase 3
+  epi.store(a, img, j0, Tc, halo, tid);
+}
+
+// one tile per workgroup: tile blockIdx.x
 template <class I, class E>
 __device__ __forceinline__ void ch_body(const ChArgs &a, const E &epi) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float2 *img = reinterpret_cast<float2 *>(smem_raw);
   __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
-  const int tid = (int)threadIdx.x, tile = (int)blockIdx.x, M = a.M;
-  const I *in = static_cast<const I *>(a.in);
+  const int tid = (int)threadIdx.x, tile = (int)blockIdx.x;
+  if (tile < a.tiles) ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+  epi.template roll<I>(a, tid);
+}
 
-  if (tile < a.tiles) {
-    const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
-    for (int tt = tid; tt < Ti; tt += CH_THREADS) {
-      const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
-      tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
-      rel_s[tt] = a.lead + (int)jd;
-    }
-    __syncthreads();
-    // phase 1
-    for (int e = tid; e < Ti * M; e += CH_THREADS) {
-      const int tt = e / M, r = e - tt * M;
-      int rel = rel_s[tt] - r;
-      float re = 0.f, im = 0.f;
-#pragma unroll 4
-      for (int l = r; l < a.n_taps; l += M, rel -= M) {
-        // (the clamps never bind — see the head of the file; they keep a wrong count from becoming a wild read)
-        const float2 v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : a.hist[max(a.HH + rel, 0)];
-        const float hv = a.taps[l];
-        re = __builtin_fmaf(hv, v.x, re);
-        im = __builtin_fmaf(hv, v.y, im);
-      }
-      int jw = r - tmod_s[tt];
-      jw += jw < 0 ? M : 0;
-      img[tt * a.ld + a.invperm[jw]] = make_float2(re, im);
-    }
-    __syncthreads();
-    // phase 2
-    int s = 1;
-    for (int pass = a.fft.npass - 1; pass >= 0; pass--) {
-      const int r = a.fft.radix[pass];
-#define SDRHIP_CH_CALL(R_) ch_pass<R_>(img, a.fft, s, Ti, a.ld, tid)
-      SDRHIP_GEN_RADIX_SWITCH(r, SDRHIP_CH_CALL)
-#undef SDRHIP_CH_CALL
-      __syncthreads();
-      s *= r;
-    }
-    // phase 3
-    epi.store(a, img, j0, Tc, halo, tid);
-  }
+// a bounded grid: workgroup b takes the tiles b, b + gridDim.x, ... in that order
+template <class I, class E>
+__device__ __forceinline__ void ch_body_strided(const ChArgs &a, const E &epi) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float2 *img = reinterpret_cast<float2 *>(smem_raw);
+  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+  const int tid = (int)threadIdx.x;
+  for (int tile = (int)blockIdx.x; tile < a.tiles; tile += (int)gridDim.x) ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
   epi.template roll<I>(a, tid);
 }
 

@@ -1,0 +1,296 @@
+// chanpower.hip — the channel power monitor (sdrhip_chanpower.h): the polyphase channelizer's arithmetic on one antenna row with
+// no rows out — M sums of |y|^2 per call, a smoothed level and a squelch flag per channel. Phases 1 and 2 are
+// channelizer_body.hpp's, shared with channelizer.hip and chanaudio.hip, so the spectra have the plain channelizer's bits; this
+// file's epilogue is
+//   3  lane tid owns the channels k = tid, tid + CH_THREADS, ...: it walks the tile's images at img[tt ld + k] (consecutive
+//      lanes read consecutive LDS words) and adds e = (double)re (double)re + (double)im (double)im, in time order, onto the
+//      workgroup's row of the [grid][M] partial buffer — from +0 on the workgroup's first tile, a read-modify-write by the one
+//      owner of the element on the later ones. No atomics: the order is the header's, whatever the timing.
+// The grid is bounded (ch_body_strided: workgroup b takes the tiles b, b + W, ...), so the partial buffer is. The finish kernel
+// runs behind the launch on the same stream, one lane per channel: the rows of the workgroups that ran, added in row order, the
+// call's sum where asked for, and the level and flag update; calls, J and alpha come from the host as arguments.
+#include "sdrhip_internal.hpp"
+#include "sdrhip_chanpower.h"
+#include "entry.hpp"
+#include "channelizer_body.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+
+using namespace sdrhip;
+
+namespace {
+
+constexpr int CP_GRID_PER_CU = 2;   // (an M = 1024 workgroup's images take 64 KiB of the CU's 160)
+constexpr int CP_BATCH = 32;        // partial rows the finish kernel has in flight per lane
+
+// no rows out, no image before the tile; `partial` is [gridDim.x][M]
+struct ChStorePower {
+  double *partial;
+  __device__ __forceinline__ int halo(const ChArgs &, int) const { return 0; }
+  __device__ __forceinline__ void store(const ChArgs &a, const float2 *img, int j0, int Tc, int, int tid) const {
+    double *row = partial + (size_t)blockIdx.x * (size_t)a.M;
+    const bool first = j0 == (int)blockIdx.x * a.T;   // the workgroup's first tile is tile blockIdx.x
+    for (int k = tid; k < a.M; k += CH_THREADS) {
+      double acc = first ? 0.0 : row[k];
+#pragma unroll 4
+      for (int tt = 0; tt < Tc; tt++) {
+        const float2 y = img[tt * a.ld + k];
+        const double re = (double)y.x, im = (double)y.y;
+        acc += re * re + im * im;   // (-ffp-contract=off: two exact products, one rounded add, one rounded accumulation)
+      }
+      row[k] = acc;
+    }
+  }
+  template <class I>
+  __device__ __forceinline__ void roll(const ChArgs &a, int tid) const { ch_roll_tail<I>(a, tid); }
+};
+
+__global__ __launch_bounds__(CH_THREADS) void chanpower_cs16_kernel(const ChArgs a, double *partial) {
+  ch_body_strided<short2>(a, ChStorePower{partial});
+}
+__global__ __launch_bounds__(CH_THREADS) void chanpower_cf32_kernel(const ChArgs a, double *partial) {
+  ch_body_strided<float2>(a, ChStorePower{partial});
+}
+
+struct CpFinishArgs {
+  const double *partial;            // [rows][M]
+  const double *open_thr, *close_thr;   // [M]
+  double *level;                    // [M]
+  unsigned char *open;              // [M]
+  double *sum;                      // [M] or NULL
+  double alpha;
+  int M, rows, J, first;            // rows: the workgroups that ran (0 where J = 0); first: calls == 0
+};
+
+__global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFinishArgs f) {
+  const int k = (int)blockIdx.x * CH_THREADS + (int)threadIdx.x;
+  if (k >= f.M) return;
+  // the rows in increasing order, CP_BATCH loads in flight at a time: the adds are a chain, the loads need not wait for it
+  const double *col = f.partial + k;
+  double s = 0.0;
+  int b = 0;
+  for (; b + CP_BATCH <= f.rows; b += CP_BATCH) {
+    double v[CP_BATCH];
+#pragma unroll
+    for (int i = 0; i < CP_BATCH; i++) v[i] = col[(size_t)(b + i) * (size_t)f.M];
+#pragma unroll
+    for (int i = 0; i < CP_BATCH; i++) s += v[i];
+  }
+  for (; b < f.rows; b++) s += col[(size_t)b * (size_t)f.M];
+  if (f.sum) f.sum[k] = s;
+  if (f.J <= 0) return;
+  const double mean = s / (double)f.J, old = f.level[k];
+  const double level = f.first ? mean : old + f.alpha * (mean - old);
+  f.level[k] = level;
+  f.open[k] = f.open[k] ? !(level < f.close_thr[k]) : level >= f.open_thr[k];
+}
+
+void require_alpha(double alpha) {
+  SDRHIP_REQUIRE(alpha > 0.0 && alpha <= 1.0, SDRHIP_E_INVALID, "alpha %g outside (0,1]", alpha);   // (a NaN fails both)
+}
+
+}  // namespace
+
+struct sdrhip_chanpower : ChPlan {
+  double alpha = 1.0;
+  uint64_t calls = 0;
+  int G = 1;                                   // the workgroups of a launch at most
+  DevBuf<double> partial, level, thr_open, thr_close;   // [G][M], [M], [M], [M]
+  DevBuf<unsigned char> open;                  // [M]
+  size_t lds_bytes() const { return (size_t)T * (size_t)ld * sizeof(float2); }
+  void fresh_state() {
+    SDRHIP_CHECK_HIP(hipMemsetAsync(level.p, 0, (size_t)M * sizeof(double), ctx->stream));
+    SDRHIP_CHECK_HIP(hipMemsetAsync(open.p, 0, (size_t)M, ctx->stream));
+    fresh_tail();   // (synchronises)
+    calls = 0;
+  }
+  // n >= 1; sum_dev may be NULL
+  void launch(const void *in_dev, size_t n, double *sum_dev, size_t n_out) {
+    ctx->use();
+    const ChArgs a = args(in_dev, n, nullptr, 0, n_out);
+    const int rows = std::min(a.tiles, G);
+    const dim3 grid((unsigned)std::max(rows, 1)), block(CH_THREADS);
+    const size_t lds = lds_bytes();
+    (void)hipGetLastError();
+    if (dtype == SDRHIP_CHAN_CS16) hipLaunchKernelGGL(chanpower_cs16_kernel, grid, block, lds, ctx->stream, a, partial.p);
+    else hipLaunchKernelGGL(chanpower_cf32_kernel, grid, block, lds, ctx->stream, a, partial.p);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    advance(n);
+    if (n_out == 0 && !sum_dev) return;
+    CpFinishArgs f;
+    f.partial = partial.p; f.open_thr = thr_open.p; f.close_thr = thr_close.p; f.level = level.p; f.open = open.p; f.sum = sum_dev;
+    f.alpha = alpha; f.M = M; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
+    hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)M, (size_t)CH_THREADS)), block, 0, ctx->stream, f);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    if (n_out) calls++;
+  }
+};
+
+extern "C" {
+
+int sdrhip_chanpower_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha,
+                            sdrhip_chanpower **out) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
+    std::vector<float> h32;
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32);
+    require_alpha(alpha);
+    require_device_for_null_ctx(ctx);
+    make_handle(ctx, out, true, [&](sdrhip_chanpower *h) {
+      h->build(ctx, dtype, M, D, h32, max_in);
+      h->alpha = alpha;
+      const char *e = getenv("SDRHIP_CHANPOWER_GRID");   // read once: the partial buffer is allocated for it
+      h->G = std::max(1, CP_GRID_PER_CU * ctx->prop.multiProcessorCount);
+      if (e && atoi(e) >= 1) h->G = std::min(h->G, atoi(e));
+      // (no call has more tiles than max_in gives)
+      h->G = (int)std::min((size_t)h->G, std::max(ceil_div(h->out_count_max(max_in), (size_t)h->T), (size_t)1));
+      h->partial.alloc((size_t)h->G * (size_t)M);
+      h->level.alloc((size_t)M);
+      h->open.alloc((size_t)M);
+      std::vector<double> inf((size_t)M, HUGE_VAL), zero((size_t)M, 0.0);
+      h->thr_open.alloc((size_t)M);
+      h->thr_open.upload(inf.data(), inf.size(), ctx->stream);
+      h->thr_close.alloc((size_t)M);
+      h->thr_close.upload(zero.data(), zero.size(), ctx->stream);
+      SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // (the uploads read locals)
+      allow_lds_max(dtype == SDRHIP_CHAN_CS16 ? chanpower_cs16_kernel : chanpower_cf32_kernel, h->lds_bytes());
+      h->fresh_state();
+    });
+  });
+}
+
+int sdrhip_chanpower_out_count(sdrhip_chanpower *h, size_t n, size_t *n_out) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
+    *n_out = h->out_count(n);
+  });
+}
+
+int sdrhip_chanpower_process_dev(sdrhip_chanpower *h, const void *in_dev, size_t n, double *sum_dev, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_chanpower_process_dev");
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_dev, sum_dev ? (const void *)sum_dev : in_dev)) return;   // (the sums are optional)
+    const size_t no = h->out_count(n);
+    if (sum_dev) require_disjoint(in_dev, n, n, h->in_elem(), sum_dev, (size_t)h->M, (size_t)h->M, sizeof(double), 1);
+    h->launch(in_dev, n, sum_dev, no);
+    if (n_out) *n_out = no;
+  });
+}
+
+int sdrhip_chanpower_process(sdrhip_chanpower *h, const void *in_host, size_t n, double *sum_host, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_chanpower_process");
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_host, sum_host)) return;
+    const size_t no = h->out_count(n), eb = h->in_elem(), row_b = (size_t)h->M * sizeof(double);
+    run_staged(h->ctx, h->stage, h->max_in * eb, row_b, {in_host, n * eb, n * eb, 1}, {sum_host, row_b, row_b, 1},
+               [&](void *in, void *out) {
+                 h->launch(in, n, static_cast<double *>(out), no);
+                 return row_b;
+               });
+    if (n_out) *n_out = no;
+  });
+}
+
+int sdrhip_chanpower_set_thresholds(sdrhip_chanpower *h, const double *open_thr, const double *close_thr) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && open_thr && close_thr, SDRHIP_E_INVALID, "NULL argument");
+    for (int k = 0; k < h->M; k++)   // (a NaN fails the comparison it meets)
+      SDRHIP_REQUIRE(close_thr[k] >= 0.0 && close_thr[k] <= open_thr[k], SDRHIP_E_INVALID,
+                     "thresholds of channel %d: 0 <= close_thr %g <= open_thr %g does not hold", k, close_thr[k], open_thr[k]);
+    h->ctx->use();
+    hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued; both or none is not promised on a failing device
+    const size_t b = (size_t)h->M * sizeof(double);
+    const hipError_t e1 = hipMemcpyAsync(h->thr_open.p, open_thr, b, hipMemcpyHostToDevice, st);
+    const hipError_t e2 = hipMemcpyAsync(h->thr_close.p, close_thr, b, hipMemcpyHostToDevice, st);
+    const hipError_t e3 = hipStreamSynchronize(st);
+    SDRHIP_CHECK_HIP(e1);
+    SDRHIP_CHECK_HIP(e2);
+    SDRHIP_CHECK_HIP(e3);
+  });
+}
+
+int sdrhip_chanpower_set_alpha(sdrhip_chanpower *h, double alpha) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    require_alpha(alpha);
+    h->alpha = alpha;
+  });
+}
+
+int sdrhip_chanpower_set_taps(sdrhip_chanpower *h, const double *taps) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
+    h->ctx->use();
+    h->set_taps(taps);
+  });
+}
+
+int sdrhip_chanpower_reset(sdrhip_chanpower *h) {
+  return guarded([&] {
+    use_handle(h);
+    h->fresh_state();
+  });
+}
+
+int sdrhip_chanpower_get_levels(sdrhip_chanpower *h, double *level, unsigned char *open, int len) {
+  return guarded([&] {
+    use_handle(h);
+    SDRHIP_REQUIRE(len >= h->M, SDRHIP_E_SIZE, "len %d < M = %d", len, h->M);
+    if (level) get_sync(h->ctx, level, h->level.p, (size_t)h->M * sizeof(double));
+    if (open) get_sync(h->ctx, open, h->open.p, (size_t)h->M);
+  });
+}
+
+int sdrhip_chanpower_get_occupied(sdrhip_chanpower *h, int *idx, int cap, int *count) {
+  return guarded([&] {
+    use_handle(h);
+    SDRHIP_REQUIRE(count && (idx || cap <= 0), SDRHIP_E_INVALID, "NULL argument");
+    std::vector<unsigned char> open((size_t)h->M);
+    get_sync(h->ctx, open.data(), h->open.p, open.size());
+    int n = 0;
+    for (int k = 0; k < h->M; k++)
+      if (open[(size_t)k]) {
+        if (n < cap) idx[n] = k;
+        n++;
+      }
+    *count = n;
+  });
+}
+
+int sdrhip_chanpower_get_state(sdrhip_chanpower *h, uint64_t *consumed, float *tail, size_t tail_len, uint64_t *calls) {
+  return guarded([&] {
+    use_handle(h);
+    h->get_tail(consumed, tail, tail_len);
+    if (calls) *calls = h->calls;
+  });
+}
+
+int sdrhip_chanpower_plan_info(sdrhip_chanpower *h, int *tile_times, int *branch_taps, int *lds_bytes, int *grid, int *partial_bytes) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+    if (tile_times) *tile_times = h->T;
+    if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
+    if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+    if (grid) *grid = h->G;
+    if (partial_bytes) *partial_bytes = (int)(h->partial.n * sizeof(double));
+  });
+}
+
+int sdrhip_chanpower_kernel_names(sdrhip_chanpower *h, char *buf, size_t len) {
+  return guarded([&] {
+    write_names(h, buf, len, [&] {
+      return h->dtype == SDRHIP_CHAN_CS16 ? "chanpower_cs16_kernel,chanpower_finish_kernel" : "chanpower_cf32_kernel,chanpower_finish_kernel";
+    });
+  });
+}
+
+int sdrhip_chanpower_destroy(sdrhip_chanpower *h) {
+  return guarded([&] { destroy_handle(h); });
+}
+
+}  // extern "C"
