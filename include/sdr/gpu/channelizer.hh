@@ -8,6 +8,9 @@
  * per row, in row order, as views of it; a buffer that completes no block of D samples sends nothing. processDev() runs the
  * same plan on device rows of the node's device and synchronises nothing: its rows drop into the processDev of the banks that
  * take complex float rows (gpu::InpolSubSamplerBank, the BPSK31 and AGC banks).
+ *
+ * The node's body is gpu::ChannelizerNode<Grid>; Grid says what the complex node and the real-input one of chanreal.hh
+ * (gpu::RealChannelizer<Scalar>) differ in: the input element, the rule for M, the channel count and the create call.
  */
 #ifndef SDR_GPU_CHANNELIZER_HH
 #define SDR_GPU_CHANNELIZER_HH
@@ -16,6 +19,7 @@
 #include "../../sdrhip_channelizer.h"
 
 #include <cmath>
+#include <string>
 #include <vector>
 
 namespace sdr {
@@ -25,43 +29,57 @@ namespace detail {
 template <class Scalar> struct ChannelizerType;
 template <> struct ChannelizerType<int16_t> { enum { dtype = SDRHIP_CHAN_CS16 }; };
 template <> struct ChannelizerType<float> { enum { dtype = SDRHIP_CHAN_CF32 }; };
+
+/** The complex node's grid: M channels of an M-point transform, sdrhip_channelizer_create. */
+template <class Scalar> struct ComplexGrid {
+  typedef std::complex<Scalar> In;
+  static const char *name() { return "Channelizer"; }
+  static const char *ruleM() { return " (2 ... 4096, prime factors up to 13)"; }
+  static bool admitsM(size_t M) { return M >= 2 && M <= 4096; }
+  static size_t transform(size_t M) { return M; }
+  static size_t channels(size_t M) { return M; }
+  static int create(sdrhip_ctx *ctx, int M, int D, const double *taps, int nTaps, size_t maxIn, sdrhip_channelizer **out) {
+    return sdrhip_channelizer_create(ctx, ChannelizerType<Scalar>::dtype, M, D, taps, nTaps, maxIn, out);
+  }
+};
 }  // namespace detail
 
-template <class Scalar>
-class Channelizer : public Sink< std::complex<Scalar> > {
+template <class Grid>
+class ChannelizerNode : public Sink<typename Grid::In> {
 public:
-  typedef std::complex<Scalar> In;
+  typedef typename Grid::In In;
   typedef ChannelBank<int16_t>::Out Out;
 
-  /** M channels decimated by D with the prototype low-pass `taps`; channels: the channels to deliver, any order, no duplicates
-   * (empty: all M in order). The rules of sdrhip_channelizer_create are checked here and throw ConfigError: 2 <= M <= 4096 with
-   * prime factors up to 13, 1 <= D <= M, 1 <= taps.size() <= 64 M, every tap finite as a float, every channel in [0, M), once. */
-  Channelizer(size_t M, size_t D, const std::vector<double> &taps, const std::vector<int> &channels = std::vector<int>(), int device = 0)
-    : Sink<In>(), _M(M), _D(D), _taps(taps), _sel(channels), _device(device), _ctx(0), _bs(0), _outStride(0) {
-    size_t rest = M;
+  /** M, D, taps and channels as gpu::Channelizer and gpu::RealChannelizer say; the grid's rules are checked here and throw
+   * ConfigError. */
+  ChannelizerNode(size_t M, size_t D, const std::vector<double> &taps, const std::vector<int> &channels, int device)
+    : Sink<In>(), _M(M), _D(D), _taps(taps), _sel(channels), _device(device), _ctx(0), _bs(0), _outStride(0),
+      _gpuName(std::string("gpu::") + Grid::name()) {
+    size_t rest = Grid::admitsM(M) ? Grid::transform(M) : 0;
     const size_t primes[] = {2, 3, 5, 7, 11, 13};
     for (size_t q = 0; q < 6; q++) while (rest > 1 && rest % primes[q] == 0) rest /= primes[q];
     bool finite = true;
     for (size_t i = 0; i < taps.size(); i++) finite = finite && std::isfinite(float(taps[i]));
-    if (M < 2 || M > 4096 || rest != 1 || D < 1 || D > M || taps.empty() || taps.size() > 64 * M || !finite) {
+    if (rest != 1 || D < 1 || D > M || taps.empty() || taps.size() > 64 * M || !finite) {
       ConfigError err;
-      err << "Can not configure Channelizer node: M = " << M << " (2 ... 4096, prime factors up to 13), D = " << D << " (1 ... M), "
+      err << "Can not configure " << Grid::name() << " node: M = " << M << Grid::ruleM() << ", D = " << D << " (1 ... M), "
           << taps.size() << " taps (1 ... 64 M, all finite as floats)";
       throw err;
     }
-    if (_sel.empty()) for (size_t k = 0; k < M; k++) _sel.push_back(int(k));
-    std::vector<bool> seen(M, false);
+    const size_t K = Grid::channels(M);
+    if (_sel.empty()) for (size_t k = 0; k < K; k++) _sel.push_back(int(k));
+    std::vector<bool> seen(K, false);
     for (size_t i = 0; i < _sel.size(); i++) {
-      if (_sel[i] < 0 || size_t(_sel[i]) >= M || seen[size_t(_sel[i])]) {
+      if (_sel[i] < 0 || size_t(_sel[i]) >= K || seen[size_t(_sel[i])]) {
         ConfigError err;
-        err << "Can not configure Channelizer node: channel " << _sel[i] << " (row " << i << ") is outside [0, " << M << ") or selected twice";
+        err << "Can not configure " << Grid::name() << " node: channel " << _sel[i] << " (row " << i << ") is outside [0, " << K << ") or selected twice";
         throw err;
       }
       seen[size_t(_sel[i])] = true;
     }
     for (size_t i = 0; i < _sel.size(); i++) _outs.push_back(new Out());
   }
-  virtual ~Channelizer() {
+  virtual ~ChannelizerNode() {
     _release();
     for (size_t i = 0; i < _outs.size(); i++) delete _outs[i];
   }
@@ -76,20 +94,19 @@ public:
 
   virtual void config(const Config &cfg) {
     if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
-    detail::checkType<In>(cfg, "Channelizer node");
+    detail::checkType<In>(cfg, (std::string(Grid::name()) + " node").c_str());
     _release();
     _bs = cfg.bufferSize();
     if (_bs == 0) return;
     _ctx = Device::get(_device);
-    detail::configCheck(sdrhip_channelizer_create(_ctx, detail::ChannelizerType<Scalar>::dtype, int(_M), int(_D), _taps.data(), int(_taps.size()),
-                                                  _bs, _plan.out()), "Channelizer");
-    detail::configCheck(sdrhip_channelizer_set_channels(_plan, _sel.data(), int(_sel.size())), "Channelizer");
+    detail::configCheck(Grid::create(_ctx, int(_M), int(_D), _taps.data(), int(_taps.size()), _bs, _plan.out()), Grid::name());
+    detail::configCheck(sdrhip_channelizer_set_channels(_plan, _sel.data(), int(_sel.size())), Grid::name());
     _outStride = (_bs + _D - 1) / _D;
     const size_t R = _sel.size();
-    _din.alloc(_ctx, _bs * sizeof(In), "Channelizer");
-    _dout.alloc(_ctx, R * _outStride * sizeof(cf32), "Channelizer");
+    _din.alloc(_ctx, _bs * sizeof(In), Grid::name());
+    _dout.alloc(_ctx, R * _outStride * sizeof(cf32), Grid::name());
     _stageOut = Buffer<cf32>(R * _outStride);
-    _pinOut.reset(_stageOut.data(), R * _outStride * sizeof(cf32), "Channelizer");
+    _pinOut.reset(_stageOut.data(), R * _outStride * sizeof(cf32), Grid::name());
     for (size_t i = 0; i < R; i++) _outs[i]->configure(Config(Config::typeId<cf32>(), cfg.sampleRate() / double(_D), _outStride, 1));
   }
 
@@ -98,16 +115,16 @@ public:
     // the per-row outputs are views of _stageOut: while a consumer still holds one of the last round, this round is dropped
     if (!_stageOut.isUnused()) {
       LogMessage msg(LOG_WARNING);
-      msg << "gpu::Channelizer: output of the last round still in use downstream; buffer dropped";
+      msg << _gpuName << ": output of the last round still in use downstream; buffer dropped";
       Logger::get().log(msg);
       return;
     }
     const size_t R = _sel.size();
     size_t n = 0;
-    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din.get(), b.data(), b.size() * sizeof(In)), "gpu::Channelizer") ||
-        !detail::processOk(sdrhip_channelizer_process_dev(_plan, _din.get(), b.size(), _dout.get(), _outStride, &n), "gpu::Channelizer") ||
-        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout.get(), R * _outStride * sizeof(cf32)), "gpu::Channelizer") ||
-        !detail::processOk(sdrhip_ctx_synchronize(_ctx), "gpu::Channelizer"))
+    if (!detail::processOk(sdrhip_memcpy_h2d_async(_ctx, _din.get(), b.data(), b.size() * sizeof(In)), _gpuName.c_str()) ||
+        !detail::processOk(sdrhip_channelizer_process_dev(_plan, _din.get(), b.size(), _dout.get(), _outStride, &n), _gpuName.c_str()) ||
+        !detail::processOk(sdrhip_memcpy_d2h_async(_ctx, _stageOut.data(), _dout.get(), R * _outStride * sizeof(cf32)), _gpuName.c_str()) ||
+        !detail::processOk(sdrhip_ctx_synchronize(_ctx), _gpuName.c_str()))
       return;
     if (n == 0) return;
     for (size_t i = 0; i < R; i++) _outs[i]->emit(_stageOut.sub(i * _outStride, n), false);
@@ -116,23 +133,23 @@ public:
   /** One row of n device samples in, rows() device rows out (outStride in complex floats, at least the call's output count);
    * one launch on the context's stream, nothing is synchronised. After config() only. */
   bool processDev(const void *inDev, size_t n, void *outDev, size_t outStride, size_t *nOut) {
-    return detail::processOk(sdrhip_channelizer_process_dev(_plan, inDev, n, outDev, outStride, nOut), "gpu::Channelizer");
+    return detail::processOk(sdrhip_channelizer_process_dev(_plan, inDev, n, outDev, outStride, nOut), _gpuName.c_str());
   }
   /** A new prototype of the same length; the stream goes on. */
   void setTaps(const std::vector<double> &taps) {
     if (taps.size() != _taps.size()) {
       ConfigError err;
-      err << "Channelizer: " << taps.size() << " taps where the node has " << _taps.size();
+      err << Grid::name() << ": " << taps.size() << " taps where the node has " << _taps.size();
       throw err;
     }
-    if (_plan) detail::configCheck(sdrhip_channelizer_set_taps(_plan, taps.data()), "Channelizer");
+    if (_plan) detail::configCheck(sdrhip_channelizer_set_taps(_plan, taps.data()), Grid::name());
     _taps = taps;
   }
-  void reset() { if (_plan) detail::configCheck(sdrhip_channelizer_reset(_plan), "Channelizer"); }
+  void reset() { if (_plan) detail::configCheck(sdrhip_channelizer_reset(_plan), Grid::name()); }
   /** The samples taken since config() or reset(). */
   uint64_t consumed() const {
     uint64_t c = 0;
-    if (_plan) detail::configCheck(sdrhip_channelizer_get_state(_plan, &c, 0, 0), "Channelizer");
+    if (_plan) detail::configCheck(sdrhip_channelizer_get_state(_plan, &c, 0, 0), Grid::name());
     return c;
   }
 
@@ -158,6 +175,17 @@ protected:
   size_t _bs, _outStride;
   std::vector<Out *> _outs;
   Buffer<cf32> _stageOut;
+  std::string _gpuName;     // "gpu::<name>", for the log
+};
+
+template <class Scalar>
+class Channelizer : public ChannelizerNode< detail::ComplexGrid<Scalar> > {
+public:
+  /** M channels decimated by D with the prototype low-pass `taps`; channels: the channels to deliver, any order, no duplicates
+   * (empty: all M in order). The rules of sdrhip_channelizer_create are checked here and throw ConfigError: 2 <= M <= 4096 with
+   * prime factors up to 13, 1 <= D <= M, 1 <= taps.size() <= 64 M, every tap finite as a float, every channel in [0, M), once. */
+  Channelizer(size_t M, size_t D, const std::vector<double> &taps, const std::vector<int> &channels = std::vector<int>(), int device = 0)
+    : ChannelizerNode< detail::ComplexGrid<Scalar> >(M, D, taps, channels, device) {}
 };
 
 }  // namespace gpu

@@ -13,6 +13,7 @@ from .pocsag import POCSAGBank, MessageAssembler, Message  # noqa: F401
 from .agc import AGC, AGCBank, design_agc_lambda, design_agc_target  # noqa: F401
 from .psk31 import BPSK31, BPSK31Bank, Varicode, design_inpol_taps  # noqa: F401
 from .resample import InpolSubSampler, InpolSubSamplerBank  # noqa: F401
+from . import abi_chanreal  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from .chanaudio import AudioChannelizer  # noqa: F401
 from .chanpower import ChannelPower  # noqa: F401

@@ -23,13 +23,17 @@ class AudioChannelizer(Channelizer):
     _out_dtype = np.int16
     epilogue = EPI_FM   # (any demodulator: the rows are real)
     _abi = abi_chanaudio
+    _create_real = "sdrhip_chanreal_audio_create"
 
-    def __init__(self, ctx, dtype, M, D, taps, modes=None, gains=None, channels=None, max_in=65536):
+    def __init__(self, ctx, dtype, M, D, taps, modes=None, gains=None, channels=None, max_in=65536, real=False):
+        """real=True: a row [n] of real samples; modes and gains have M / 2 + 1 entries (sdrhip_chanreal.h)"""
         m = None if modes is None else np.ascontiguousarray(modes, np.intc).ravel()
         g = None if gains is None else np.ascontiguousarray(gains, np.float32).ravel()
-        assert m is None or m.size == int(M), (m.size, M)
-        assert g is None or g.size == int(M), (g.size, M)
-        super().__init__(ctx, dtype, M, D, taps, channels, max_in, _more=(None if m is None else _p(m, True), None if g is None else _p(g, True)))
+        K = int(M) // 2 + 1 if real else int(M)
+        assert m is None or m.size == K, (m.size, K)
+        assert g is None or g.size == K, (g.size, K)
+        super().__init__(ctx, dtype, M, D, taps, channels, max_in, _more=(None if m is None else _p(m, True), None if g is None else _p(g, True)),
+                         real=real)
 
     def set_mode(self, row, mode):
         """Row `row`'s channel gets the demodulator and starts from last = 0."""

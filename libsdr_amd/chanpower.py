@@ -23,9 +23,11 @@ class ChannelPower(_Grid):
     _calls = ("out_count process process_dev set_thresholds set_alpha set_taps reset get_levels get_occupied get_state plan_info "
               "kernel_names")
     _abi = abi_chanpower
+    _create_real = "sdrhip_chanreal_power_create"
 
-    def __init__(self, ctx, dtype, M, D, taps, alpha=0.25, max_in=65536):
-        super().__init__(ctx, dtype, M, D, taps, max_in, _more=(float(alpha),))
+    def __init__(self, ctx, dtype, M, D, taps, alpha=0.25, max_in=65536, real=False):
+        """real=True: a row [n] of real samples; sums, levels, flags and thresholds have M / 2 + 1 entries (sdrhip_chanreal.h)"""
+        super().__init__(ctx, dtype, M, D, taps, max_in, _more=(float(alpha),), real=real)
         self.alpha = float(alpha)
 
     def process(self, x):
@@ -33,7 +35,7 @@ class ChannelPower(_Grid):
         x = self._rows(x)
         n = x.shape[1]
         no = self.out_count(n)
-        out = np.zeros((1, self.M), np.float64)   # (one row of M doubles: what the router guards)
+        out = np.zeros((1, self.n_channels), np.float64)   # (one row of doubles, one per channel: what the router guards)
         if nodes.device_router is not None and n:
             nodes.device_router(self.ctx, x, out, lambda i, si, o, so: self._dev_checked(i, n, o, no))
         else:
@@ -49,7 +51,7 @@ class ChannelPower(_Grid):
 
     def set_thresholds(self, open, close):
         """open, close: [M] each, or scalars for every channel; 0 <= close <= open. The flags move with the next call."""
-        o, c = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (self.M,))) for v in (open, close))
+        o, c = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (self.n_channels,))) for v in (open, close))
         check(self._c_set_thresholds(self._h, _p(o, True), _p(c, True)))
 
     def set_alpha(self, alpha):
@@ -58,14 +60,14 @@ class ChannelPower(_Grid):
 
     def levels(self):
         """-> (level [M] float64, open [M] bool) behind the calls enqueued so far"""
-        level, flags = np.zeros(self.M, np.float64), np.zeros(self.M, np.uint8)
-        check(self._c_get_levels(self._h, _p(level, True), _p(flags, True), self.M))
+        level, flags = np.zeros(self.n_channels, np.float64), np.zeros(self.n_channels, np.uint8)
+        check(self._c_get_levels(self._h, _p(level, True), _p(flags, True), self.n_channels))
         return level, flags.astype(bool)
 
     def occupied(self):
         """-> the open channels, ascending: what set_channels of the two channelizers takes (where it is not empty)"""
-        idx, count = np.zeros(self.M, np.intc), C.c_int(0)
-        check(self._c_get_occupied(self._h, _p(idx, True), self.M, C.byref(count)))
+        idx, count = np.zeros(self.n_channels, np.intc), C.c_int(0)
+        check(self._c_get_occupied(self._h, _p(idx, True), self.n_channels, C.byref(count)))
         return [int(k) for k in idx[:count.value]]
 
     def get_state(self):

@@ -8,8 +8,11 @@
 //      j = 1 differences against the channel's `last`, j = 0 is q.re.
 // `last` is per channel and double-buffered like the tail: the workgroup holding output n_out - 1 (n_out >= 2) writes every FM
 // channel's angle there — selected or not, its image has all M bins — and block 0 copies every other entry.
+// A handle of sdrhip_chanreal_audio_create (sdrhip_chanreal.h) runs chanaudio_real_s16_kernel / chanaudio_real_f32_kernel: the body's
+// real form in front of the same epilogue; the per-channel arrays then have nch = M / 2 + 1 entries.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanaudio.h"
+#include "sdrhip_chanreal.h"
 #include "entry.hpp"
 #include "channelizer_body.hpp"
 #include "fm_phi.hpp"
@@ -23,10 +26,10 @@ namespace {
 
 struct ChAudioArgs {
   ChArgs c;
-  const int *mode;      // [M] SDRHIP_EPI_FM | _AM | _USB
-  const float *gain;    // [M]
-  const int *last;      // [M] the angles before the call
-  int *last_new;        // [M] behind it
+  const int *mode;      // [nch] SDRHIP_EPI_FM | _AM | _USB
+  const float *gain;    // [nch]
+  const int *last;      // [nch] the angles before the call
+  int *last_new;        // [nch] behind it
   int fm_rows;          // selected rows that are FM
 };
 
@@ -78,6 +81,12 @@ struct ChStoreAudio {
 
 __global__ __launch_bounds__(CH_THREADS) void chanaudio_cs16_kernel(const ChAudioArgs a) { ch_body<short2>(a.c, ChStoreAudio{a}); }
 __global__ __launch_bounds__(CH_THREADS) void chanaudio_cf32_kernel(const ChAudioArgs a) { ch_body<float2>(a.c, ChStoreAudio{a}); }
+__global__ __launch_bounds__(CH_THREADS) void chanaudio_real_s16_kernel(const ChAudioArgs a) { ch_body<short>(a.c, ChStoreAudio{a}); }
+__global__ __launch_bounds__(CH_THREADS) void chanaudio_real_f32_kernel(const ChAudioArgs a) { ch_body<float>(a.c, ChStoreAudio{a}); }
+
+using CaKernel = void (*)(const ChAudioArgs);
+constexpr CaKernel CA_KERNELS[2][2] = {{chanaudio_cs16_kernel, chanaudio_cf32_kernel}, {chanaudio_real_s16_kernel, chanaudio_real_f32_kernel}};
+constexpr const char *CA_NAMES[2][2] = {{"chanaudio_cs16_kernel", "chanaudio_cf32_kernel"}, {"chanaudio_real_s16_kernel", "chanaudio_real_f32_kernel"}};
 
 // SDRHIP_EPI_NONE has a code of its own: its rows would have another element size
 void require_mode(int mode, const char *what, int index) {
@@ -93,10 +102,11 @@ void require_gain(float gain, const char *what, int index) {
 }  // namespace
 
 struct sdrhip_chanaudio : ChPlan {
-  std::vector<int> mode_host;      // [M]
-  std::vector<float> gain_host;    // [M]
-  DevBuf<int> mode, last[2];       // [M] each; last[cur] holds the state (the buffers flip with the tail's)
-  DevBuf<float> gain;              // [M]
+  std::vector<int> mode_host;      // [nch]
+  std::vector<float> gain_host;    // [nch]
+  DevBuf<int> mode, last[2];       // [nch] each; last[cur] holds the state (the buffers flip with the tail's)
+  DevBuf<float> gain;              // [nch]
+  CaKernel kernel() const { return CA_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
   size_t lds_bytes() const { return (size_t)(T + 1) * (size_t)ld * sizeof(float2); }
   int fm_rows() const {
     int n = 0;
@@ -104,7 +114,7 @@ struct sdrhip_chanaudio : ChPlan {
     return n;
   }
   void fresh_state() {
-    SDRHIP_CHECK_HIP(hipMemsetAsync(last[0].p, 0, (size_t)M * sizeof(int), ctx->stream));
+    SDRHIP_CHECK_HIP(hipMemsetAsync(last[0].p, 0, (size_t)nch * sizeof(int), ctx->stream));
     fresh_tail();   // (synchronises, and cur = 0)
   }
   void require_row(int row) const { SDRHIP_REQUIRE(row >= 0 && row < n_sel, SDRHIP_E_INVALID, "row %d outside [0,%d)", row, n_sel); }
@@ -118,40 +128,55 @@ struct sdrhip_chanaudio : ChPlan {
     const dim3 grid((unsigned)std::max(a.c.tiles, 1)), block(CH_THREADS);
     const size_t lds = lds_bytes();
     (void)hipGetLastError();
-    if (dtype == SDRHIP_CHAN_CS16) hipLaunchKernelGGL(chanaudio_cs16_kernel, grid, block, lds, ctx->stream, a);
-    else hipLaunchKernelGGL(chanaudio_cf32_kernel, grid, block, lds, ctx->stream, a);
+    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a);
     SDRHIP_CHECK_HIP(hipGetLastError());
     advance(n);
   }
 };
 
-extern "C" {
+namespace {
 
-int sdrhip_chanaudio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes,
-                            const float *gains, sdrhip_chanaudio **out) {
+// both create calls; real: sdrhip_chanreal.h's, K = M / 2 + 1 channels (the rules before have made M even)
+int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes, const float *gains,
+           sdrhip_chanaudio **out, bool real) {
   return guarded([&] {
     if (out) *out = nullptr;
     SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
     std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32);
-    for (int k = 0; modes && k < M; k++) require_mode(modes[k], "channel", k);
-    for (int k = 0; gains && k < M; k++) require_gain(gains[k], "channel", k);
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
+    const int K = real ? M / 2 + 1 : M;
+    for (int k = 0; modes && k < K; k++) require_mode(modes[k], "channel", k);
+    for (int k = 0; gains && k < K; k++) require_gain(gains[k], "channel", k);
     require_device_for_null_ctx(ctx);
     make_handle(ctx, out, true, [&](sdrhip_chanaudio *h) {
-      h->build(ctx, dtype, M, D, h32, max_in);
-      h->mode_host.assign((size_t)M, SDRHIP_EPI_FM);
-      h->gain_host.assign((size_t)M, 1.0f);
-      if (modes) h->mode_host.assign(modes, modes + M);
-      if (gains) h->gain_host.assign(gains, gains + M);
-      h->mode.alloc((size_t)M);
-      h->mode.upload(h->mode_host.data(), (size_t)M, ctx->stream);
-      h->gain.alloc((size_t)M);
-      h->gain.upload(h->gain_host.data(), (size_t)M, ctx->stream);
-      for (auto &b : h->last) { b.alloc((size_t)M); b.zero(ctx->stream); }
-      allow_lds_max(dtype == SDRHIP_CHAN_CS16 ? chanaudio_cs16_kernel : chanaudio_cf32_kernel, h->lds_bytes());
+      h->build(ctx, dtype, M, D, h32, max_in, real);
+      h->mode_host.assign((size_t)K, SDRHIP_EPI_FM);
+      h->gain_host.assign((size_t)K, 1.0f);
+      if (modes) h->mode_host.assign(modes, modes + K);
+      if (gains) h->gain_host.assign(gains, gains + K);
+      h->mode.alloc((size_t)K);
+      h->mode.upload(h->mode_host.data(), (size_t)K, ctx->stream);
+      h->gain.alloc((size_t)K);
+      h->gain.upload(h->gain_host.data(), (size_t)K, ctx->stream);
+      for (auto &b : h->last) { b.alloc((size_t)K); b.zero(ctx->stream); }
+      allow_lds_max(h->kernel(), h->lds_bytes());
       h->fresh_state();
     });
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdrhip_chanaudio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes,
+                            const float *gains, sdrhip_chanaudio **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, modes, gains, out, false);
+}
+
+int sdrhip_chanreal_audio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in,
+                                 const int *modes, const float *gains, sdrhip_chanaudio **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, modes, gains, out, true);
 }
 
 int sdrhip_chanaudio_out_count(sdrhip_chanaudio *h, size_t n, size_t *n_out) {
@@ -264,7 +289,7 @@ int sdrhip_chanaudio_get_state(sdrhip_chanaudio *h, uint64_t *consumed, float *t
     SDRHIP_REQUIRE(!last || n_last >= (size_t)h->n_sel, SDRHIP_E_SIZE, "n_last %zu < rows = %d", n_last, h->n_sel);
     h->get_tail(consumed, tail, tail_len);
     if (last) {
-      std::vector<int> all((size_t)h->M);
+      std::vector<int> all((size_t)h->nch);
       get_sync(h->ctx, all.data(), h->last[h->cur].p, all.size() * sizeof(int));
       for (int i = 0; i < h->n_sel; i++) last[i] = all[(size_t)h->sel_host[(size_t)i]];
     }
@@ -289,7 +314,7 @@ int sdrhip_chanaudio_plan_info(sdrhip_chanaudio *h, int *tile_times, int *branch
 
 int sdrhip_chanaudio_kernel_names(sdrhip_chanaudio *h, char *buf, size_t len) {
   return guarded([&] {
-    write_names(h, buf, len, [&] { return h->dtype == SDRHIP_CHAN_CS16 ? "chanaudio_cs16_kernel" : "chanaudio_cf32_kernel"; });
+    write_names(h, buf, len, [&] { return CA_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
   });
 }
 

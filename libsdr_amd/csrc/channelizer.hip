@@ -6,8 +6,11 @@
 //      element apart from a multiple of M in LDS so that the lanes of a row do not meet on a bank.
 // Every block also rolls its share of the tail (the last n_taps - 1 samples, as complex float) into the handle's other tail
 // buffer: the blocks of a launch read the old one.
+// A handle of sdrhip_chanreal_channelizer_create (sdrhip_chanreal.h) runs channelizer_real_s16_kernel / channelizer_real_f32_kernel: the
+// body's real form in front of the same epilogue, rows 0 ... M / 2.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
+#include "sdrhip_chanreal.h"
 #include "entry.hpp"
 #include "channelizer_body.hpp"
 
@@ -36,10 +39,17 @@ struct ChStoreComplex {
 
 __global__ __launch_bounds__(CH_THREADS) void channelizer_cs16_kernel(const ChArgs a) { ch_body<short2>(a, ChStoreComplex()); }
 __global__ __launch_bounds__(CH_THREADS) void channelizer_cf32_kernel(const ChArgs a) { ch_body<float2>(a, ChStoreComplex()); }
+__global__ __launch_bounds__(CH_THREADS) void channelizer_real_s16_kernel(const ChArgs a) { ch_body<short>(a, ChStoreComplex()); }
+__global__ __launch_bounds__(CH_THREADS) void channelizer_real_f32_kernel(const ChArgs a) { ch_body<float>(a, ChStoreComplex()); }
+
+using ChKernel = void (*)(const ChArgs);
+constexpr ChKernel CH_KERNELS[2][2] = {{channelizer_cs16_kernel, channelizer_cf32_kernel}, {channelizer_real_s16_kernel, channelizer_real_f32_kernel}};
+constexpr const char *CH_NAMES[2][2] = {{"channelizer_cs16_kernel", "channelizer_cf32_kernel"}, {"channelizer_real_s16_kernel", "channelizer_real_f32_kernel"}};
 
 }  // namespace
 
 struct sdrhip_channelizer : ChPlan {
+  ChKernel kernel() const { return CH_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
   size_t lds_bytes() const { return (size_t)T * (size_t)ld * sizeof(float2); }
   // n >= 1
   void launch(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) {
@@ -48,29 +58,42 @@ struct sdrhip_channelizer : ChPlan {
     const dim3 grid((unsigned)std::max(a.tiles, 1)), block(CH_THREADS);
     const size_t lds = lds_bytes();
     (void)hipGetLastError();
-    if (dtype == SDRHIP_CHAN_CS16) hipLaunchKernelGGL(channelizer_cs16_kernel, grid, block, lds, ctx->stream, a);
-    else hipLaunchKernelGGL(channelizer_cf32_kernel, grid, block, lds, ctx->stream, a);
+    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a);
     SDRHIP_CHECK_HIP(hipGetLastError());
     advance(n);
   }
 };
 
-extern "C" {
+namespace {
 
-int sdrhip_channelizer_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in,
-                              sdrhip_channelizer **out) {
+// both create calls; real: sdrhip_chanreal.h's
+int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, sdrhip_channelizer **out, bool real) {
   return guarded([&] {
     if (out) *out = nullptr;
     SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
     std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32);
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
     require_device_for_null_ctx(ctx);
     make_handle(ctx, out, true, [&](sdrhip_channelizer *h) {
-      h->build(ctx, dtype, M, D, h32, max_in);
-      allow_lds_max(dtype == SDRHIP_CHAN_CS16 ? channelizer_cs16_kernel : channelizer_cf32_kernel, h->lds_bytes());
+      h->build(ctx, dtype, M, D, h32, max_in, real);
+      allow_lds_max(h->kernel(), h->lds_bytes());
       h->fresh_tail();
     });
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdrhip_channelizer_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in,
+                              sdrhip_channelizer **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, out, false);
+}
+
+int sdrhip_chanreal_channelizer_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in,
+                                   sdrhip_channelizer **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, out, true);
 }
 
 int sdrhip_channelizer_out_count(sdrhip_channelizer *h, size_t n, size_t *n_out) {
@@ -153,7 +176,7 @@ int sdrhip_channelizer_plan_info(sdrhip_channelizer *h, int *tile_times, int *br
 
 int sdrhip_channelizer_kernel_names(sdrhip_channelizer *h, char *buf, size_t len) {
   return guarded([&] {
-    write_names(h, buf, len, [&] { return h->dtype == SDRHIP_CHAN_CS16 ? "channelizer_cs16_kernel" : "channelizer_cf32_kernel"; });
+    write_names(h, buf, len, [&] { return CH_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
   });
 }
 

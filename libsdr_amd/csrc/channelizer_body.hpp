@@ -21,6 +21,13 @@
 // agree bit for bit on the spectra.
 // The input is read at [0, n) and the tail at [0, n_taps - 1) only: the first output time of a call is not before its first
 // sample, the last not behind its last, and terms at l >= n_taps are skipped.
+//
+// The real-input form (sdrhip_chanreal.h; I = short or float, ChIn<I>::real) is ch_tile_real: the same three phases with a real
+// branch sum (one fma per term, a float tail), the sum packed as component jw & 1 of element jw >> 1 of an M / 2-point image,
+// the M / 2-point plan's passes, and between phases 2 and 3 the untangling pass ch_untangle that leaves the M / 2 + 1 distinct
+// channels at img[tt ld + k], natural order — what the epilogue policies read. A policy is handed the arguments with M replaced
+// by the channels an image holds, M / 2 + 1 (ch_epi_args), so its per-channel loops and strides need no second form. The complex
+// instances see none of this: ChArgs is what it was, and they take the `else` of every `if constexpr`.
 #pragma once
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
@@ -29,12 +36,13 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace sdrhip {
 
 constexpr int CH_THREADS = fftgen::GT, CH_TMAX = 256;
-constexpr int CH_M_MIN = 2, CH_M_MAX = 4096, CH_BRANCH_MAX = 64;
+constexpr int CH_M_MIN = 2, CH_M_MIN_REAL = 4, CH_M_MAX = 4096, CH_BRANCH_MAX = 64;
 constexpr int CH_ELEMS_SMALL = 4096, CH_ELEMS_LARGE = 8192, CH_M_SMALL = 512;   // complex elements of LDS a workgroup's T images take
 
 struct ChArgs {
@@ -43,7 +51,8 @@ struct ChArgs {
   const float2 *hist;      // [HH] the tail before the call, oldest first
   float2 *hist_new;        // [HH] the tail behind it
   const float *taps;       // [n_taps]
-  const int *invperm;      // [M] natural index -> position in inverse_dit's input
+  const int *invperm;      // [M] natural index -> position in inverse_dit's input (a real row: [M / 2], and behind them, at
+                           // the next even index, the untangling pass's roots exp(+2 pi i k / M) as [M / 4 + 1] float2)
   const int *sel;          // [n_sel]
   void *out;               // rows of the policy's element type
   long out_stride;
@@ -54,6 +63,13 @@ struct ChArgs {
 
 __device__ __forceinline__ float2 ch_sample(const short2 *p, int i) { const short2 v = p[i]; return make_float2((float)v.x, (float)v.y); }
 __device__ __forceinline__ float2 ch_sample(const float2 *p, int i) { return p[i]; }
+__device__ __forceinline__ float ch_sample(const short *p, int i) { return (float)p[i]; }
+__device__ __forceinline__ float ch_sample(const float *p, int i) { return p[i]; }
+
+// the input element decides the form: which tile body runs, and whether the tail is complex or real floats
+template <class I> struct ChIn { static constexpr bool real = false; };
+template <> struct ChIn<short> { static constexpr bool real = true; };
+template <> struct ChIn<float> { static constexpr bool real = true; };
 
 // one backward DIT pass of radix R over nimg images ld apart: pass_dit's arithmetic, the lane loop over (image, butterfly)
 template <int R>
@@ -79,7 +95,9 @@ __device__ __forceinline__ void ch_roll_tail(const ChArgs &a, int tid) {
   const I *in = static_cast<const I *>(a.in);
   for (int k = (int)blockIdx.x * CH_THREADS + tid; k < a.HH; k += (int)gridDim.x * CH_THREADS) {
     const int q = a.n + k;   // n < 2^30, HH < 2^18
-    a.hist_new[k] = q < a.HH ? a.hist[q] : ch_sample(in, q - a.HH);
+    if constexpr (ChIn<I>::real)   // (a real row's tail: the floats at the head of the same buffers)
+      reinterpret_cast<float *>(a.hist_new)[k] = q < a.HH ? reinterpret_cast<const float *>(a.hist)[q] : ch_sample(in, q - a.HH);
+    else a.hist_new[k] = q < a.HH ? a.hist[q] : ch_sample(in, q - a.HH);
   }
 }
 
@@ -130,6 +148,91 @@ __device__ __forceinline__ void ch_tile(const ChArgs &a, const E &epi, int tile,
   epi.store(a, img, j0, Tc, halo, tid);
 }
 
+// the untangling pass over Ti images of the H-point transforms Z of z[j] = w[2 j] + i w[2 j + 1], H = M / 2: lane (tt, k),
+// k in [0, H / 2], takes the pair (k, kp = (H - k) mod H) in place, with a = Z[k], b = Z[kp], (c, s) = untw[k], in float32 and in
+// this order (sdrhip_chanreal.h states it):
+//     er = 0.5 (a.x + b.x)   ei = 0.5 (a.y - b.y)         E[k] = (Z[k] + conj Z[kp]) / 2
+//     qr = 0.5 (a.y + b.y)   qi = 0.5 (b.x - a.x)         O[k] = (Z[k] - conj Z[kp]) / (2 i)
+//     pr = fma(c, qr, -(s qi))   pi = fma(c, qi, s qr)    exp(+2 pi i k / M) O[k]
+//     slot k  = (er + pr, ei + pi)
+//     slot kp = (er - pr, pi - ei)     where kp != k; the lane of k = 0 writes it to slot H (y_H = Re E[0] - Re O[0])
+// Slot H lies behind the transform's H elements, and no other lane reads or writes the pair's slots.
+__device__ __forceinline__ void ch_untangle(const ChArgs &a, float2 *img, int Ti, int tid) {
+  const int H = a.M >> 1, per = (H >> 1) + 1;
+  const float2 *untw = reinterpret_cast<const float2 *>(a.invperm + ((H + 1) & ~1));
+  for (int i = tid; i < Ti * per; i += CH_THREADS) {
+    const int tt = i / per, k = i - tt * per, kp = k ? H - k : 0;
+    float2 *z = img + tt * a.ld;
+    const float2 va = z[k], vb = z[kp], w = untw[k];
+    const float er = 0.5f * (va.x + vb.x), ei = 0.5f * (va.y - vb.y);
+    const float qr = 0.5f * (va.y + vb.y), qi = 0.5f * (vb.x - va.x);
+    const float pr = __builtin_fmaf(w.x, qr, -(w.y * qi)), pi = __builtin_fmaf(w.x, qi, w.y * qr);
+    z[k] = make_float2(er + pr, ei + pi);
+    if (kp != k || k == 0) z[k ? kp : H] = make_float2(er - pr, pi - ei);
+  }
+}
+
+// the arguments an epilogue policy of a real row sees: M is the channels an image holds
+__device__ __forceinline__ ChArgs ch_epi_args(const ChArgs &a) {
+  ChArgs e = a;
+  e.M = (a.M >> 1) + 1;
+  return e;
+}
+
+// ch_tile for a row of real samples: a.M is the definition's M, a.fft and a.invperm are the M / 2-point plan's, an image has
+// M / 2 + 1 elements of a.ld
+template <class I, class E>
+__device__ __forceinline__ void ch_tile_real(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
+  const int M = a.M;
+  const I *in = static_cast<const I *>(a.in);
+  const float *hist = reinterpret_cast<const float *>(a.hist);
+  float *imgf = reinterpret_cast<float *>(img);
+  const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
+  for (int tt = tid; tt < Ti; tt += CH_THREADS) {
+    const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
+    tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
+    rel_s[tt] = a.lead + (int)jd;
+  }
+  __syncthreads();
+  // phase 1
+  for (int e = tid; e < Ti * M; e += CH_THREADS) {
+    const int tt = e / M, r = e - tt * M;
+    int rel = rel_s[tt] - r;
+    float u = 0.f;
+#pragma unroll 4
+    for (int l = r; l < a.n_taps; l += M, rel -= M) {
+      // (the clamps never bind, as in ch_tile)
+      const float v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : hist[max(a.HH + rel, 0)];
+      u = __builtin_fmaf(a.taps[l], v, u);
+    }
+    int jw = r - tmod_s[tt];
+    jw += jw < 0 ? M : 0;
+    imgf[2 * (tt * a.ld + a.invperm[jw >> 1]) + (jw & 1)] = u;
+  }
+  __syncthreads();
+  // phase 2
+  int s = 1;
+  for (int pass = a.fft.npass - 1; pass >= 0; pass--) {
+    const int r = a.fft.radix[pass];
+#define SDRHIP_CH_CALL(R_) ch_pass<R_>(img, a.fft, s, Ti, a.ld, tid)
+    SDRHIP_GEN_RADIX_SWITCH(r, SDRHIP_CH_CALL)
+#undef SDRHIP_CH_CALL
+    __syncthreads();
+    s *= r;
+  }
+  ch_untangle(a, img, Ti, tid);
+  __syncthreads();
+  // phase 3
+  epi.store(ch_epi_args(a), img, j0, Tc, halo, tid);
+}
+
+// the tile body of the input type
+template <class I, class E>
+__device__ __forceinline__ void ch_tile_any(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
+  if constexpr (ChIn<I>::real) ch_tile_real<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+  else ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+}
+
 // one tile per workgroup: tile blockIdx.x
 template <class I, class E>
 __device__ __forceinline__ void ch_body(const ChArgs &a, const E &epi) {
@@ -137,8 +240,9 @@ __device__ __forceinline__ void ch_body(const ChArgs &a, const E &epi) {
   float2 *img = reinterpret_cast<float2 *>(smem_raw);
   __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
   const int tid = (int)threadIdx.x, tile = (int)blockIdx.x;
-  if (tile < a.tiles) ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  epi.template roll<I>(a, tid);
+  if (tile < a.tiles) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
+  else epi.template roll<I>(a, tid);
 }
 
 // a bounded grid: workgroup b takes the tiles b, b + gridDim.x, ... in that order
@@ -148,20 +252,30 @@ __device__ __forceinline__ void ch_body_strided(const ChArgs &a, const E &epi) {
   float2 *img = reinterpret_cast<float2 *>(smem_raw);
   __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
   const int tid = (int)threadIdx.x;
-  for (int tile = (int)blockIdx.x; tile < a.tiles; tile += (int)gridDim.x) ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  epi.template roll<I>(a, tid);
+  for (int tile = (int)blockIdx.x; tile < a.tiles; tile += (int)gridDim.x) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
+  else epi.template roll<I>(a, tid);
 }
 
 // ---- host side: what both handle types hold and do ---------------------------------------------------------------------------
 // the argument rules of create, in the header's order (before the context: host rules); h32: the taps rounded once to float32
-static inline void ch_require_args(int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, std::vector<float> &h32) {
+// (real: the rules of sdrhip_chanreal.h — the type codes have the complex ones' values, M is even and at least 4, and the
+// transform is M / 2 points long)
+static inline void ch_require_args(int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, std::vector<float> &h32,
+                                   bool real = false) {
   SDRHIP_REQUIRE(dtype == SDRHIP_CHAN_CS16 || dtype == SDRHIP_CHAN_CF32, SDRHIP_E_INVALID, "bad dtype %d", dtype);
-  SDRHIP_REQUIRE(M >= CH_M_MIN && M <= CH_M_MAX, SDRHIP_E_SIZE, "M %d outside [%d,%d] (one transform lives in one workgroup's LDS)", M,
-                 CH_M_MIN, CH_M_MAX);
+  const int m_min = real ? CH_M_MIN_REAL : CH_M_MIN;
+  SDRHIP_REQUIRE(M >= m_min && M <= CH_M_MAX, SDRHIP_E_SIZE, "M %d outside [%d,%d] (one transform lives in one workgroup's LDS)", M,
+                 m_min, CH_M_MAX);
   std::vector<int> radix;
   int bad = 1;
-  SDRHIP_REQUIRE(fftgen::GenPlan<float2>::factor(M, radix, &bad), SDRHIP_E_INVALID,
-                 "M %d has the prime factor %d: the device transforms sizes made of 2, 3, 5, 7, 11 and 13", M, bad);
+  if (real) {
+    SDRHIP_REQUIRE(M % 2 == 0, SDRHIP_E_INVALID, "M %d is odd: a real row's transform is M / 2 points long", M);
+    SDRHIP_REQUIRE(fftgen::GenPlan<float2>::factor(M / 2, radix, &bad), SDRHIP_E_INVALID,
+                   "M / 2 = %d has the prime factor %d: the device transforms sizes made of 2, 3, 5, 7, 11 and 13", M / 2, bad);
+  } else
+    SDRHIP_REQUIRE(fftgen::GenPlan<float2>::factor(M, radix, &bad), SDRHIP_E_INVALID,
+                   "M %d has the prime factor %d: the device transforms sizes made of 2, 3, 5, 7, 11 and 13", M, bad);
   SDRHIP_REQUIRE(D >= 1 && D <= M, SDRHIP_E_INVALID, "D %d outside [1,M = %d]", D, M);
   SDRHIP_REQUIRE(n_taps >= 1 && n_taps <= CH_BRANCH_MAX * M, SDRHIP_E_SIZE, "n_taps %d outside [1,%d M = %d]", n_taps, CH_BRANCH_MAX,
                  CH_BRANCH_MAX * M);
@@ -176,6 +290,8 @@ static inline void ch_require_args(int dtype, int M, int D, const double *taps, 
 struct ChPlan {
   sdrhip_ctx *ctx = nullptr;
   int dtype = SDRHIP_CHAN_CS16, M = 2, D = 1, n_taps = 1, T = 1, ld = 3, n_sel = 2;
+  bool real = false;               // a row of real samples in (sdrhip_chanreal.h): the plan is M / 2 points long
+  int nch = 2;                     // the channels: M, or M / 2 + 1 of a real row
   size_t max_in = 0;
   uint64_t consumed = 0;
   int cur = 0;                     // which tail buffer holds the state
@@ -183,40 +299,54 @@ struct ChPlan {
   DevBuf<float> taps;
   DevBuf<int> invperm, sel;
   std::vector<int> sel_host;       // [n_sel]
-  DevBuf<float2> hist[2];          // [n_taps - 1] each (at least one element)
+  DevBuf<float2> hist[2];          // [n_taps - 1] each (at least one element); a real row's tail is the floats at their head
   Staging stage;
-  size_t in_elem() const { return dtype == SDRHIP_CHAN_CS16 ? 4 : 8; }
+  size_t in_elem() const { return (dtype == SDRHIP_CHAN_CS16 ? 4 : 8) / (real ? 2 : 1); }
+  const char *nch_name() const { return real ? "K" : "M"; }
   int HH() const { return n_taps - 1; }
   size_t out_count(size_t n) const { return (size_t)((consumed + n) / (uint64_t)D - consumed / (uint64_t)D); }
   size_t out_count_max(size_t n) const { return ceil_div(n, (size_t)D); }   // whatever N is
 
   // inside make_handle, behind ch_require_args; the caller ends with allow_lds_max and its fresh state
-  void build(sdrhip_ctx *c, int dtype_, int M_, int D_, const std::vector<float> &h32, size_t max_in_) {
-    dtype = dtype_; M = M_; D = D_; n_taps = (int)h32.size(); max_in = max_in_;
+  // A real row's plan (sdrhip_chanreal.h states the rule): the transform is L = M / 2 points long, an image holds the L + 1
+  // channels at ld = (L + 1) | 1 elements — odd, so that consecutive images start two banks apart as the complex form's do —
+  // and T is the complex form's: as many workgroups per call, each with half the LDS (twice the tile times in the same LDS
+  // halve the workgroups of a call: a 2^21-sample call at M = 1024 then fills half the device and takes 1.6x as long).
+  void build(sdrhip_ctx *c, int dtype_, int M_, int D_, const std::vector<float> &h32, size_t max_in_, bool real_ = false) {
+    dtype = dtype_; M = M_; D = D_; n_taps = (int)h32.size(); max_in = max_in_; real = real_;
+    const int L = real ? M / 2 : M;
+    nch = real ? L + 1 : M;
     T = std::min(CH_TMAX, (M <= CH_M_SMALL ? CH_ELEMS_SMALL : CH_ELEMS_LARGE) / M);
-    ld = M + 1;
-    plan.build(c, M, CH_M_MAX);
-    std::vector<int> inv((size_t)M);
-    for (int pos = 0; pos < M; pos++) inv[(size_t)plan.perm[pos]] = pos;
-    invperm.alloc((size_t)M);
+    ld = real ? ((L + 1) | 1) : M + 1;
+    plan.build(c, L, CH_M_MAX);
+    // (a real row: the untangling pass's roots ride behind the permutation, at the next even index — ChArgs stays what it was)
+    const size_t at = ((size_t)L + 1) & ~(size_t)1;
+    std::vector<int> inv(real ? at + 2 * (size_t)(M / 4 + 1) : (size_t)L, 0);
+    for (int pos = 0; pos < L; pos++) inv[(size_t)plan.perm[pos]] = pos;
+    for (int k = 0; real && k <= M / 4; k++) {
+      const double ph = 2.0 * 3.14159265358979323846 * (double)k / (double)M;
+      const float w[2] = {(float)std::cos(ph), (float)std::sin(ph)};
+      memcpy(&inv[at + 2 * (size_t)k], w, sizeof w);
+    }
+    invperm.alloc(inv.size());
     invperm.upload(inv.data(), inv.size(), c->stream);
     taps.alloc((size_t)n_taps);
     taps.upload(h32.data(), h32.size(), c->stream);
-    sel.alloc((size_t)M);
+    sel.alloc((size_t)nch);
     select(nullptr, 0);
     for (auto &b : hist) { b.alloc((size_t)std::max(HH(), 1)); b.zero(c->stream); }
   }
-  // set_channels: idx = NULL selects all M in order; a bad selection changes nothing
+  // set_channels: idx = NULL selects all nch in order; a bad selection changes nothing
   void select(const int *idx, int n) {
     std::vector<int> s;
     if (!idx) {
-      s.resize((size_t)M);
-      for (int k = 0; k < M; k++) s[(size_t)k] = k;
+      s.resize((size_t)nch);
+      for (int k = 0; k < nch; k++) s[(size_t)k] = k;
     } else {
-      SDRHIP_REQUIRE(n >= 1 && n <= M, SDRHIP_E_INVALID, "n_sel %d outside [1,M = %d]", n, M);
-      std::vector<char> seen((size_t)M, 0);
+      SDRHIP_REQUIRE(n >= 1 && n <= nch, SDRHIP_E_INVALID, "n_sel %d outside [1,%s = %d]", n, nch_name(), nch);
+      std::vector<char> seen((size_t)nch, 0);
       for (int i = 0; i < n; i++) {
-        SDRHIP_REQUIRE(idx[i] >= 0 && idx[i] < M, SDRHIP_E_INVALID, "channel %d (row %d) outside [0,%d)", idx[i], i, M);
+        SDRHIP_REQUIRE(idx[i] >= 0 && idx[i] < nch, SDRHIP_E_INVALID, "channel %d (row %d) outside [0,%d)", idx[i], i, nch);
         SDRHIP_REQUIRE(!seen[(size_t)idx[i]], SDRHIP_E_INVALID, "channel %d is selected twice (row %d)", idx[i], i);
         seen[(size_t)idx[i]] = 1;
       }
@@ -241,7 +371,12 @@ struct ChPlan {
   }
   void get_tail(uint64_t *consumed_out, float *tail, size_t tail_len) {
     SDRHIP_REQUIRE(!tail || tail_len >= (size_t)HH(), SDRHIP_E_SIZE, "tail_len %zu < n_taps - 1 = %d", tail_len, HH());
-    if (tail && HH() > 0) get_sync(ctx, tail, hist[cur].p, (size_t)HH() * sizeof(float2));
+    if (tail && HH() > 0 && !real) get_sync(ctx, tail, hist[cur].p, (size_t)HH() * sizeof(float2));
+    if (tail && HH() > 0 && real) {   // (re, 0) pairs: one layout for the callers
+      std::vector<float> re((size_t)HH());
+      get_sync(ctx, re.data(), hist[cur].p, re.size() * sizeof(float));
+      for (int i = 0; i < HH(); i++) { tail[2 * i] = re[(size_t)i]; tail[2 * i + 1] = 0.f; }
+    }
     if (consumed_out) *consumed_out = consumed;
   }
   // the arguments of a launch of n >= 1 samples from the current state; the grid is max(tiles, 1) blocks of CH_THREADS

@@ -9,8 +9,12 @@
 // The grid is bounded (ch_body_strided: workgroup b takes the tiles b, b + W, ...), so the partial buffer is. The finish kernel
 // runs behind the launch on the same stream, one lane per channel: the rows of the workgroups that ran, added in row order, the
 // call's sum where asked for, and the level and flag update; calls, J and alpha come from the host as arguments.
+// A handle of sdrhip_chanreal_power_create (sdrhip_chanreal.h) runs chanpower_real_s16_kernel / chanpower_real_f32_kernel: the body's real
+// form in front of the same epilogue; the partial buffer, the finish launch and every per-channel array then take nch = M / 2 + 1
+// channels.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanpower.h"
+#include "sdrhip_chanreal.h"
 #include "entry.hpp"
 #include "channelizer_body.hpp"
 
@@ -22,10 +26,11 @@ using namespace sdrhip;
 
 namespace {
 
-constexpr int CP_GRID_PER_CU = 2;   // (an M = 1024 workgroup's images take 64 KiB of the CU's 160)
+constexpr int CP_GRID_PER_CU = 2;   // (an M = 1024 workgroup's images take 64 KiB of the CU's 160; a real handle's take 32 KiB, and
+                                    // its grid is kept at the same two per CU: the partial buffer and the finish launch grow with it)
 constexpr int CP_BATCH = 32;        // partial rows the finish kernel has in flight per lane
 
-// no rows out, no image before the tile; `partial` is [gridDim.x][M]
+// no rows out, no image before the tile; `partial` is [gridDim.x][nch]
 struct ChStorePower {
   double *partial;
   __device__ __forceinline__ int halo(const ChArgs &, int) const { return 0; }
@@ -53,6 +58,17 @@ __global__ __launch_bounds__(CH_THREADS) void chanpower_cs16_kernel(const ChArgs
 __global__ __launch_bounds__(CH_THREADS) void chanpower_cf32_kernel(const ChArgs a, double *partial) {
   ch_body_strided<float2>(a, ChStorePower{partial});
 }
+__global__ __launch_bounds__(CH_THREADS) void chanpower_real_s16_kernel(const ChArgs a, double *partial) {
+  ch_body_strided<short>(a, ChStorePower{partial});
+}
+__global__ __launch_bounds__(CH_THREADS) void chanpower_real_f32_kernel(const ChArgs a, double *partial) {
+  ch_body_strided<float>(a, ChStorePower{partial});
+}
+
+using CpKernel = void (*)(const ChArgs, double *);
+constexpr CpKernel CP_KERNELS[2][2] = {{chanpower_cs16_kernel, chanpower_cf32_kernel}, {chanpower_real_s16_kernel, chanpower_real_f32_kernel}};
+constexpr const char *CP_NAMES[2][2] = {{"chanpower_cs16_kernel,chanpower_finish_kernel", "chanpower_cf32_kernel,chanpower_finish_kernel"},
+                                        {"chanpower_real_s16_kernel,chanpower_finish_kernel", "chanpower_real_f32_kernel,chanpower_finish_kernel"}};
 
 struct CpFinishArgs {
   const double *partial;            // [rows][M]
@@ -61,7 +77,7 @@ struct CpFinishArgs {
   unsigned char *open;              // [M]
   double *sum;                      // [M] or NULL
   double alpha;
-  int M, rows, J, first;            // rows: the workgroups that ran (0 where J = 0); first: calls == 0
+  int M, rows, J, first;            // M: the handle's channels (nch); rows: the workgroups that ran (0 where J = 0); first: calls == 0
 };
 
 __global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFinishArgs f) {
@@ -97,12 +113,13 @@ struct sdrhip_chanpower : ChPlan {
   double alpha = 1.0;
   uint64_t calls = 0;
   int G = 1;                                   // the workgroups of a launch at most
-  DevBuf<double> partial, level, thr_open, thr_close;   // [G][M], [M], [M], [M]
-  DevBuf<unsigned char> open;                  // [M]
+  DevBuf<double> partial, level, thr_open, thr_close;   // [G][nch], [nch], [nch], [nch]
+  DevBuf<unsigned char> open;                  // [nch]
+  CpKernel kernel() const { return CP_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
   size_t lds_bytes() const { return (size_t)T * (size_t)ld * sizeof(float2); }
   void fresh_state() {
-    SDRHIP_CHECK_HIP(hipMemsetAsync(level.p, 0, (size_t)M * sizeof(double), ctx->stream));
-    SDRHIP_CHECK_HIP(hipMemsetAsync(open.p, 0, (size_t)M, ctx->stream));
+    SDRHIP_CHECK_HIP(hipMemsetAsync(level.p, 0, (size_t)nch * sizeof(double), ctx->stream));
+    SDRHIP_CHECK_HIP(hipMemsetAsync(open.p, 0, (size_t)nch, ctx->stream));
     fresh_tail();   // (synchronises)
     calls = 0;
   }
@@ -114,52 +131,67 @@ struct sdrhip_chanpower : ChPlan {
     const dim3 grid((unsigned)std::max(rows, 1)), block(CH_THREADS);
     const size_t lds = lds_bytes();
     (void)hipGetLastError();
-    if (dtype == SDRHIP_CHAN_CS16) hipLaunchKernelGGL(chanpower_cs16_kernel, grid, block, lds, ctx->stream, a, partial.p);
-    else hipLaunchKernelGGL(chanpower_cf32_kernel, grid, block, lds, ctx->stream, a, partial.p);
+    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a, partial.p);
     SDRHIP_CHECK_HIP(hipGetLastError());
     advance(n);
     if (n_out == 0 && !sum_dev) return;
     CpFinishArgs f;
     f.partial = partial.p; f.open_thr = thr_open.p; f.close_thr = thr_close.p; f.level = level.p; f.open = open.p; f.sum = sum_dev;
-    f.alpha = alpha; f.M = M; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
-    hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)M, (size_t)CH_THREADS)), block, 0, ctx->stream, f);
+    f.alpha = alpha; f.M = nch; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
+    hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)nch, (size_t)CH_THREADS)), block, 0, ctx->stream, f);
     SDRHIP_CHECK_HIP(hipGetLastError());
     if (n_out) calls++;
   }
 };
 
-extern "C" {
+namespace {
 
-int sdrhip_chanpower_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha,
-                            sdrhip_chanpower **out) {
+// both create calls; real: sdrhip_chanreal.h's
+int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha, sdrhip_chanpower **out,
+           bool real) {
   return guarded([&] {
     if (out) *out = nullptr;
     SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
     std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32);
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
     require_alpha(alpha);
     require_device_for_null_ctx(ctx);
     make_handle(ctx, out, true, [&](sdrhip_chanpower *h) {
-      h->build(ctx, dtype, M, D, h32, max_in);
+      h->build(ctx, dtype, M, D, h32, max_in, real);
+      const size_t K = (size_t)h->nch;
       h->alpha = alpha;
       const char *e = getenv("SDRHIP_CHANPOWER_GRID");   // read once: the partial buffer is allocated for it
       h->G = std::max(1, CP_GRID_PER_CU * ctx->prop.multiProcessorCount);
       if (e && atoi(e) >= 1) h->G = std::min(h->G, atoi(e));
       // (no call has more tiles than max_in gives)
       h->G = (int)std::min((size_t)h->G, std::max(ceil_div(h->out_count_max(max_in), (size_t)h->T), (size_t)1));
-      h->partial.alloc((size_t)h->G * (size_t)M);
-      h->level.alloc((size_t)M);
-      h->open.alloc((size_t)M);
-      std::vector<double> inf((size_t)M, HUGE_VAL), zero((size_t)M, 0.0);
-      h->thr_open.alloc((size_t)M);
+      h->partial.alloc((size_t)h->G * K);
+      h->level.alloc(K);
+      h->open.alloc(K);
+      std::vector<double> inf(K, HUGE_VAL), zero(K, 0.0);
+      h->thr_open.alloc(K);
       h->thr_open.upload(inf.data(), inf.size(), ctx->stream);
-      h->thr_close.alloc((size_t)M);
+      h->thr_close.alloc(K);
       h->thr_close.upload(zero.data(), zero.size(), ctx->stream);
       SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // (the uploads read locals)
-      allow_lds_max(dtype == SDRHIP_CHAN_CS16 ? chanpower_cs16_kernel : chanpower_cf32_kernel, h->lds_bytes());
+      allow_lds_max(h->kernel(), h->lds_bytes());
       h->fresh_state();
     });
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdrhip_chanpower_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha,
+                            sdrhip_chanpower **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, alpha, out, false);
+}
+
+int sdrhip_chanreal_power_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha,
+                                 sdrhip_chanpower **out) {
+  return create(ctx, dtype, M, D, taps, n_taps, max_in, alpha, out, true);
 }
 
 int sdrhip_chanpower_out_count(sdrhip_chanpower *h, size_t n, size_t *n_out) {
@@ -175,7 +207,7 @@ int sdrhip_chanpower_process_dev(sdrhip_chanpower *h, const void *in_dev, size_t
     if (n_out) *n_out = 0;
     if (!call_begin(h, "n", n, in_dev, sum_dev ? (const void *)sum_dev : in_dev)) return;   // (the sums are optional)
     const size_t no = h->out_count(n);
-    if (sum_dev) require_disjoint(in_dev, n, n, h->in_elem(), sum_dev, (size_t)h->M, (size_t)h->M, sizeof(double), 1);
+    if (sum_dev) require_disjoint(in_dev, n, n, h->in_elem(), sum_dev, (size_t)h->nch, (size_t)h->nch, sizeof(double), 1);
     h->launch(in_dev, n, sum_dev, no);
     if (n_out) *n_out = no;
   });
@@ -186,7 +218,7 @@ int sdrhip_chanpower_process(sdrhip_chanpower *h, const void *in_host, size_t n,
     Range roctx_range("sdrhip_chanpower_process");
     if (n_out) *n_out = 0;
     if (!call_begin(h, "n", n, in_host, sum_host)) return;
-    const size_t no = h->out_count(n), eb = h->in_elem(), row_b = (size_t)h->M * sizeof(double);
+    const size_t no = h->out_count(n), eb = h->in_elem(), row_b = (size_t)h->nch * sizeof(double);
     run_staged(h->ctx, h->stage, h->max_in * eb, row_b, {in_host, n * eb, n * eb, 1}, {sum_host, row_b, row_b, 1},
                [&](void *in, void *out) {
                  h->launch(in, n, static_cast<double *>(out), no);
@@ -199,12 +231,12 @@ int sdrhip_chanpower_process(sdrhip_chanpower *h, const void *in_host, size_t n,
 int sdrhip_chanpower_set_thresholds(sdrhip_chanpower *h, const double *open_thr, const double *close_thr) {
   return guarded([&] {
     SDRHIP_REQUIRE(h && open_thr && close_thr, SDRHIP_E_INVALID, "NULL argument");
-    for (int k = 0; k < h->M; k++)   // (a NaN fails the comparison it meets)
+    for (int k = 0; k < h->nch; k++)   // (a NaN fails the comparison it meets)
       SDRHIP_REQUIRE(close_thr[k] >= 0.0 && close_thr[k] <= open_thr[k], SDRHIP_E_INVALID,
                      "thresholds of channel %d: 0 <= close_thr %g <= open_thr %g does not hold", k, close_thr[k], open_thr[k]);
     h->ctx->use();
     hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued; both or none is not promised on a failing device
-    const size_t b = (size_t)h->M * sizeof(double);
+    const size_t b = (size_t)h->nch * sizeof(double);
     const hipError_t e1 = hipMemcpyAsync(h->thr_open.p, open_thr, b, hipMemcpyHostToDevice, st);
     const hipError_t e2 = hipMemcpyAsync(h->thr_close.p, close_thr, b, hipMemcpyHostToDevice, st);
     const hipError_t e3 = hipStreamSynchronize(st);
@@ -240,9 +272,9 @@ int sdrhip_chanpower_reset(sdrhip_chanpower *h) {
 int sdrhip_chanpower_get_levels(sdrhip_chanpower *h, double *level, unsigned char *open, int len) {
   return guarded([&] {
     use_handle(h);
-    SDRHIP_REQUIRE(len >= h->M, SDRHIP_E_SIZE, "len %d < M = %d", len, h->M);
-    if (level) get_sync(h->ctx, level, h->level.p, (size_t)h->M * sizeof(double));
-    if (open) get_sync(h->ctx, open, h->open.p, (size_t)h->M);
+    SDRHIP_REQUIRE(len >= h->nch, SDRHIP_E_SIZE, "len %d < %s = %d", len, h->nch_name(), h->nch);
+    if (level) get_sync(h->ctx, level, h->level.p, (size_t)h->nch * sizeof(double));
+    if (open) get_sync(h->ctx, open, h->open.p, (size_t)h->nch);
   });
 }
 
@@ -250,10 +282,10 @@ int sdrhip_chanpower_get_occupied(sdrhip_chanpower *h, int *idx, int cap, int *c
   return guarded([&] {
     use_handle(h);
     SDRHIP_REQUIRE(count && (idx || cap <= 0), SDRHIP_E_INVALID, "NULL argument");
-    std::vector<unsigned char> open((size_t)h->M);
+    std::vector<unsigned char> open((size_t)h->nch);
     get_sync(h->ctx, open.data(), h->open.p, open.size());
     int n = 0;
-    for (int k = 0; k < h->M; k++)
+    for (int k = 0; k < h->nch; k++)
       if (open[(size_t)k]) {
         if (n < cap) idx[n] = k;
         n++;
@@ -283,9 +315,7 @@ int sdrhip_chanpower_plan_info(sdrhip_chanpower *h, int *tile_times, int *branch
 
 int sdrhip_chanpower_kernel_names(sdrhip_chanpower *h, char *buf, size_t len) {
   return guarded([&] {
-    write_names(h, buf, len, [&] {
-      return h->dtype == SDRHIP_CHAN_CS16 ? "chanpower_cs16_kernel,chanpower_finish_kernel" : "chanpower_cf32_kernel,chanpower_finish_kernel";
-    });
+    write_names(h, buf, len, [&] { return CP_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
   });
 }
 
