@@ -7,8 +7,9 @@
  * Per buffer: one H2D copy, two launches, one D2H copy of M doubles. processDev() runs the same plan on a device row of the node's
  * device and synchronises nothing.
  *
- * The node's body is gpu::ChannelPowerNode<Grid>, as gpu::ChannelizerNode is gpu::Channelizer's: Grid says what the complex node
- * and the real-input one of chanreal.hh (gpu::RealChannelPower<Scalar>) differ in; channels() is the grid's channel count.
+ * The node's body is gpu::ChannelPowerNode<Grid> on detail::ChannelNodeBase (channelizer.hh), which has the M / D / taps rule,
+ * setTaps, reset and consumed: Grid says what the complex node and the real-input one of chanreal.hh
+ * (gpu::RealChannelPower<Scalar>) differ in; channels() is the grid's channel count.
  */
 #ifndef SDR_GPU_CHANPOWER_HH
 #define SDR_GPU_CHANPOWER_HH
@@ -17,6 +18,7 @@
 #include "../../sdrhip_chanpower.h"
 
 #include <cmath>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -24,8 +26,25 @@ namespace sdr {
 namespace gpu {
 
 namespace detail {
+/** What the node bodies call of sdrhip_chanpower.h (no rows: no selection, and process_dev has its own shape). */
+struct ChanPowerApi {
+  typedef sdrhip_chanpower Plan;
+  static int destroy(Plan *p) { return sdrhip_chanpower_destroy(p); }
+  static int setTaps(Plan *p, const double *taps) { return sdrhip_chanpower_set_taps(p, taps); }
+  static int reset(Plan *p) { return sdrhip_chanpower_reset(p); }
+  static int consumed(Plan *p, uint64_t *c) { return sdrhip_chanpower_get_state(p, c, 0, 0, 0); }
+};
+
+/** The alpha clause of the monitor's rule message. */
+inline std::string alphaClause(double alpha) {
+  std::ostringstream s;
+  s << ", alpha = " << alpha << " (in (0, 1])";
+  return s.str();
+}
+
 /** The complex monitor's grid: detail::ComplexGrid with sdrhip_chanpower_create. */
 template <class Scalar> struct ComplexPowerGrid : ComplexGrid<Scalar> {
+  typedef ChanPowerApi Api;
   static const char *name() { return "ChannelPower"; }
   static int create(sdrhip_ctx *ctx, int M, int D, const double *taps, int nTaps, size_t maxIn, double alpha, sdrhip_chanpower **out) {
     return sdrhip_chanpower_create(ctx, ChannelizerType<Scalar>::dtype, M, D, taps, nTaps, maxIn, alpha, out);
@@ -34,26 +53,14 @@ template <class Scalar> struct ComplexPowerGrid : ComplexGrid<Scalar> {
 }  // namespace detail
 
 template <class Grid>
-class ChannelPowerNode : public Sink<typename Grid::In> {
+class ChannelPowerNode : public detail::ChannelNodeBase<Grid> {
 public:
   typedef typename Grid::In In;
 
   /** M, D, taps and alpha as gpu::ChannelPower and gpu::RealChannelPower say; the grid's rules are checked here and throw
    * ConfigError. */
   ChannelPowerNode(size_t M, size_t D, const std::vector<double> &taps, double alpha, int device)
-    : Sink<In>(), _M(M), _K(Grid::admitsM(M) ? Grid::channels(M) : 0), _D(D), _taps(taps), _alpha(alpha), _device(device), _ctx(0), _bs(0),
-      _last(0), _gpuName(std::string("gpu::") + Grid::name()) {
-    size_t rest = Grid::admitsM(M) ? Grid::transform(M) : 0;
-    const size_t primes[] = {2, 3, 5, 7, 11, 13};
-    for (size_t q = 0; q < 6; q++) while (rest > 1 && rest % primes[q] == 0) rest /= primes[q];
-    bool finite = true;
-    for (size_t i = 0; i < taps.size(); i++) finite = finite && std::isfinite(float(taps[i]));
-    if (rest != 1 || D < 1 || D > M || taps.empty() || taps.size() > 64 * M || !finite || !(alpha > 0.0 && alpha <= 1.0)) {
-      ConfigError err;
-      err << "Can not configure " << Grid::name() << " node: M = " << M << Grid::ruleM() << ", D = " << D << " (1 ... M), "
-          << taps.size() << " taps (1 ... 64 M, all finite as floats), alpha = " << alpha << " (in (0, 1])";
-      throw err;
-    }
+    : detail::ChannelNodeBase<Grid>(M, D, taps, device, alpha > 0.0 && alpha <= 1.0, detail::alphaClause(alpha)), _alpha(alpha), _last(0) {
     _open.assign(_K, HUGE_VAL);
     _close.assign(_K, 0.0);
     _sums.assign(_K, 0.0);
@@ -61,7 +68,6 @@ public:
   virtual ~ChannelPowerNode() { _release(); }
 
   size_t channels() const { return _K; }
-  sdrhip_ctx *context() const { return _ctx; }
 
   /** Absolute thresholds in the units of |y|^2, for every channel or per channel: 0 <= close <= open, no NaN (ConfigError). They
    * hold from the next buffer on, and over config(). */
@@ -87,24 +93,8 @@ public:
     if (_plan) detail::configCheck(sdrhip_chanpower_set_alpha(_plan, alpha), Grid::name());
     _alpha = alpha;
   }
-  /** A new prototype of the same length; the stream, the levels and the flags go on. */
-  void setTaps(const std::vector<double> &taps) {
-    if (taps.size() != _taps.size()) {
-      ConfigError err;
-      err << Grid::name() << ": " << taps.size() << " taps where the node has " << _taps.size();
-      throw err;
-    }
-    if (_plan) detail::configCheck(sdrhip_chanpower_set_taps(_plan, taps.data()), Grid::name());
-    _taps = taps;
-  }
-
   virtual void config(const Config &cfg) {
-    if (!cfg.hasType() || !cfg.hasSampleRate() || !cfg.hasBufferSize()) return;
-    detail::checkType<In>(cfg, (std::string(Grid::name()) + " node").c_str());
-    _release();
-    _bs = cfg.bufferSize();
-    if (_bs == 0) return;
-    _ctx = Device::get(_device);
+    if (!this->_begin(cfg)) return;
     detail::configCheck(Grid::create(_ctx, int(_M), int(_D), _taps.data(), int(_taps.size()), _bs, _alpha, _plan.out()), Grid::name());
     detail::configCheck(sdrhip_chanpower_set_thresholds(_plan, _open.data(), _close.data()), Grid::name());
     _din.alloc(_ctx, _bs * sizeof(In), Grid::name());
@@ -149,14 +139,7 @@ public:
     idx.resize(size_t(count));
     return idx;
   }
-  /** As freshly configured, with the current taps, alpha and thresholds. */
-  void reset() { if (_plan) detail::configCheck(sdrhip_chanpower_reset(_plan), Grid::name()); }
-  /** The samples taken, and the buffers that completed an output, since config() or reset(). */
-  uint64_t consumed() const {
-    uint64_t c = 0;
-    if (_plan) detail::configCheck(sdrhip_chanpower_get_state(_plan, &c, 0, 0, 0), Grid::name());
-    return c;
-  }
+  /** The buffers that completed an output since config() or reset(). */
   uint64_t calls() const {
     uint64_t c = 0;
     if (_plan) detail::configCheck(sdrhip_chanpower_get_state(_plan, 0, 0, 0, &c), Grid::name());
@@ -164,23 +147,24 @@ public:
   }
 
 protected:
-  /** In this order: the device is idle before anything it may still use goes. */
-  void _release() {
-    if (_ctx) sdrhip_ctx_synchronize(_ctx);
-    _plan.reset();
-    _din.reset();
+  virtual void _release() {
+    detail::ChannelNodeBase<Grid>::_release();
     _dsum.reset();
   }
 
-  size_t _M, _K, _D;        // _K: the grid's channels
-  std::vector<double> _taps, _open, _close, _sums;
+  using detail::ChannelNodeBase<Grid>::_M;
+  using detail::ChannelNodeBase<Grid>::_K;
+  using detail::ChannelNodeBase<Grid>::_D;
+  using detail::ChannelNodeBase<Grid>::_taps;
+  using detail::ChannelNodeBase<Grid>::_ctx;
+  using detail::ChannelNodeBase<Grid>::_plan;
+  using detail::ChannelNodeBase<Grid>::_din;
+  using detail::ChannelNodeBase<Grid>::_bs;
+  using detail::ChannelNodeBase<Grid>::_gpuName;
+  std::vector<double> _open, _close, _sums;
   double _alpha;
-  int _device;
-  sdrhip_ctx *_ctx;
-  detail::Handle<sdrhip_chanpower, sdrhip_chanpower_destroy> _plan;
-  detail::DeviceMem _din, _dsum;
-  size_t _bs, _last;
-  std::string _gpuName;     // "gpu::<name>", for the log
+  detail::DeviceMem _dsum;
+  size_t _last;
 };
 
 template <class Scalar>

@@ -28,6 +28,7 @@ template <> struct RealChannelizerType<float> { enum { dtype = SDRHIP_CHANREAL_F
 /** The real-input grid: M even, M / 2 + 1 channels of an M / 2-point transform, sdrhip_chanreal_channelizer_create. */
 template <class Scalar> struct RealGrid {
   typedef Scalar In;
+  typedef ChannelizerApi Api;
   static const char *name() { return "RealChannelizer"; }
   static const char *ruleM() { return " (even, 4 ... 4096, M / 2 with prime factors up to 13)"; }
   static bool admitsM(size_t M) { return M >= 4 && M <= 4096 && M % 2 == 0; }
@@ -38,6 +39,7 @@ template <class Scalar> struct RealGrid {
   }
 };
 template <class Scalar> struct RealAudioGrid : RealGrid<Scalar> {
+  typedef ChanAudioApi Api;
   static const char *name() { return "RealAudioChannelizer"; }
   static int create(sdrhip_ctx *ctx, int M, int D, const double *taps, int nTaps, size_t maxIn, const int *modes, const float *gains,
                     sdrhip_chanaudio **out) {
@@ -45,6 +47,7 @@ template <class Scalar> struct RealAudioGrid : RealGrid<Scalar> {
   }
 };
 template <class Scalar> struct RealPowerGrid : RealGrid<Scalar> {
+  typedef ChanPowerApi Api;
   static const char *name() { return "RealChannelPower"; }
   static int create(sdrhip_ctx *ctx, int M, int D, const double *taps, int nTaps, size_t maxIn, double alpha, sdrhip_chanpower **out) {
     return sdrhip_chanreal_power_create(ctx, RealChannelizerType<Scalar>::dtype, M, D, taps, nTaps, maxIn, alpha, out);

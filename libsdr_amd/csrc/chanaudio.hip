@@ -106,7 +106,7 @@ struct sdrhip_chanaudio : ChPlan {
   std::vector<float> gain_host;    // [nch]
   DevBuf<int> mode, last[2];       // [nch] each; last[cur] holds the state (the buffers flip with the tail's)
   DevBuf<float> gain;              // [nch]
-  CaKernel kernel() const { return CA_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
+  CaKernel kernel() const { return pick(CA_KERNELS); }
   size_t lds_bytes() const { return (size_t)(T + 1) * (size_t)ld * sizeof(float2); }
   int fm_rows() const {
     int n = 0;
@@ -125,12 +125,7 @@ struct sdrhip_chanaudio : ChPlan {
     a.c = args(in_dev, n, out_dev, out_stride, n_out);
     a.mode = mode.p; a.gain = gain.p; a.last = last[cur].p; a.last_new = last[cur ^ 1].p;
     a.fm_rows = fm_rows();
-    const dim3 grid((unsigned)std::max(a.c.tiles, 1)), block(CH_THREADS);
-    const size_t lds = lds_bytes();
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a);
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    advance(n);
+    launch_tiles(kernel(), a.c.tiles, lds_bytes(), n, a);
   }
 };
 
@@ -139,29 +134,34 @@ namespace {
 // both create calls; real: sdrhip_chanreal.h's, K = M / 2 + 1 channels (the rules before have made M even)
 int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes, const float *gains,
            sdrhip_chanaudio **out, bool real) {
+  int K = 0;
+  return ch_create(
+      ctx, dtype, M, D, taps, n_taps, max_in, out, real,
+      [&] {
+        K = real ? M / 2 + 1 : M;
+        for (int k = 0; modes && k < K; k++) require_mode(modes[k], "channel", k);
+        for (int k = 0; gains && k < K; k++) require_gain(gains[k], "channel", k);
+      },
+      [&](sdrhip_chanaudio *h) {
+        h->mode_host.assign((size_t)K, SDRHIP_EPI_FM);
+        h->gain_host.assign((size_t)K, 1.0f);
+        if (modes) h->mode_host.assign(modes, modes + K);
+        if (gains) h->gain_host.assign(gains, gains + K);
+        h->mode.alloc((size_t)K);
+        h->mode.upload(h->mode_host.data(), (size_t)K, ctx->stream);
+        h->gain.alloc((size_t)K);
+        h->gain.upload(h->gain_host.data(), (size_t)K, ctx->stream);
+        for (auto &b : h->last) { b.alloc((size_t)K); b.zero(ctx->stream); }
+      });
+}
+
+// get_modes / get_gains: row i's entry of the per-channel host array; short_fmt: the message for an array below n_sel entries
+template <class X>
+int get_rows(sdrhip_chanaudio *h, const std::vector<X> sdrhip_chanaudio::*per_channel, X *rows, int n, const char *short_fmt) {
   return guarded([&] {
-    if (out) *out = nullptr;
-    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
-    std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
-    const int K = real ? M / 2 + 1 : M;
-    for (int k = 0; modes && k < K; k++) require_mode(modes[k], "channel", k);
-    for (int k = 0; gains && k < K; k++) require_gain(gains[k], "channel", k);
-    require_device_for_null_ctx(ctx);
-    make_handle(ctx, out, true, [&](sdrhip_chanaudio *h) {
-      h->build(ctx, dtype, M, D, h32, max_in, real);
-      h->mode_host.assign((size_t)K, SDRHIP_EPI_FM);
-      h->gain_host.assign((size_t)K, 1.0f);
-      if (modes) h->mode_host.assign(modes, modes + K);
-      if (gains) h->gain_host.assign(gains, gains + K);
-      h->mode.alloc((size_t)K);
-      h->mode.upload(h->mode_host.data(), (size_t)K, ctx->stream);
-      h->gain.alloc((size_t)K);
-      h->gain.upload(h->gain_host.data(), (size_t)K, ctx->stream);
-      for (auto &b : h->last) { b.alloc((size_t)K); b.zero(ctx->stream); }
-      allow_lds_max(h->kernel(), h->lds_bytes());
-      h->fresh_state();
-    });
+    SDRHIP_REQUIRE(h && rows, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(n >= h->n_sel, SDRHIP_E_INVALID, short_fmt, n, h->n_sel);
+    for (int i = 0; i < h->n_sel; i++) rows[i] = (h->*per_channel)[(size_t)h->sel_host[(size_t)i]];
   });
 }
 
@@ -179,51 +179,17 @@ int sdrhip_chanreal_audio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const
   return create(ctx, dtype, M, D, taps, n_taps, max_in, modes, gains, out, true);
 }
 
-int sdrhip_chanaudio_out_count(sdrhip_chanaudio *h, size_t n, size_t *n_out) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
-    *n_out = h->out_count(n);
-  });
-}
+int sdrhip_chanaudio_out_count(sdrhip_chanaudio *h, size_t n, size_t *n_out) { return ch_out_count(h, n, n_out); }
 
 int sdrhip_chanaudio_process_dev(sdrhip_chanaudio *h, const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t *n_out) {
-  return guarded([&] {
-    Range roctx_range("sdrhip_chanaudio_process_dev");
-    if (n_out) *n_out = 0;
-    if (!call_begin(h, "n", n, in_dev, out_dev)) return;
-    const size_t no = h->out_count(n);
-    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
-    require_disjoint(in_dev, n, n, h->in_elem(), out_dev, s.out, no, sizeof(short), 1, (size_t)h->n_sel);
-    h->launch(in_dev, n, out_dev, s.out, no);
-    if (n_out) *n_out = no;
-  });
+  return ch_process_dev(h, "sdrhip_chanaudio_process_dev", sizeof(short), in_dev, n, out_dev, out_stride, n_out);
 }
 
 int sdrhip_chanaudio_process(sdrhip_chanaudio *h, const void *in_host, size_t n, void *out_host, size_t out_stride, size_t *n_out) {
-  return guarded([&] {
-    Range roctx_range("sdrhip_chanaudio_process");
-    if (n_out) *n_out = 0;
-    if (!call_begin(h, "n", n, in_host, out_host)) return;
-    const size_t no = h->out_count(n), rows = (size_t)h->n_sel, eb = h->in_elem(), ob = sizeof(short);
-    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
-    // (the staged rows follow the selection: a set_channels can raise them)
-    const size_t out_cap_b = rows * h->out_count_max(h->max_in) * ob;
-    if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
-    run_staged(h->ctx, h->stage, h->max_in * eb, out_cap_b, {in_host, n * eb, n * eb, 1}, {out_host, s.out * ob, no * ob, rows},
-               [&](void *in, void *out) {
-                 h->launch(in, n, out, no, no);
-                 return no * ob;
-               });
-    if (n_out) *n_out = no;
-  });
+  return ch_process(h, "sdrhip_chanaudio_process", sizeof(short), in_host, n, out_host, out_stride, n_out);
 }
 
-int sdrhip_chanaudio_set_channels(sdrhip_chanaudio *h, const int *idx, int n_sel) {
-  return guarded([&] {
-    use_handle(h);
-    h->select(idx, n_sel);
-  });
-}
+int sdrhip_chanaudio_set_channels(sdrhip_chanaudio *h, const int *idx, int n_sel) { return ch_set_channels(h, idx, n_sel); }
 
 int sdrhip_chanaudio_set_mode(sdrhip_chanaudio *h, int row, int mode) {
   return guarded([&] {
@@ -231,21 +197,15 @@ int sdrhip_chanaudio_set_mode(sdrhip_chanaudio *h, int row, int mode) {
     h->require_row(row);
     require_mode(mode, "row", row);
     h->ctx->use();
-    hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued
-    const int k = h->sel_host[(size_t)row];
-    h->mode_host[(size_t)k] = mode;
-    SDRHIP_CHECK_HIP(hipMemcpyAsync(h->mode.p + k, &h->mode_host[(size_t)k], sizeof(int), hipMemcpyHostToDevice, st));
-    SDRHIP_CHECK_HIP(hipMemsetAsync(h->last[h->cur].p + k, 0, sizeof(int), st));
-    SDRHIP_CHECK_HIP(hipStreamSynchronize(st));
+    // stream-ordered after the launches already enqueued: the mode, and behind it the row's `last` = 0
+    const size_t k = (size_t)h->sel_host[(size_t)row];
+    const int zero = 0;
+    replace_row(h->ctx, h->mode.p + k, h->mode_host[k], mode, h->last[h->cur].p + k, &zero, sizeof zero);
   });
 }
 
 int sdrhip_chanaudio_get_modes(sdrhip_chanaudio *h, int *modes, int n) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && modes, SDRHIP_E_INVALID, "NULL argument");
-    SDRHIP_REQUIRE(n >= h->n_sel, SDRHIP_E_INVALID, "modes holds %d entries, the node writes %d rows", n, h->n_sel);
-    for (int i = 0; i < h->n_sel; i++) modes[i] = h->mode_host[(size_t)h->sel_host[(size_t)i]];
-  });
+  return get_rows(h, &sdrhip_chanaudio::mode_host, modes, n, "modes holds %d entries, the node writes %d rows");
 }
 
 int sdrhip_chanaudio_set_gain(sdrhip_chanaudio *h, int row, float gain) {
@@ -261,27 +221,12 @@ int sdrhip_chanaudio_set_gain(sdrhip_chanaudio *h, int row, float gain) {
 }
 
 int sdrhip_chanaudio_get_gains(sdrhip_chanaudio *h, float *gains, int n) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && gains, SDRHIP_E_INVALID, "NULL argument");
-    SDRHIP_REQUIRE(n >= h->n_sel, SDRHIP_E_INVALID, "gains holds %d entries, the node writes %d rows", n, h->n_sel);
-    for (int i = 0; i < h->n_sel; i++) gains[i] = h->gain_host[(size_t)h->sel_host[(size_t)i]];
-  });
+  return get_rows(h, &sdrhip_chanaudio::gain_host, gains, n, "gains holds %d entries, the node writes %d rows");
 }
 
-int sdrhip_chanaudio_set_taps(sdrhip_chanaudio *h, const double *taps) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
-    h->ctx->use();
-    h->set_taps(taps);
-  });
-}
+int sdrhip_chanaudio_set_taps(sdrhip_chanaudio *h, const double *taps) { return ch_set_taps(h, taps); }
 
-int sdrhip_chanaudio_reset(sdrhip_chanaudio *h) {
-  return guarded([&] {
-    use_handle(h);
-    h->fresh_state();
-  });
-}
+int sdrhip_chanaudio_reset(sdrhip_chanaudio *h) { return ch_reset(h); }
 
 int sdrhip_chanaudio_get_state(sdrhip_chanaudio *h, uint64_t *consumed, float *tail, size_t tail_len, int *last, size_t n_last) {
   return guarded([&] {
@@ -299,10 +244,7 @@ int sdrhip_chanaudio_get_state(sdrhip_chanaudio *h, uint64_t *consumed, float *t
 int sdrhip_chanaudio_plan_info(sdrhip_chanaudio *h, int *tile_times, int *branch_taps, int *lds_bytes, int *rows, int *fm_rows,
                                int *halo_tiles) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    if (tile_times) *tile_times = h->T;
-    if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
-    if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+    ch_plan_head(h, tile_times, branch_taps, lds_bytes);
     if (rows) *rows = h->n_sel;
     if (fm_rows) *fm_rows = h->fm_rows();
     if (halo_tiles) {
@@ -312,11 +254,7 @@ int sdrhip_chanaudio_plan_info(sdrhip_chanaudio *h, int *tile_times, int *branch
   });
 }
 
-int sdrhip_chanaudio_kernel_names(sdrhip_chanaudio *h, char *buf, size_t len) {
-  return guarded([&] {
-    write_names(h, buf, len, [&] { return CA_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
-  });
-}
+int sdrhip_chanaudio_kernel_names(sdrhip_chanaudio *h, char *buf, size_t len) { return ch_kernel_names(h, buf, len, CA_NAMES); }
 
 int sdrhip_chanaudio_destroy(sdrhip_chanaudio *h) {
   return guarded([&] { destroy_handle(h); });

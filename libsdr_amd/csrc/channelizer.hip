@@ -49,18 +49,13 @@ constexpr const char *CH_NAMES[2][2] = {{"channelizer_cs16_kernel", "channelizer
 }  // namespace
 
 struct sdrhip_channelizer : ChPlan {
-  ChKernel kernel() const { return CH_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
+  ChKernel kernel() const { return pick(CH_KERNELS); }
   size_t lds_bytes() const { return (size_t)T * (size_t)ld * sizeof(float2); }
   // n >= 1
   void launch(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) {
     ctx->use();
     const ChArgs a = args(in_dev, n, out_dev, out_stride, n_out);
-    const dim3 grid((unsigned)std::max(a.tiles, 1)), block(CH_THREADS);
-    const size_t lds = lds_bytes();
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a);
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    advance(n);
+    launch_tiles(kernel(), a.tiles, lds_bytes(), n, a);
   }
 };
 
@@ -68,18 +63,7 @@ namespace {
 
 // both create calls; real: sdrhip_chanreal.h's
 int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, sdrhip_channelizer **out, bool real) {
-  return guarded([&] {
-    if (out) *out = nullptr;
-    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
-    std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
-    require_device_for_null_ctx(ctx);
-    make_handle(ctx, out, true, [&](sdrhip_channelizer *h) {
-      h->build(ctx, dtype, M, D, h32, max_in, real);
-      allow_lds_max(h->kernel(), h->lds_bytes());
-      h->fresh_tail();
-    });
-  });
+  return ch_create(ctx, dtype, M, D, taps, n_taps, max_in, out, real, [] {}, [](sdrhip_channelizer *) {});
 }
 
 }  // namespace
@@ -96,66 +80,21 @@ int sdrhip_chanreal_channelizer_create(sdrhip_ctx *ctx, int dtype, int M, int D,
   return create(ctx, dtype, M, D, taps, n_taps, max_in, out, true);
 }
 
-int sdrhip_channelizer_out_count(sdrhip_channelizer *h, size_t n, size_t *n_out) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
-    *n_out = h->out_count(n);
-  });
-}
+int sdrhip_channelizer_out_count(sdrhip_channelizer *h, size_t n, size_t *n_out) { return ch_out_count(h, n, n_out); }
 
 int sdrhip_channelizer_process_dev(sdrhip_channelizer *h, const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t *n_out) {
-  return guarded([&] {
-    Range roctx_range("sdrhip_channelizer_process_dev");
-    if (n_out) *n_out = 0;
-    if (!call_begin(h, "n", n, in_dev, out_dev)) return;
-    const size_t no = h->out_count(n);
-    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
-    require_disjoint(in_dev, n, n, h->in_elem(), out_dev, s.out, no, sizeof(float2), 1, (size_t)h->n_sel);
-    h->launch(in_dev, n, out_dev, s.out, no);
-    if (n_out) *n_out = no;
-  });
+  return ch_process_dev(h, "sdrhip_channelizer_process_dev", sizeof(float2), in_dev, n, out_dev, out_stride, n_out);
 }
 
 int sdrhip_channelizer_process(sdrhip_channelizer *h, const void *in_host, size_t n, void *out_host, size_t out_stride, size_t *n_out) {
-  return guarded([&] {
-    Range roctx_range("sdrhip_channelizer_process");
-    if (n_out) *n_out = 0;
-    if (!call_begin(h, "n", n, in_host, out_host)) return;
-    const size_t no = h->out_count(n), rows = (size_t)h->n_sel, eb = h->in_elem(), ob = sizeof(float2);
-    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
-    // (the staged rows follow the selection: a set_channels can raise them)
-    const size_t out_cap_b = rows * h->out_count_max(h->max_in) * ob;
-    if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
-    run_staged(h->ctx, h->stage, h->max_in * eb, out_cap_b, {in_host, n * eb, n * eb, 1}, {out_host, s.out * ob, no * ob, rows},
-               [&](void *in, void *out) {
-                 h->launch(in, n, out, no, no);
-                 return no * ob;
-               });
-    if (n_out) *n_out = no;
-  });
+  return ch_process(h, "sdrhip_channelizer_process", sizeof(float2), in_host, n, out_host, out_stride, n_out);
 }
 
-int sdrhip_channelizer_set_channels(sdrhip_channelizer *h, const int *idx, int n_sel) {
-  return guarded([&] {
-    use_handle(h);
-    h->select(idx, n_sel);
-  });
-}
+int sdrhip_channelizer_set_channels(sdrhip_channelizer *h, const int *idx, int n_sel) { return ch_set_channels(h, idx, n_sel); }
 
-int sdrhip_channelizer_set_taps(sdrhip_channelizer *h, const double *taps) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
-    h->ctx->use();
-    h->set_taps(taps);
-  });
-}
+int sdrhip_channelizer_set_taps(sdrhip_channelizer *h, const double *taps) { return ch_set_taps(h, taps); }
 
-int sdrhip_channelizer_reset(sdrhip_channelizer *h) {
-  return guarded([&] {
-    use_handle(h);
-    h->fresh_tail();
-  });
-}
+int sdrhip_channelizer_reset(sdrhip_channelizer *h) { return ch_reset(h); }
 
 int sdrhip_channelizer_get_state(sdrhip_channelizer *h, uint64_t *consumed, float *tail, size_t tail_len) {
   return guarded([&] {
@@ -166,19 +105,12 @@ int sdrhip_channelizer_get_state(sdrhip_channelizer *h, uint64_t *consumed, floa
 
 int sdrhip_channelizer_plan_info(sdrhip_channelizer *h, int *tile_times, int *branch_taps, int *lds_bytes, int *rows) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    if (tile_times) *tile_times = h->T;
-    if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
-    if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+    ch_plan_head(h, tile_times, branch_taps, lds_bytes);
     if (rows) *rows = h->n_sel;
   });
 }
 
-int sdrhip_channelizer_kernel_names(sdrhip_channelizer *h, char *buf, size_t len) {
-  return guarded([&] {
-    write_names(h, buf, len, [&] { return CH_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
-  });
-}
+int sdrhip_channelizer_kernel_names(sdrhip_channelizer *h, char *buf, size_t len) { return ch_kernel_names(h, buf, len, CH_NAMES); }
 
 int sdrhip_channelizer_destroy(sdrhip_channelizer *h) {
   return guarded([&] { destroy_handle(h); });

@@ -257,7 +257,7 @@ __device__ __forceinline__ void ch_body_strided(const ChArgs &a, const E &epi) {
   else epi.template roll<I>(a, tid);
 }
 
-// ---- host side: what both handle types hold and do ---------------------------------------------------------------------------
+// ---- host side: what the handle types hold and do ----------------------------------------------------------------------------
 // the argument rules of create, in the header's order (before the context: host rules); h32: the taps rounded once to float32
 // (real: the rules of sdrhip_chanreal.h — the type codes have the complex ones' values, M is even and at least 4, and the
 // transform is M / 2 points long)
@@ -394,6 +394,124 @@ struct ChPlan {
   }
   // the state moves on only behind a launch that was accepted
   void advance(size_t n) { consumed += n; cur ^= 1; }
+  // a handle's entry of its [real][dtype] table of kernels or of their names
+  template <class X>
+  const X &pick(const X (&table)[2][2]) const { return table[real][dtype != SDRHIP_CHAN_CS16]; }
+  // the launch of n >= 1 samples: max(blocks, 1) workgroups of CH_THREADS on the context's stream, with the state moved on
+  // (always inlined: it is the tail of a handle type's launch(), and the library's dynamic symbols stay the handle types' own)
+  template <class K, class... A>
+  __attribute__((always_inline)) void launch_tiles(K kernel, int blocks, size_t lds, size_t n, const A &...a) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(blocks, 1)), dim3(CH_THREADS), lds, ctx->stream, a...);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    advance(n);
+  }
+  // a handle type with state besides the tail has its own, and ends it with fresh_tail
+  void fresh_state() { fresh_tail(); }
 };
+
+// ---- the entry points of a handle type H : ChPlan (channelizer.hip, chanaudio.hip, chanpower.hip) ---------------------------------
+// H has kernel(), lds_bytes(), fresh_state() and, for the row calls, launch(in_dev, n, out_dev, out_stride, n_out).
+// Both create calls of a type (real: sdrhip_chanreal.h's). rules(): the node's own argument rules, host rules like those before
+// them; init(h): the node's own buffers, on the built plan.
+template <class H, class Rules, class Init>
+static inline int ch_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, H **out, bool real,
+                            Rules &&rules, Init &&init) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
+    std::vector<float> h32;
+    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
+    rules();
+    require_device_for_null_ctx(ctx);
+    make_handle(ctx, out, true, [&](H *h) {
+      h->build(ctx, dtype, M, D, h32, max_in, real);
+      init(h);
+      allow_lds_max(h->kernel(), h->lds_bytes());
+      h->fresh_state();
+    });
+  });
+}
+
+template <class H>
+static inline int ch_out_count(H *h, size_t n, size_t *n_out) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
+    *n_out = h->out_count(n);
+  });
+}
+
+// the row calls: n_sel rows of elements of `ob` bytes; range: the call's name
+template <class H>
+static inline int ch_process_dev(H *h, const char *range, size_t ob, const void *in_dev, size_t n, void *out_dev, size_t out_stride,
+                                 size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range(range);
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_dev, out_dev)) return;
+    const size_t no = h->out_count(n);
+    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
+    require_disjoint(in_dev, n, n, h->in_elem(), out_dev, s.out, no, ob, 1, (size_t)h->n_sel);
+    h->launch(in_dev, n, out_dev, s.out, no);
+    if (n_out) *n_out = no;
+  });
+}
+template <class H>
+static inline int ch_process(H *h, const char *range, size_t ob, const void *in_host, size_t n, void *out_host, size_t out_stride,
+                             size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range(range);
+    if (n_out) *n_out = 0;
+    if (!call_begin(h, "n", n, in_host, out_host)) return;
+    const size_t no = h->out_count(n), rows = (size_t)h->n_sel, eb = h->in_elem();
+    const Strides s = call_strides("n", n, 0, no, out_stride, STRIDE_OUT);
+    // (the staged rows follow the selection: a set_channels can raise them)
+    const size_t out_cap_b = rows * h->out_count_max(h->max_in) * ob;
+    if (h->stage.out.p && h->stage.out.n < out_cap_b) h->stage.out.alloc(out_cap_b);
+    run_staged(h->ctx, h->stage, h->max_in * eb, out_cap_b, {in_host, n * eb, n * eb, 1}, {out_host, s.out * ob, no * ob, rows},
+               [&](void *in, void *out) {
+                 h->launch(in, n, out, no, no);
+                 return no * ob;
+               });
+    if (n_out) *n_out = no;
+  });
+}
+
+template <class H>
+static inline int ch_set_channels(H *h, const int *idx, int n_sel) {
+  return guarded([&] {
+    use_handle(h);
+    h->select(idx, n_sel);
+  });
+}
+template <class H>
+static inline int ch_set_taps(H *h, const double *taps) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
+    h->ctx->use();
+    h->set_taps(taps);
+  });
+}
+template <class H>
+static inline int ch_reset(H *h) {
+  return guarded([&] {
+    use_handle(h);
+    h->fresh_state();
+  });
+}
+// the head of *_plan_info, inside the entry point's guarded(): the handle rule and the fields every type has
+template <class H>
+static inline void ch_plan_head(H *h, int *tile_times, int *branch_taps, int *lds_bytes) {
+  SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
+  if (tile_times) *tile_times = h->T;
+  if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
+  if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+}
+template <class H>
+static inline int ch_kernel_names(H *h, char *buf, size_t len, const char *const (&names)[2][2]) {
+  return guarded([&] {
+    write_names(h, buf, len, [&] { return h->pick(names); });
+  });
+}
 
 }  // namespace sdrhip

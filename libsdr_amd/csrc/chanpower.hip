@@ -115,7 +115,7 @@ struct sdrhip_chanpower : ChPlan {
   int G = 1;                                   // the workgroups of a launch at most
   DevBuf<double> partial, level, thr_open, thr_close;   // [G][nch], [nch], [nch], [nch]
   DevBuf<unsigned char> open;                  // [nch]
-  CpKernel kernel() const { return CP_KERNELS[real][dtype != SDRHIP_CHAN_CS16]; }
+  CpKernel kernel() const { return pick(CP_KERNELS); }
   size_t lds_bytes() const { return (size_t)T * (size_t)ld * sizeof(float2); }
   void fresh_state() {
     SDRHIP_CHECK_HIP(hipMemsetAsync(level.p, 0, (size_t)nch * sizeof(double), ctx->stream));
@@ -128,17 +128,12 @@ struct sdrhip_chanpower : ChPlan {
     ctx->use();
     const ChArgs a = args(in_dev, n, nullptr, 0, n_out);
     const int rows = std::min(a.tiles, G);
-    const dim3 grid((unsigned)std::max(rows, 1)), block(CH_THREADS);
-    const size_t lds = lds_bytes();
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kernel(), grid, block, lds, ctx->stream, a, partial.p);
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    advance(n);
+    launch_tiles(kernel(), rows, lds_bytes(), n, a, partial.p);
     if (n_out == 0 && !sum_dev) return;
     CpFinishArgs f;
     f.partial = partial.p; f.open_thr = thr_open.p; f.close_thr = thr_close.p; f.level = level.p; f.open = open.p; f.sum = sum_dev;
     f.alpha = alpha; f.M = nch; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
-    hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)nch, (size_t)CH_THREADS)), block, 0, ctx->stream, f);
+    hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)nch, (size_t)CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, f);
     SDRHIP_CHECK_HIP(hipGetLastError());
     if (n_out) calls++;
   }
@@ -149,34 +144,23 @@ namespace {
 // both create calls; real: sdrhip_chanreal.h's
 int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha, sdrhip_chanpower **out,
            bool real) {
-  return guarded([&] {
-    if (out) *out = nullptr;
-    SDRHIP_REQUIRE(out && taps, SDRHIP_E_INVALID, "NULL argument");
-    std::vector<float> h32;
-    ch_require_args(dtype, M, D, taps, n_taps, max_in, h32, real);
-    require_alpha(alpha);
-    require_device_for_null_ctx(ctx);
-    make_handle(ctx, out, true, [&](sdrhip_chanpower *h) {
-      h->build(ctx, dtype, M, D, h32, max_in, real);
-      const size_t K = (size_t)h->nch;
-      h->alpha = alpha;
-      const char *e = getenv("SDRHIP_CHANPOWER_GRID");   // read once: the partial buffer is allocated for it
-      h->G = std::max(1, CP_GRID_PER_CU * ctx->prop.multiProcessorCount);
-      if (e && atoi(e) >= 1) h->G = std::min(h->G, atoi(e));
-      // (no call has more tiles than max_in gives)
-      h->G = (int)std::min((size_t)h->G, std::max(ceil_div(h->out_count_max(max_in), (size_t)h->T), (size_t)1));
-      h->partial.alloc((size_t)h->G * K);
-      h->level.alloc(K);
-      h->open.alloc(K);
-      std::vector<double> inf(K, HUGE_VAL), zero(K, 0.0);
-      h->thr_open.alloc(K);
-      h->thr_open.upload(inf.data(), inf.size(), ctx->stream);
-      h->thr_close.alloc(K);
-      h->thr_close.upload(zero.data(), zero.size(), ctx->stream);
-      SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // (the uploads read locals)
-      allow_lds_max(h->kernel(), h->lds_bytes());
-      h->fresh_state();
-    });
+  return ch_create(ctx, dtype, M, D, taps, n_taps, max_in, out, real, [&] { require_alpha(alpha); }, [&](sdrhip_chanpower *h) {
+    const size_t K = (size_t)h->nch;
+    h->alpha = alpha;
+    const char *e = getenv("SDRHIP_CHANPOWER_GRID");   // read once: the partial buffer is allocated for it
+    h->G = std::max(1, CP_GRID_PER_CU * ctx->prop.multiProcessorCount);
+    if (e && atoi(e) >= 1) h->G = std::min(h->G, atoi(e));
+    // (no call has more tiles than max_in gives)
+    h->G = (int)std::min((size_t)h->G, std::max(ceil_div(h->out_count_max(max_in), (size_t)h->T), (size_t)1));
+    h->partial.alloc((size_t)h->G * K);
+    h->level.alloc(K);
+    h->open.alloc(K);
+    std::vector<double> inf(K, HUGE_VAL), zero(K, 0.0);
+    h->thr_open.alloc(K);
+    h->thr_open.upload(inf.data(), inf.size(), ctx->stream);
+    h->thr_close.alloc(K);
+    h->thr_close.upload(zero.data(), zero.size(), ctx->stream);
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // (the uploads read locals)
   });
 }
 
@@ -194,12 +178,7 @@ int sdrhip_chanreal_power_create(sdrhip_ctx *ctx, int dtype, int M, int D, const
   return create(ctx, dtype, M, D, taps, n_taps, max_in, alpha, out, true);
 }
 
-int sdrhip_chanpower_out_count(sdrhip_chanpower *h, size_t n, size_t *n_out) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && n_out, SDRHIP_E_INVALID, "NULL argument");
-    *n_out = h->out_count(n);
-  });
-}
+int sdrhip_chanpower_out_count(sdrhip_chanpower *h, size_t n, size_t *n_out) { return ch_out_count(h, n, n_out); }
 
 int sdrhip_chanpower_process_dev(sdrhip_chanpower *h, const void *in_dev, size_t n, double *sum_dev, size_t *n_out) {
   return guarded([&] {
@@ -235,14 +214,10 @@ int sdrhip_chanpower_set_thresholds(sdrhip_chanpower *h, const double *open_thr,
       SDRHIP_REQUIRE(close_thr[k] >= 0.0 && close_thr[k] <= open_thr[k], SDRHIP_E_INVALID,
                      "thresholds of channel %d: 0 <= close_thr %g <= open_thr %g does not hold", k, close_thr[k], open_thr[k]);
     h->ctx->use();
-    hipStream_t st = h->ctx->stream;   // stream-ordered after the launches already enqueued; both or none is not promised on a failing device
+    // stream-ordered after the launches already enqueued; both or none is not promised on a failing device
     const size_t b = (size_t)h->nch * sizeof(double);
-    const hipError_t e1 = hipMemcpyAsync(h->thr_open.p, open_thr, b, hipMemcpyHostToDevice, st);
-    const hipError_t e2 = hipMemcpyAsync(h->thr_close.p, close_thr, b, hipMemcpyHostToDevice, st);
-    const hipError_t e3 = hipStreamSynchronize(st);
-    SDRHIP_CHECK_HIP(e1);
-    SDRHIP_CHECK_HIP(e2);
-    SDRHIP_CHECK_HIP(e3);
+    put_sync(h->ctx, h->thr_open.p, open_thr, b);
+    put_sync(h->ctx, h->thr_close.p, close_thr, b);
   });
 }
 
@@ -254,20 +229,9 @@ int sdrhip_chanpower_set_alpha(sdrhip_chanpower *h, double alpha) {
   });
 }
 
-int sdrhip_chanpower_set_taps(sdrhip_chanpower *h, const double *taps) {
-  return guarded([&] {
-    SDRHIP_REQUIRE(h && taps, SDRHIP_E_INVALID, "NULL argument");
-    h->ctx->use();
-    h->set_taps(taps);
-  });
-}
+int sdrhip_chanpower_set_taps(sdrhip_chanpower *h, const double *taps) { return ch_set_taps(h, taps); }
 
-int sdrhip_chanpower_reset(sdrhip_chanpower *h) {
-  return guarded([&] {
-    use_handle(h);
-    h->fresh_state();
-  });
-}
+int sdrhip_chanpower_reset(sdrhip_chanpower *h) { return ch_reset(h); }
 
 int sdrhip_chanpower_get_levels(sdrhip_chanpower *h, double *level, unsigned char *open, int len) {
   return guarded([&] {
@@ -304,20 +268,13 @@ int sdrhip_chanpower_get_state(sdrhip_chanpower *h, uint64_t *consumed, float *t
 
 int sdrhip_chanpower_plan_info(sdrhip_chanpower *h, int *tile_times, int *branch_taps, int *lds_bytes, int *grid, int *partial_bytes) {
   return guarded([&] {
-    SDRHIP_REQUIRE(h, SDRHIP_E_INVALID, "handle is NULL");
-    if (tile_times) *tile_times = h->T;
-    if (branch_taps) *branch_taps = (int)ceil_div((size_t)h->n_taps, (size_t)h->M);
-    if (lds_bytes) *lds_bytes = (int)h->lds_bytes();
+    ch_plan_head(h, tile_times, branch_taps, lds_bytes);
     if (grid) *grid = h->G;
     if (partial_bytes) *partial_bytes = (int)(h->partial.n * sizeof(double));
   });
 }
 
-int sdrhip_chanpower_kernel_names(sdrhip_chanpower *h, char *buf, size_t len) {
-  return guarded([&] {
-    write_names(h, buf, len, [&] { return CP_NAMES[h->real][h->dtype != SDRHIP_CHAN_CS16]; });
-  });
-}
+int sdrhip_chanpower_kernel_names(sdrhip_chanpower *h, char *buf, size_t len) { return ch_kernel_names(h, buf, len, CP_NAMES); }
 
 int sdrhip_chanpower_destroy(sdrhip_chanpower *h) {
   return guarded([&] { destroy_handle(h); });

@@ -27,44 +27,10 @@
 #include <vector>
 
 #include "sdr/gpu/chanreal.hh"
-
-using namespace sdr;
-
-template <class T>
-static std::vector<T> readBin(const std::string &path, size_t count) {
-  std::vector<T> v(count);
-  std::ifstream f(path.c_str(), std::ios::binary);
-  f.read(reinterpret_cast<char *>(v.data()), count * sizeof(T));
-  if ((size_t)f.gcount() != count * sizeof(T)) { fprintf(stderr, "%s: short file\n", path.c_str()); exit(2); }
-  return v;
-}
-
-template <class T>
-class Capture : public Sink<T> {
-public:
-  std::vector<T> data;
-  Config cfg;
-  virtual void config(const Config &c) { cfg = c; }
-  virtual void process(const Buffer<T> &b, bool) {
-    for (size_t i = 0; i < b.size(); i++) data.push_back(b[i]);
-  }
-};
-
-template <class T>
-class Feeder : public Source {
-public:
-  void configure(double Fs, size_t maxlen) { this->setConfig(Config(Config::typeId<T>(), Fs, maxlen, 1)); }
-  void feed(T *p, size_t n) { Buffer<T> view(p, n); this->send(view, false); }
-};
+#include "harness.hh"
 
 typedef int16_t cs;   // the real row's element
 typedef std::complex<float> cf;
-
-template <class F>
-static bool refused(F make) {
-  try { make(); } catch (ConfigError &) { return true; } catch (SDRError &) {}
-  return false;
-}
 
 static int runRules() {
   int failures = 0, n = 0;
@@ -373,17 +339,11 @@ static int runPower(const char *casePath, const char *tapsPath, const char *xPat
 }
 
 int main(int argc, char **argv) {
-  int failures = 0;
-  try {
-    if (argc >= 2 && std::string(argv[1]) == "rules") failures = runRules();
-    else if (argc >= 6 && std::string(argv[1]) == "graph") failures = runGraph(argv[2], argv[3], argv[4], argv[5]);
-    else if (argc >= 7 && std::string(argv[1]) == "audio") failures = runAudio(argv[2], argv[3], argv[4], argv[5], argv[6]);
-    else if (argc >= 6 && std::string(argv[1]) == "power") failures = runPower(argv[2], argv[3], argv[4], argv[5]);
-    else { fprintf(stderr, "usage: test_chanreal rules | graph|power <case.txt> <taps.bin> <x.bin> <want.bin> | audio ... <want_one.bin>\n"); return 2; }
-  } catch (SDRError &e) {
-    printf("FAIL exception: %s\n", e.what());
-    failures++;
-  }
-  printf("%s (%d failures)\n", failures ? "FAILED" : "OK", failures);
-  return failures ? 1 : 0;
+  return runMain("usage: test_chanreal rules | graph|power <case.txt> <taps.bin> <x.bin> <want.bin> | audio ... <want_one.bin>\n", [&]() -> int {
+    if (argc >= 2 && std::string(argv[1]) == "rules") return runRules();
+    if (argc >= 6 && std::string(argv[1]) == "graph") return runGraph(argv[2], argv[3], argv[4], argv[5]);
+    if (argc >= 7 && std::string(argv[1]) == "audio") return runAudio(argv[2], argv[3], argv[4], argv[5], argv[6]);
+    if (argc >= 6 && std::string(argv[1]) == "power") return runPower(argv[2], argv[3], argv[4], argv[5]);
+    return -1;
+  });
 }

@@ -15,8 +15,7 @@
 #include <vector>
 
 #include "sdr/gpu/resample.hh"
-
-using namespace sdr;
+#include "harness.hh"
 
 struct Case {
   std::string name, dtype;
@@ -26,34 +25,7 @@ struct Case {
   std::vector<uint32_t> mu;
 };
 
-template <class T>
-static std::vector<T> readBin(const std::string &path, size_t count) {
-  std::vector<T> v(count);
-  std::ifstream f(path.c_str(), std::ios::binary);
-  f.read(reinterpret_cast<char *>(v.data()), count * sizeof(T));
-  if ((size_t)f.gcount() != count * sizeof(T)) { fprintf(stderr, "%s: short file\n", path.c_str()); exit(2); }
-  return v;
-}
-
 static uint32_t bitsOf(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-
-template <class T>
-class Capture : public Sink<T> {
-public:
-  std::vector<T> data;
-  Config cfg;
-  virtual void config(const Config &c) { cfg = c; }
-  virtual void process(const Buffer<T> &b, bool) {
-    for (size_t i = 0; i < b.size(); i++) data.push_back(b[i]);
-  }
-};
-
-template <class T>
-class Feeder : public Source {
-public:
-  void configure(double Fs, size_t maxlen) { this->setConfig(Config(Config::typeId<T>(), Fs, maxlen, 1)); }
-  void feed(T *p, size_t n) { Buffer<T> view(p, n); this->send(view, false); }
-};
 
 static int runRules() {
   int failures = 0;

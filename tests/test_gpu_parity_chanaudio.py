@@ -271,6 +271,58 @@ def test_setters_between_calls(ctx):
 
 
 @pytest.mark.hostptr_only
+def test_host_pointer_staging_grows_with_the_selection(ctx):
+    """The first host-pointer call stages two rows (reordered: get_modes and get_gains follow the rows); set_channels then
+    raises the rows to M, and the staged output has to regrow. Calls of 1, 7 and 23 samples, one of T + 1 outputs, the rest."""
+    shape, dtype = (6, 4, 14), "cs16"
+    M, D, _ = shape
+    _, x = _stream(shape, dtype)
+    modes, gains = _modes(M), _gains(M, dtype)
+    lens = [1, 7, 23, (tile_times(M) + 1) * D]
+    lens.append(len(x) - sum(lens))
+    sel = [3, 0]                                             # both FM
+    node, plain = _pair(ctx, shape, dtype, len(x), modes, gains, channels=sel)
+    assert node.get_modes() == [modes[k] for k in sel] and np.array_equal(node.get_gains(), gains[sel])
+    ref = A.Rows(modes, gains)
+    _run(node, plain, ref, x, lens, rows=sel)
+    before = node.get_state()["last"].tolist()
+    assert before[0] != 0 and before[1] != 0
+    node.set_mode(1, FM)                                    # row 1 is channel 0: its `last` starts from 0, channel 3's stays
+    ref.set_mode(0, FM)
+    assert node.get_state()["last"].tolist() == [ref.last[3], ref.last[0]] == [before[0], 0]
+    part = x[:23]
+    assert np.array_equal(node.process(part), ref.process(plain.process(part), sel))
+    for v in (node, plain):
+        v.reset()
+        v.set_channels(None)
+    assert node.plan_info()["rows"] == M and node.get_modes() == modes and np.array_equal(node.get_gains(), gains)
+    y, w = _run(node, plain, A.Rows(modes, gains), x, lens)
+    assert y.shape == (M, len(x) // D)
+    for v in (node, plain):
+        v.reset()
+    _run(node, plain, A.Rows(modes, gains), x, [len(x)])    # one call of max_in samples: the largest staged output
+    # set_taps in mid-stream: the node and the plain channelizer take the new prototype; one that is not finite changes nothing
+    import libsdr_amd as sa
+    other = _taps(M, 14)[::-1] * np.linspace(0.5, 1.5, 14)
+    bad = other.copy()
+    bad[3] = np.inf
+    ref = A.Rows(modes, gains)
+    for v in (node, plain):
+        v.reset()
+    _run(node, plain, ref, x, [7, 23])
+    for v in (node, plain):
+        v.set_taps(other)
+    with pytest.raises(sa.SdrHipError) as e:
+        node.set_taps(bad)
+    assert e.value.code == sa.abi.E_INVALID
+    part = x[30:30 + (tile_times(M) + 1) * D]
+    y, y32 = node.process(part), plain.process(part)
+    assert np.array_equal(y, ref.process(y32)) and node.get_state()["last"].tolist() == ref.last
+    node.close()
+    plain.close()
+
+
+@pytest.mark.hostptr_only
 def test_host_pointer_calls_and_refusals(ctx):
     from libsdr_amd import abi
     shape, dtype = (12, 5, 30), "cs16"

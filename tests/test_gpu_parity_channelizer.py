@@ -177,6 +177,31 @@ def test_set_taps_in_mid_stream(ctx, shape, dtype):
 
 
 @pytest.mark.hostptr_only
+def test_host_pointer_staging_grows_with_the_selection(ctx):
+    """The first host-pointer call stages two rows; set_channels then raises the rows to M, and the staged output has to regrow:
+    calls of 1, 7 and 23 samples (blocks of D with a remainder), one of T + 1 outputs (two workgroups) and the rest."""
+    shape, dtype = (6, 4, 14), "cs16"
+    M, D, _ = shape
+    taps, x, _, ref = _case(shape, dtype)
+    lens = [1, 7, 23, (tile_times(M) + 1) * D]
+    lens.append(len(x) - sum(lens))
+    node = _node(ctx, shape, dtype, taps, len(x), channels=[4, 1])
+    y2 = _run(node, x, lens)
+    assert y2.shape == (2, ref.shape[1], 2) and _err(y2, ref[[4, 1]]) <= BOUND
+    node.reset()
+    node.set_channels(None)
+    assert node.plan_info()["rows"] == M
+    y = _run(node, x, lens)
+    err = _err(y, ref)
+    print("channelizer %s %s, rows 2 -> %d through the staging: %.3g" % (shape, dtype, M, err))
+    assert y.shape == (M, ref.shape[1], 2) and err <= BOUND, err
+    assert same(y[[4, 1]], y2)
+    node.reset()
+    assert same(node.process(x), y)                         # one call of max_in samples: the largest staged output
+    node.close()
+
+
+@pytest.mark.hostptr_only
 def test_host_pointer_calls_and_refusals(ctx):
     import libsdr_amd as sa
     from libsdr_amd import abi

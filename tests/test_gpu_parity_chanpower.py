@@ -288,6 +288,37 @@ def test_setters_between_calls(ctx, shape, dtype):
     node.close()
 
 
+def test_thresholds_hold_from_the_next_call_on(ctx):
+    """set_thresholds leaves level and open as the last call left them — thresholds under which every flag would flip — and the
+    next call applies them. Calls of 1, 7 and 23 samples, one of T + 1 outputs (two tiles), the rest."""
+    shape, dtype = (6, 4, 14), "cs16"
+    M, D, _ = shape
+    taps, x, _, _, _, thr = _case(shape, dtype)
+    lens = [1, 7, 23, (tile_times(M) + 1) * D]
+    lens.append(len(x) - sum(lens))
+    node, ref, dev = _node(ctx, shape, dtype, taps, len(x)), P.Monitor(taps, M, D, ALPHA), P.Monitor(taps, M, D, ALPHA)
+    # (no output); every flag opens; every flag closes; opens; the restatement's median level decides
+    settings = [(0.0, 0.0), (0.0, 0.0), (np.inf, np.inf), (0.0, 0.0), thr]
+    off = 0
+    for n, t in zip(lens, settings):
+        level, flags = node.levels()
+        for v in (node, ref, dev):
+            v.set_thresholds(*t)
+        after = node.levels()
+        assert same(after[0], level) and np.array_equal(after[1], flags) and np.array_equal(flags, dev.open)   # not this call's
+        J = node.out_count(n)
+        s, w = node.process(x[off:off + n]), ref.process(x[off:off + n])
+        off += n
+        dev.update(s, J)
+        assert (np.abs(s - w).max() <= BOUND * w.max()) if J else not s.any()
+        level, flags = node.levels()
+        assert same(level, dev.level) and np.array_equal(flags, dev.open) and node.occupied() == dev.occupied(), n
+        if t == (0.0, 0.0) or t == (np.inf, np.inf):
+            assert np.array_equal(flags, np.full(M, bool(J) and t[0] == 0.0))
+    assert dev.calls == 4 == node.get_state()["calls"]
+    node.close()
+
+
 def test_a_nan_sample_on_a_float_row(ctx):
     shape, dtype = (12, 6, 30), "cf32"
     M, D, n_taps = shape

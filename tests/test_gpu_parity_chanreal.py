@@ -203,6 +203,30 @@ def test_inf_and_nan_samples(ctx, shape):
 
 
 @pytest.mark.hostptr_only
+def test_host_pointer_staging_grows_with_the_selection(ctx):
+    """As the complex node's case: two staged rows first, then all M / 2 + 1 through the same staging."""
+    shape, dtype = (12, 5, 30), "s16"
+    M, D, _ = shape
+    taps, x, _, ref = _case(shape, dtype)
+    lens = [1, 7, 23, (RR.tile_times(M) + 1) * D]
+    lens.append(len(x) - sum(lens))
+    node = _node(ctx, shape, dtype, taps, len(x), channels=[5, 0])
+    y2 = _run(node, x, lens)
+    assert y2.shape == (2, ref.shape[1], 2) and _err(y2, ref[[5, 0]]) <= BOUND
+    node.reset()
+    node.set_channels(None)
+    assert node.plan_info()["rows"] == M // 2 + 1
+    y = _run(node, x, lens)
+    err = _err(y, ref)
+    print("chanreal %s %s, rows 2 -> %d through the staging: %.3g" % (shape, dtype, M // 2 + 1, err))
+    assert y.shape == (M // 2 + 1, ref.shape[1], 2) and err <= BOUND, err
+    assert same(y[[5, 0]], y2)
+    node.reset()
+    assert same(node.process(x), y)                         # one call of max_in samples: the largest staged output
+    node.close()
+
+
+@pytest.mark.hostptr_only
 def test_host_pointer_calls_and_refusals(ctx):
     import libsdr_amd as sa
     from libsdr_amd import abi

@@ -15,33 +15,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "agc_bench.json")
 C, N, FS = 1024, 8192, 22050.0
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(5):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def main():
@@ -71,7 +52,7 @@ def main():
             "bitstream": lambda: bits.process_dev(dsym, N, N, dbits, cap, dcnt),
         }
         result = {"device": ctx.device_name(), "channels": C, "samples_per_channel": N, "reps": REPS, "rounds": ROUNDS, "lambda": lam,
-                  "plan": agc16.plan_info(N), "stages": timed_interleaved(ctx, cand),
+                  "plan": agc16.plan_info(N), "stages": timed_interleaved(ctx, cand, REPS, ROUNDS, warmup=5),
                   "kernels": {"agc_i16": agc16.kernel_names, "agc_f32": agcf.kernel_names, "deemph_i16": de.kernel_names(N),
                               "bitstream": bits.kernel_names}}
         ctx.synchronize()

@@ -19,6 +19,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "chanaudio_bench.json")
@@ -28,27 +30,6 @@ STEP_LIMIT_S = 150
 SHAPES = {"m1024_d1024": (1024, 1024, 8192, (None, 64), False), "m1024_d512": (1024, 512, 8192, (None, 64), False),
           "m128_d128": (128, 128, 512, (None,), True)}
 TUNER_C, TUNER_ORDER, TUNER_D = 128, 513, 128
-
-
-def timed_interleaved(sa, ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def run_shape(name):
@@ -80,7 +61,7 @@ def run_shape(name):
             cand[k] = lambda node=node: node.process_dev(din, N, dout, s)
         if tuner is not None:
             cand["tuner_fm_128_order513_d128"] = lambda: tuner.process_dev(din, N, dout, N // TUNER_D + 1)
-        stages = timed_interleaved(sa, ctx, cand)
+        stages = timed_interleaved(ctx, cand, REPS, ROUNDS)
         ctx.synchronize()
     finally:
         ctx.free(din)

@@ -16,6 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -27,27 +29,6 @@ WORKLOADS = {"m1024_d1024_all": (1024, 1024, 8192, None), "m1024_d1024_sel64": (
              "m1024_d512_all": (1024, 512, 8192, None), "m1024_d512_sel64": (1024, 512, 8192, 64),
              "m128_d128_all": (128, 128, 512, None)}
 TUNER_C, TUNER_ORDER, TUNER_D = 128, 513, 128
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def parity(ctx):
@@ -85,7 +66,7 @@ def main():
         ctx.h2d(din, x)
         cand = {name: (lambda node=node, s=N // WORKLOADS[name][1]: node.process_dev(din, N, dout, s)) for name, node in nodes.items()}
         cand["tuner_128_order513_d128"] = lambda: tuner.process_dev(din, N, dout, N // TUNER_D + 1)
-        stages = timed_interleaved(ctx, cand)
+        stages = timed_interleaved(ctx, cand, REPS, ROUNDS)
         ctx.synchronize()
         for name in WORKLOADS:
             D = WORKLOADS[name][1]

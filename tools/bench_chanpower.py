@@ -14,6 +14,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -22,27 +24,6 @@ OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "chan
 N, FS, SEL = 1 << 20, 2.048e6, 64
 # name -> (M, D, n_taps)
 SHAPES = {"m1024_d1024": (1024, 1024, 8192), "m1024_d512": (1024, 512, 8192), "m128_d128": (128, 128, 512)}
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def main():
@@ -65,7 +46,7 @@ def main():
             cand[name + "_monitor_state_only"] = lambda mon=mon: mon.process_dev(din, N)
             cand[name + "_channelizer_all"] = lambda v=every, s=N // D: v.process_dev(din, N, dout, s)
             cand[name + "_channelizer_sel64"] = lambda v=some, s=N // D: v.process_dev(din, N, dout, s)
-        stages = timed_interleaved(ctx, cand)
+        stages = timed_interleaved(ctx, cand, REPS, ROUNDS)
         ctx.synchronize()
         ratios = {}
         for name in SHAPES:

@@ -18,6 +18,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -43,27 +45,6 @@ def parity(ctx):
             errs["%d-%d-%d-%s" % (shape + (dtype,))] = float("%.3g" % T._err(node.process(x), ref))
             node.close()
     return errs
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def main():
@@ -102,7 +83,7 @@ def main():
         cand[NODES_AT + "_audio_widened"] = lambda: a_wide.process_dev(dwide, N, dout, N // D)
         cand[NODES_AT + "_power_real"] = lambda: p_real.process_dev(din, N, dsum)
         cand[NODES_AT + "_power_widened"] = lambda: p_wide.process_dev(dwide, N, dsum)
-        stages = timed_interleaved(ctx, cand)
+        stages = timed_interleaved(ctx, cand, REPS, ROUNDS)
         ctx.synchronize()
         ratios = {}
         for k in stages:

@@ -16,6 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 import psk31_restatement as R
 
@@ -23,27 +25,6 @@ REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "psk31_bench.json")
 C, N, FS = 1024, 8192, 8000.0
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def main():
@@ -78,7 +59,7 @@ def main():
             "bitstream": lambda: bits.process_dev(dsym, N, N, dbits, cap, dcnt),
         }
         result = {"device": ctx.device_name(), "channels": C, "samples_per_channel": N, "sample_rate": FS, "reps": REPS, "rounds": ROUNDS,
-                  "plan": p16.plan_info(N), "bit_capacity": pcap, "stages": timed_interleaved(ctx, cand),
+                  "plan": p16.plan_info(N), "bit_capacity": pcap, "stages": timed_interleaved(ctx, cand, REPS, ROUNDS),
                   "kernels": {"psk31_cs16": p16.kernel_names, "psk31_cf32": pf.kernel_names, "agc_i16": agc16.kernel_names,
                               "bitstream": bits.kernel_names}}
         ctx.synchronize()

@@ -20,6 +20,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 from libsdr_amd import abi
 
@@ -30,27 +32,6 @@ CH, N_IN, D = 1024, 65536, 8
 M = N_IN // D
 FS_IN, FS = 176400.0, 22050.0
 AX25, RTTY = (1200.0, 1200.0, 2200.0), (90.90, 930.0, 1100.0)
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def inside(x, ref):
@@ -122,7 +103,7 @@ def receiver(ctx, order, x, result):
         ctx.synchronize()
         cnt = np.zeros(CH, np.uint32)
         ctx.d2h(cnt, d["cnt"])
-        w = timed_interleaved(ctx, {"a_receiver_bank": a, "b_chained_on_device": b, "c_through_pinned_host": c})
+        w = timed_interleaved(ctx, {"a_receiver_bank": a, "b_chained_on_device": b, "c_through_pinned_host": c}, REPS, ROUNDS)
         w["bits_per_channel_and_step"] = float(cnt.mean())
         w["kernels"] = tuner.kernel_names + deemph.kernel_names(M) + det.kernel_names + bits.kernel_names
         w["a_inside_b_range"] = inside(w["a_receiver_bank"], w["b_chained_on_device"])
@@ -136,7 +117,7 @@ def receiver(ctx, order, x, result):
             half = sa.FMDeemphBankI16(ctx, sa.design_fmdeemph_alpha(FS), [c % 2 == 0 for c in range(CH)], max_in=M)
             cand = {k: (lambda v=v: v.process_dev(d["a0"], M, M, d["a1"], M))
                     for k, v in (("one_parameter", one), ("bank_all_enabled", all_on), ("bank_half_enabled", half))}
-            w = timed_interleaved(ctx, cand)
+            w = timed_interleaved(ctx, cand, REPS, ROUNDS)
             w["kernels"] = {"one_parameter": one.kernel_names(M), "bank": all_on.kernel_names(M)}
             w["all_enabled_inside_one_parameter_range"] = inside(w["bank_all_enabled"], w["one_parameter"])
             w["cost_of_the_flag_percent"] = round(100.0 * (w["bank_all_enabled"]["ms"] / w["one_parameter"]["ms"] - 1.0), 2)

@@ -14,6 +14,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 from libsdr_amd.resample import RESAMPLE_F32, RESAMPLE_CF32, RESAMPLE_I16, RESAMPLE_CS16_CF32
 
@@ -24,27 +26,6 @@ C, N, FS = 1024, 8192, 22050.0
 FRACS = {"0p5": 0.5, "1p378125": 1.378125, "7p9": 7.9}
 # name -> (code, bytes per input element, bytes per output element)
 TYPES = {"f32": (RESAMPLE_F32, 4, 4), "cf32": (RESAMPLE_CF32, 8, 8), "i16": (RESAMPLE_I16, 2, 2), "cs16_cf32": (RESAMPLE_CS16_CF32, 4, 8)}
-
-
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(5):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
 
 
 def main():
@@ -78,7 +59,7 @@ def main():
         cand["agc_i16"] = lambda: agc16.process_dev(din["i16"], N, N, o16, N)
         cand["agc_f32"] = lambda: agcf.process_dev(din["f32"], N, N, of, N)
         cand["bitstream"] = lambda: bits.process_dev(dsym, N, N, dbits, bcap, dcnt)
-        stages = timed_interleaved(ctx, cand)
+        stages = timed_interleaved(ctx, cand, REPS, ROUNDS, warmup=5)
         ctx.synchronize()
         outputs = {}
         counts = np.zeros(C, np.uint32)

@@ -24,6 +24,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from benchkit import timed_interleaved  # noqa: E402
+
 import libsdr_amd as sa
 
 PER_CHANNEL = "--per-channel" in sys.argv
@@ -121,27 +123,6 @@ def main():
         f.write("\n")
 
 
-def timed_interleaved(ctx, candidates):
-    """{name: fn} -> {name: median / min / max ms per call}: every round times each candidate once, in turn."""
-    for fn in candidates.values():
-        for _ in range(5):
-            fn()
-    ms = {k: [] for k in candidates}
-    for _ in range(ROUNDS):
-        for k, fn in candidates.items():
-            t = sa.Timer(ctx)
-            t.start()
-            for _ in range(REPS):
-                fn()
-            t.stop()
-            ms[k].append(t.elapsed_ms() / REPS)
-    out = {}
-    for k, v in ms.items():
-        v.sort()
-        out[k] = {"ms": round(v[len(v) // 2], 5), "min_ms": round(v[0], 5), "max_ms": round(v[-1], 5)}
-    return out
-
-
 def main_per_channel():
     import torch   # plumbing only: device buffers, the stream the context borrows, and the regrouped variant's row gather
 
@@ -200,7 +181,7 @@ def main_per_channel():
         cand["d_regrouped_gather_alone"] = gather
         result = {"device": ctx.device_name(), "channels": C, "audio_samples_per_channel": M, "reps": REPS, "rounds": ROUNDS,
                   "corr_len": {n: int(FS / np.float32(baud[n])) for n in WORKLOADS},
-                  "detector": timed_interleaved(ctx, cand),
+                  "detector": timed_interleaved(ctx, cand, REPS, ROUNDS, warmup=5),
                   "detector_kernels": {k: v.kernel_names for k, v in det.items()}}
         print(json.dumps({"detector": result["detector"]}), flush=True)
         for v in [det["c_per_channel_alternating"]] + halves:            # (the timed calls left them at different sample counts)
@@ -212,7 +193,7 @@ def main_per_channel():
         assert torch.equal(sym.index_select(0, by_protocol), sym_s)       # (d) computes (c)'s rows, regrouped
         cand = {k: (lambda v=v: v.process_dev(dsym, M, M, dbits, cap, dcnt)) for k, v in bits.items()}
         cand["d_regrouped_two_halves"] = bits_halves
-        result["bitstream"] = timed_interleaved(ctx, cand)
+        result["bitstream"] = timed_interleaved(ctx, cand, REPS, ROUNDS, warmup=5)
         result["bitstream_kernels"] = {k: v.kernel_names for k, v in bits.items()}
         print(json.dumps({"bitstream": result["bitstream"]}), flush=True)
 
@@ -222,7 +203,7 @@ def main_per_channel():
 
         cand = {k: both(k) for k in det}
         cand["d_regrouped_gather_plus_two_halves_per_stage"] = lambda: (det_regrouped(), bits_halves())
-        result["detector_then_bitstream"] = timed_interleaved(ctx, cand)
+        result["detector_then_bitstream"] = timed_interleaved(ctx, cand, REPS, ROUNDS, warmup=5)
         print(json.dumps({"detector_then_bitstream": result["detector_then_bitstream"]}), flush=True)
         ctx.synchronize()
         for v in list(det.values()) + list(bits.values()) + halves + bhalves:
