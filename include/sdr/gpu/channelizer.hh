@@ -104,6 +104,8 @@ public:
   typedef typename Grid::Api Api;
 
   sdrhip_ctx *context() const { return _ctx; }
+  /** The node's plan handle (null before config()): what gpu::ChannelGroup borrows. The node stays its owner. */
+  typename Api::Plan *plan() const { return _plan.get(); }
   /** A new prototype of the same length; the stream (and a monitor's levels and flags) go on. */
   void setTaps(const std::vector<double> &taps) {
     if (taps.size() != _taps.size()) {

@@ -10,6 +10,7 @@
 // channel's angle there — selected or not, its image has all M bins — and block 0 copies every other entry.
 // A handle of sdrhip_chanreal_audio_create (sdrhip_chanreal.h) runs chanaudio_real_s16_kernel / chanaudio_real_f32_kernel: the body's
 // real form in front of the same epilogue; the per-channel arrays then have nch = M / 2 + 1 entries.
+// A group of handles (sdrhip_changroup.h) runs group_chanaudio_*_kernel: member blockIdx.y's body on its own arguments.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanaudio.h"
 #include "sdrhip_chanreal.h"
@@ -84,7 +85,32 @@ __global__ __launch_bounds__(CH_THREADS) void chanaudio_cf32_kernel(const ChAudi
 __global__ __launch_bounds__(CH_THREADS) void chanaudio_real_s16_kernel(const ChAudioArgs a) { ch_body<short>(a.c, ChStoreAudio{a}); }
 __global__ __launch_bounds__(CH_THREADS) void chanaudio_real_f32_kernel(const ChAudioArgs a) { ch_body<float>(a.c, ChStoreAudio{a}); }
 
+// a group launch (sdrhip_changroup.h): member blockIdx.y's body on its own arguments
+using CaGroupArgs = ChGroupArgs<ChAudioArgs>;
+static_assert(sizeof(CaGroupArgs) <= CG_ARG_BYTES, "the member table travels in the kernel arguments");
+__global__ __launch_bounds__(CH_THREADS) void group_chanaudio_cs16_kernel(const CaGroupArgs g) {
+  const ChAudioArgs &a = g.m[blockIdx.y];
+  ch_body<short2>(a.c, ChStoreAudio{a});
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanaudio_cf32_kernel(const CaGroupArgs g) {
+  const ChAudioArgs &a = g.m[blockIdx.y];
+  ch_body<float2>(a.c, ChStoreAudio{a});
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanaudio_real_s16_kernel(const CaGroupArgs g) {
+  const ChAudioArgs &a = g.m[blockIdx.y];
+  ch_body<short>(a.c, ChStoreAudio{a});
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanaudio_real_f32_kernel(const CaGroupArgs g) {
+  const ChAudioArgs &a = g.m[blockIdx.y];
+  ch_body<float>(a.c, ChStoreAudio{a});
+}
+
 using CaKernel = void (*)(const ChAudioArgs);
+using CaGroupKernel = void (*)(const CaGroupArgs);
+constexpr CaGroupKernel CAG_KERNELS[2][2] = {{group_chanaudio_cs16_kernel, group_chanaudio_cf32_kernel},
+                                             {group_chanaudio_real_s16_kernel, group_chanaudio_real_f32_kernel}};
+constexpr const char *CAG_NAMES[2][2] = {{"group_chanaudio_cs16_kernel", "group_chanaudio_cf32_kernel"},
+                                         {"group_chanaudio_real_s16_kernel", "group_chanaudio_real_f32_kernel"}};
 constexpr CaKernel CA_KERNELS[2][2] = {{chanaudio_cs16_kernel, chanaudio_cf32_kernel}, {chanaudio_real_s16_kernel, chanaudio_real_f32_kernel}};
 constexpr const char *CA_NAMES[2][2] = {{"chanaudio_cs16_kernel", "chanaudio_cf32_kernel"}, {"chanaudio_real_s16_kernel", "chanaudio_real_f32_kernel"}};
 
@@ -118,13 +144,18 @@ struct sdrhip_chanaudio : ChPlan {
     fresh_tail();   // (synchronises, and cur = 0)
   }
   void require_row(int row) const { SDRHIP_REQUIRE(row >= 0 && row < n_sel, SDRHIP_E_INVALID, "row %d outside [0,%d)", row, n_sel); }
-  // n >= 1
-  void launch(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) {
-    ctx->use();
+  // the arguments of a launch of n >= 1 samples from the current state
+  ChAudioArgs audio_args(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) const {
     ChAudioArgs a;
     a.c = args(in_dev, n, out_dev, out_stride, n_out);
     a.mode = mode.p; a.gain = gain.p; a.last = last[cur].p; a.last_new = last[cur ^ 1].p;
     a.fm_rows = fm_rows();
+    return a;
+  }
+  // n >= 1
+  void launch(const void *in_dev, size_t n, void *out_dev, size_t out_stride, size_t n_out) {
+    ctx->use();
+    const ChAudioArgs a = audio_args(in_dev, n, out_dev, out_stride, n_out);
     launch_tiles(kernel(), a.c.tiles, lds_bytes(), n, a);
   }
 };
@@ -165,9 +196,27 @@ int get_rows(sdrhip_chanaudio *h, const std::vector<X> sdrhip_chanaudio::*per_ch
   });
 }
 
+// the row call of an audio group
+void group_rows(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, void *const *out_dev, const size_t *out_stride,
+                size_t *n_out) {
+  cg_process_rows<sdrhip_chanaudio>(g, g->member[0]->pick(CAG_KERNELS), sizeof(short), in_dev, n, out_dev, out_stride, n_out,
+                                    [](sdrhip_chanaudio *h, const void *in, void *out, const CgCall &c) {
+                                      return h->audio_args(in, c.n, out, c.stride, c.no);
+                                    });
+}
+
 }  // namespace
 
 extern "C" {
+
+int sdrhip_changroup_audio_create(sdrhip_chanaudio *const *members, int count, sdrhip_changroup **out) {
+  return cg_create(members, count, out, [](sdrhip_changroup *g) {
+    allow_lds_max(g->member[0]->pick(CAG_KERNELS), g->lds);
+    g->grid_x = cg_grid_tiles(g);
+    g->names = g->member[0]->pick(CAG_NAMES);
+    g->rows = group_rows;
+  });
+}
 
 int sdrhip_chanaudio_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, const int *modes,
                             const float *gains, sdrhip_chanaudio **out) {

@@ -8,6 +8,8 @@
 // buffer: the blocks of a launch read the old one.
 // A handle of sdrhip_chanreal_channelizer_create (sdrhip_chanreal.h) runs channelizer_real_s16_kernel / channelizer_real_f32_kernel: the
 // body's real form in front of the same epilogue, rows 0 ... M / 2.
+// A group of handles (sdrhip_changroup.h) runs group_channelizer_*_kernel: the member table in the arguments, member blockIdx.y's
+// body; the entry points every group has are at the end of this file.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
 #include "sdrhip_chanreal.h"
@@ -42,7 +44,20 @@ __global__ __launch_bounds__(CH_THREADS) void channelizer_cf32_kernel(const ChAr
 __global__ __launch_bounds__(CH_THREADS) void channelizer_real_s16_kernel(const ChArgs a) { ch_body<short>(a, ChStoreComplex()); }
 __global__ __launch_bounds__(CH_THREADS) void channelizer_real_f32_kernel(const ChArgs a) { ch_body<float>(a, ChStoreComplex()); }
 
+// a group launch (sdrhip_changroup.h): member blockIdx.y's body on its own arguments
+using CgArgs = ChGroupArgs<ChArgs>;
+static_assert(sizeof(CgArgs) <= CG_ARG_BYTES, "the member table travels in the kernel arguments");
+__global__ __launch_bounds__(CH_THREADS) void group_channelizer_cs16_kernel(const CgArgs g) { ch_body<short2>(g.m[blockIdx.y], ChStoreComplex()); }
+__global__ __launch_bounds__(CH_THREADS) void group_channelizer_cf32_kernel(const CgArgs g) { ch_body<float2>(g.m[blockIdx.y], ChStoreComplex()); }
+__global__ __launch_bounds__(CH_THREADS) void group_channelizer_real_s16_kernel(const CgArgs g) { ch_body<short>(g.m[blockIdx.y], ChStoreComplex()); }
+__global__ __launch_bounds__(CH_THREADS) void group_channelizer_real_f32_kernel(const CgArgs g) { ch_body<float>(g.m[blockIdx.y], ChStoreComplex()); }
+
 using ChKernel = void (*)(const ChArgs);
+using CgKernel = void (*)(const CgArgs);
+constexpr CgKernel CG_KERNELS[2][2] = {{group_channelizer_cs16_kernel, group_channelizer_cf32_kernel},
+                                       {group_channelizer_real_s16_kernel, group_channelizer_real_f32_kernel}};
+constexpr const char *CG_NAMES[2][2] = {{"group_channelizer_cs16_kernel", "group_channelizer_cf32_kernel"},
+                                        {"group_channelizer_real_s16_kernel", "group_channelizer_real_f32_kernel"}};
 constexpr ChKernel CH_KERNELS[2][2] = {{channelizer_cs16_kernel, channelizer_cf32_kernel}, {channelizer_real_s16_kernel, channelizer_real_f32_kernel}};
 constexpr const char *CH_NAMES[2][2] = {{"channelizer_cs16_kernel", "channelizer_cf32_kernel"}, {"channelizer_real_s16_kernel", "channelizer_real_f32_kernel"}};
 
@@ -66,9 +81,57 @@ int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_t
   return ch_create(ctx, dtype, M, D, taps, n_taps, max_in, out, real, [] {}, [](sdrhip_channelizer *) {});
 }
 
+// the row call of a channelizer group
+void group_rows(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, void *const *out_dev, const size_t *out_stride,
+                size_t *n_out) {
+  cg_process_rows<sdrhip_channelizer>(g, g->member[0]->pick(CG_KERNELS), sizeof(float2), in_dev, n, out_dev, out_stride, n_out,
+                                      [](sdrhip_channelizer *h, const void *in, void *out, const CgCall &c) {
+                                        return h->args(in, c.n, out, c.stride, c.no);
+                                      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int sdrhip_changroup_channelizer_create(sdrhip_channelizer *const *members, int count, sdrhip_changroup **out) {
+  return cg_create(members, count, out, [](sdrhip_changroup *g) {
+    allow_lds_max(g->member[0]->pick(CG_KERNELS), g->lds);
+    g->grid_x = cg_grid_tiles(g);
+    g->names = g->member[0]->pick(CG_NAMES);
+    g->rows = group_rows;
+  });
+}
+
+// the calls every group has; the family stands behind g->rows (the power call: chanpower.hip)
+int sdrhip_changroup_process_dev(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, void *const *out_dev,
+                                 const size_t *out_stride, size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_changroup_process_dev");
+    SDRHIP_REQUIRE(g, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(g->rows, SDRHIP_E_INVALID, "a power group has no rows: its call is sdrhip_changroup_power_process_dev");
+    g->rows(g, in_dev, n, out_dev, out_stride, n_out);
+  });
+}
+
+int sdrhip_changroup_plan_info(sdrhip_changroup *g, int *members, int *grid_x, int *lds_bytes) {
+  return guarded([&] {
+    SDRHIP_REQUIRE(g, SDRHIP_E_INVALID, "handle is NULL");
+    if (members) *members = g->count;
+    if (grid_x) *grid_x = g->grid_x;
+    if (lds_bytes) *lds_bytes = (int)g->lds;
+  });
+}
+
+int sdrhip_changroup_kernel_names(sdrhip_changroup *g, char *buf, size_t len) {
+  return guarded([&] {
+    write_names(g, buf, len, [&] { return g->names; });
+  });
+}
+
+int sdrhip_changroup_destroy(sdrhip_changroup *g) {
+  return guarded([&] { destroy_handle(g); });
+}
 
 int sdrhip_channelizer_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in,
                               sdrhip_channelizer **out) {

@@ -15,7 +15,9 @@
 //        void store(const ChArgs &, const float2 *img, int j0, int Tc, int halo, int tid)   the tile's outputs; image halo + tt
 //                                                                    holds output time j0 + tt
 //        void roll<I>(const ChArgs &, int tid)                       every block, behind its tiles (ch_roll_tail at least)
-// ch_body gives a workgroup one tile; ch_body_strided walks a launch of fewer workgroups than tiles over them (chanpower.hip).
+// ch_body gives a workgroup one tile; ch_body_strided walks a launch of fewer workgroups than tiles over them (chanpower.hip),
+// ch_body_stride does so with the stride as an argument, inside a group launch (sdrhip_changroup.h: ChGroupArgs, and at the end of
+// this file the group's host layer).
 // An output time is computed with the same operations in the same order whichever policy asks and wherever it lies in a tile
 // (the library is built with -ffp-contract=off, and the one fused operation is written as such), so the kernel families
 // agree bit for bit on the spectra.
@@ -31,6 +33,7 @@
 #pragma once
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
+#include "sdrhip_changroup.h"
 #include "entry.hpp"
 #include "fftgen.hpp"
 
@@ -256,6 +259,28 @@ __device__ __forceinline__ void ch_body_strided(const ChArgs &a, const E &epi) {
   if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
   else epi.template roll<I>(a, tid);
 }
+
+// the same inside a launch whose gridDim.x is not the walk's own (a member of a group launch, sdrhip_changroup.h): the first W
+// workgroups take the tiles b, b + W, ... in that order — what a launch of W workgroups gives them — and the others take none;
+// every workgroup of the launch rolls its share of the tail
+template <class I, class E>
+__device__ __forceinline__ void ch_body_stride(const ChArgs &a, const E &epi, int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float2 *img = reinterpret_cast<float2 *>(smem_raw);
+  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+  const int tid = (int)threadIdx.x;
+  if ((int)blockIdx.x < W)
+    for (int tile = (int)blockIdx.x; tile < a.tiles; tile += W) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
+  else epi.template roll<I>(a, tid);
+}
+
+// the member table of a group launch, by value in the kernel arguments: workgroup (x, y) runs member y's body on m[y]. The
+// index is blockIdx.y, so the pick is a scalar load from the argument segment.
+constexpr int CG_MAX = SDRHIP_CHANGROUP_MAX;
+constexpr size_t CG_ARG_BYTES = 4096;   // what a launch's argument segment may hold (eight ChAudioArgs are 2112 bytes)
+template <class A>
+struct ChGroupArgs { A m[CG_MAX]; };
 
 // ---- host side: what the handle types hold and do ----------------------------------------------------------------------------
 // the argument rules of create, in the header's order (before the context: host rules); h32: the taps rounded once to float32
@@ -512,6 +537,115 @@ static inline int ch_kernel_names(H *h, char *buf, size_t len, const char *const
   return guarded([&] {
     write_names(h, buf, len, [&] { return h->pick(names); });
   });
+}
+
+}  // namespace sdrhip
+
+// ---- the channel group (sdrhip_changroup.h): borrowed handles of one type H : ChPlan behind one launch --------------------------
+// One struct for the three families; what differs — the member type, its argument struct, its kernels — stands behind the
+// two calls a family's create fills in (channelizer.hip, chanaudio.hip, chanpower.hip).
+struct sdrhip_changroup {
+  sdrhip_ctx *ctx = nullptr;
+  int count = 0;
+  sdrhip::ChPlan *member[sdrhip::CG_MAX] = {};   // the handles as H * (H derives from ChPlan alone)
+  size_t lds = 0;                                // the launch's dynamic LDS: the largest member's
+  int grid_x = 1;                                // plan_info's
+  const char *names = "";
+  // the row call and the power call of the family, inside the entry point's guarded(); NULL where the family has none
+  void (*rows)(sdrhip_changroup *, const void *const *, const size_t *, void *const *, const size_t *, size_t *) = nullptr;
+  void (*sums)(sdrhip_changroup *, const void *const *, const size_t *, double *const *, size_t *) = nullptr;
+};
+
+namespace sdrhip {
+
+// a member's share of an accepted group call
+struct CgCall { int i; size_t n, no, stride; };
+struct CgExtent { uintptr_t b, e; };
+static inline bool cg_meet(const CgExtent &a, const CgExtent &b) { return a.b < a.e && b.b < b.e && a.b < b.e && b.b < a.e; }
+// the rule between members: no output over another member's input, nor over another member's output (a member's own pair is its
+// own call's rule, checked before)
+static inline void cg_require_disjoint(const CgCall *c, int na, const CgExtent *in, const CgExtent *out) {
+  for (int a = 0; a < na; a++)
+    for (int b = 0; b < na; b++) {
+      if (a == b) continue;
+      SDRHIP_REQUIRE(!cg_meet(out[a], in[b]), SDRHIP_E_INVALID, "the output range of member %d overlaps the input range of member %d", c[a].i,
+                     c[b].i);
+      SDRHIP_REQUIRE(a > b || !cg_meet(out[a], out[b]), SDRHIP_E_INVALID, "the output range of member %d overlaps the output range of member %d",
+                     c[a].i, c[b].i);
+    }
+}
+
+// The create calls' rules, in the header's order, and the handle. fill(g): the family's kernel limit, names and calls.
+template <class H, class Fill>
+static inline int cg_create(H *const *members, int count, sdrhip_changroup **out, Fill &&fill) {
+  return guarded([&] {
+    if (out) *out = nullptr;
+    SDRHIP_REQUIRE(out && members, SDRHIP_E_INVALID, "NULL argument");
+    SDRHIP_REQUIRE(count >= 1 && count <= CG_MAX, SDRHIP_E_SIZE, "count %d outside [1,%d]", count, CG_MAX);
+    for (int i = 0; i < count; i++) SDRHIP_REQUIRE(members[i], SDRHIP_E_INVALID, "member %d is NULL", i);
+    for (int i = 1; i < count; i++)
+      for (int j = 0; j < i; j++) SDRHIP_REQUIRE(members[i] != members[j], SDRHIP_E_INVALID, "member %d is member %d again", i, j);
+    for (int i = 1; i < count; i++)
+      SDRHIP_REQUIRE(members[i]->ctx == members[0]->ctx, SDRHIP_E_INVALID, "member %d is on another context than member 0", i);
+    for (int i = 1; i < count; i++)
+      SDRHIP_REQUIRE(members[i]->dtype == members[0]->dtype && members[i]->real == members[0]->real, SDRHIP_E_INVALID,
+                     "member %d has another input element type than member 0", i);
+    make_handle(members[0]->ctx, out, true, [&](sdrhip_changroup *g) {
+      g->count = count;
+      for (int i = 0; i < count; i++) {
+        g->member[i] = members[i];
+        g->lds = std::max(g->lds, members[i]->lds_bytes());
+      }
+      fill(g);
+    });
+  });
+}
+
+// plan_info's grid_x of a family whose launch has a workgroup per tile
+static inline int cg_grid_tiles(const sdrhip_changroup *g) {
+  size_t gx = 1;
+  for (int i = 0; i < g->count; i++) gx = std::max(gx, ceil_div(g->member[i]->out_count_max(g->member[i]->max_in), (size_t)g->member[i]->T));
+  return (int)gx;
+}
+
+// The row call of a group of H with rows of `ob` bytes per element: every member's own rules (ch_process_dev's, in its order),
+// then the rules between members, then ONE launch — table(h, call) is the member's entry of the kernel's table A — and only
+// behind it the members' states move on.
+template <class H, class A, class Table>
+static inline void cg_process_rows(sdrhip_changroup *g, void (*kernel)(const ChGroupArgs<A>), size_t ob, const void *const *in_dev,
+                                   const size_t *n, void *const *out_dev, const size_t *out_stride, size_t *n_out, Table &&table) {
+  SDRHIP_REQUIRE(in_dev && n && out_dev && out_stride, SDRHIP_E_INVALID, "NULL argument");
+  for (int i = 0; n_out && i < g->count; i++) n_out[i] = 0;
+  CgCall c[CG_MAX];
+  CgExtent in[CG_MAX], out[CG_MAX];
+  int na = 0;
+  for (int i = 0; i < g->count; i++) {
+    H *h = static_cast<H *>(g->member[i]);
+    if (!call_begin(h, "n", n[i], in_dev[i], out_dev[i])) continue;
+    const size_t no = h->out_count(n[i]), rows = (size_t)h->n_sel;
+    const Strides s = call_strides("n", n[i], 0, no, out_stride[i], STRIDE_OUT);
+    require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), out_dev[i], s.out, no, ob, 1, rows);
+    in[na] = {(uintptr_t)in_dev[i], (uintptr_t)in_dev[i] + n[i] * h->in_elem()};
+    out[na] = {(uintptr_t)out_dev[i], (uintptr_t)out_dev[i] + (no ? ((rows - 1) * s.out + no) * ob : 0)};
+    c[na++] = {i, n[i], no, s.out};
+  }
+  cg_require_disjoint(c, na, in, out);
+  if (!na) return;
+  g->ctx->use();
+  ChGroupArgs<A> t;
+  int gx = 1;
+  for (int k = 0; k < na; k++) {
+    t.m[k] = table(static_cast<H *>(g->member[c[k].i]), in_dev[c[k].i], out_dev[c[k].i], c[k]);
+    gx = std::max(gx, (int)ceil_div(c[k].no, (size_t)g->member[c[k].i]->T));
+  }
+  for (int k = na; k < CG_MAX; k++) t.m[k] = t.m[0];   // (never read: grid.y is na)
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)na), dim3(CH_THREADS), g->lds, g->ctx->stream, t);
+  SDRHIP_CHECK_HIP(hipGetLastError());
+  for (int k = 0; k < na; k++) {
+    g->member[c[k].i]->advance(c[k].n);
+    if (n_out) n_out[c[k].i] = c[k].no;
+  }
 }
 
 }  // namespace sdrhip

@@ -12,6 +12,8 @@
 // A handle of sdrhip_chanreal_power_create (sdrhip_chanreal.h) runs chanpower_real_s16_kernel / chanpower_real_f32_kernel: the body's real
 // form in front of the same epilogue; the partial buffer, the finish launch and every per-channel array then take nch = M / 2 + 1
 // channels.
+// A group of handles (sdrhip_changroup.h) runs group_chanpower_*_kernel — the bounded walk with the member's own stride W, whatever
+// the launch's gridDim.x — and group_chanpower_finish_kernel, blockIdx.y the member.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanpower.h"
 #include "sdrhip_chanreal.h"
@@ -80,6 +82,8 @@ struct CpFinishArgs {
   int M, rows, J, first;            // M: the handle's channels (nch); rows: the workgroups that ran (0 where J = 0); first: calls == 0
 };
 
+// (group_chanpower_finish_kernel below holds these statements a second time: a change to one is a change to both — a member's
+// sums, levels and flags are bit for bit its own only while the two agree)
 __global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFinishArgs f) {
   const int k = (int)blockIdx.x * CH_THREADS + (int)threadIdx.x;
   if (k >= f.M) return;
@@ -103,6 +107,68 @@ __global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFi
   f.open[k] = f.open[k] ? !(level < f.close_thr[k]) : level >= f.open_thr[k];
 }
 
+// A group launch (sdrhip_changroup.h): member blockIdx.y's body on its own arguments. W is the stride of the member's own launch,
+// min(tiles, G): the first W workgroups of the row walk the tiles as that launch's would, each on its own row of the member's
+// partial buffer, so the finish step adds the same rows in the same order.
+struct CpGroupMember {
+  ChArgs a;
+  double *partial;   // [G][nch], the member's
+  int W;
+};
+using CpGroupArgs = ChGroupArgs<CpGroupMember>;
+using CpGroupFinishArgs = ChGroupArgs<CpFinishArgs>;
+static_assert(sizeof(CpGroupArgs) <= CG_ARG_BYTES && sizeof(CpGroupFinishArgs) <= CG_ARG_BYTES, "the member table travels in the kernel arguments");
+
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_cs16_kernel(const CpGroupArgs g) {
+  const CpGroupMember &m = g.m[blockIdx.y];
+  ch_body_stride<short2>(m.a, ChStorePower{m.partial}, m.W);
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_cf32_kernel(const CpGroupArgs g) {
+  const CpGroupMember &m = g.m[blockIdx.y];
+  ch_body_stride<float2>(m.a, ChStorePower{m.partial}, m.W);
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_real_s16_kernel(const CpGroupArgs g) {
+  const CpGroupMember &m = g.m[blockIdx.y];
+  ch_body_stride<short>(m.a, ChStorePower{m.partial}, m.W);
+}
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_real_f32_kernel(const CpGroupArgs g) {
+  const CpGroupMember &m = g.m[blockIdx.y];
+  ch_body_stride<float>(m.a, ChStorePower{m.partial}, m.W);
+}
+
+// chanpower_finish_kernel's statements on member blockIdx.y's arguments (that kernel's text stays what it is, so they stand
+// here a second time): the same adds in the same order, the same level and flag step. EDIT THE TWO TOGETHER; the parity test of
+// the group (tests/test_gpu_parity_changroup.py, levels and flags against a twin handle) fails when they drift apart.
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_finish_kernel(const CpGroupFinishArgs g) {
+  const CpFinishArgs &f = g.m[blockIdx.y];
+  const int k = (int)blockIdx.x * CH_THREADS + (int)threadIdx.x;
+  if (k >= f.M) return;
+  const double *col = f.partial + k;
+  double s = 0.0;
+  int b = 0;
+  for (; b + CP_BATCH <= f.rows; b += CP_BATCH) {
+    double v[CP_BATCH];
+#pragma unroll
+    for (int i = 0; i < CP_BATCH; i++) v[i] = col[(size_t)(b + i) * (size_t)f.M];
+#pragma unroll
+    for (int i = 0; i < CP_BATCH; i++) s += v[i];
+  }
+  for (; b < f.rows; b++) s += col[(size_t)b * (size_t)f.M];
+  if (f.sum) f.sum[k] = s;
+  if (f.J <= 0) return;
+  const double mean = s / (double)f.J, old = f.level[k];
+  const double level = f.first ? mean : old + f.alpha * (mean - old);
+  f.level[k] = level;
+  f.open[k] = f.open[k] ? !(level < f.close_thr[k]) : level >= f.open_thr[k];
+}
+
+using CpGroupKernel = void (*)(const CpGroupArgs);
+constexpr CpGroupKernel CPG_KERNELS[2][2] = {{group_chanpower_cs16_kernel, group_chanpower_cf32_kernel},
+                                             {group_chanpower_real_s16_kernel, group_chanpower_real_f32_kernel}};
+constexpr const char *CPG_NAMES[2][2] = {
+    {"group_chanpower_cs16_kernel,group_chanpower_finish_kernel", "group_chanpower_cf32_kernel,group_chanpower_finish_kernel"},
+    {"group_chanpower_real_s16_kernel,group_chanpower_finish_kernel", "group_chanpower_real_f32_kernel,group_chanpower_finish_kernel"}};
+
 void require_alpha(double alpha) {
   SDRHIP_REQUIRE(alpha > 0.0 && alpha <= 1.0, SDRHIP_E_INVALID, "alpha %g outside (0,1]", alpha);   // (a NaN fails both)
 }
@@ -123,6 +189,13 @@ struct sdrhip_chanpower : ChPlan {
     fresh_tail();   // (synchronises)
     calls = 0;
   }
+  // the finish step's arguments behind a main launch of `rows` workgroups
+  CpFinishArgs finish_args(double *sum_dev, int rows, size_t n_out) const {
+    CpFinishArgs f;
+    f.partial = partial.p; f.open_thr = thr_open.p; f.close_thr = thr_close.p; f.level = level.p; f.open = open.p; f.sum = sum_dev;
+    f.alpha = alpha; f.M = nch; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
+    return f;
+  }
   // n >= 1; sum_dev may be NULL
   void launch(const void *in_dev, size_t n, double *sum_dev, size_t n_out) {
     ctx->use();
@@ -130,9 +203,7 @@ struct sdrhip_chanpower : ChPlan {
     const int rows = std::min(a.tiles, G);
     launch_tiles(kernel(), rows, lds_bytes(), n, a, partial.p);
     if (n_out == 0 && !sum_dev) return;
-    CpFinishArgs f;
-    f.partial = partial.p; f.open_thr = thr_open.p; f.close_thr = thr_close.p; f.level = level.p; f.open = open.p; f.sum = sum_dev;
-    f.alpha = alpha; f.M = nch; f.rows = rows; f.J = (int)n_out; f.first = calls == 0;
+    const CpFinishArgs f = finish_args(sum_dev, rows, n_out);
     hipLaunchKernelGGL(chanpower_finish_kernel, dim3((unsigned)ceil_div((size_t)nch, (size_t)CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, f);
     SDRHIP_CHECK_HIP(hipGetLastError());
     if (n_out) calls++;
@@ -164,9 +235,79 @@ int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_t
   });
 }
 
+// The call of a power group: every member's own rules (sdrhip_chanpower_process_dev's, in its order), the rules between members,
+// the main launch, the members' states, and the finish launch over the members whose own call would have one.
+void group_sums(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, double *const *sum_dev, size_t *n_out) {
+  SDRHIP_REQUIRE(in_dev && n, SDRHIP_E_INVALID, "NULL argument");
+  for (int i = 0; n_out && i < g->count; i++) n_out[i] = 0;
+  CgCall c[CG_MAX];
+  CgExtent in[CG_MAX], out[CG_MAX];
+  int na = 0;
+  for (int i = 0; i < g->count; i++) {
+    sdrhip_chanpower *h = static_cast<sdrhip_chanpower *>(g->member[i]);
+    double *sum = sum_dev ? sum_dev[i] : nullptr;
+    if (!call_begin(h, "n", n[i], in_dev[i], sum ? (const void *)sum : in_dev[i])) continue;
+    const size_t no = h->out_count(n[i]);
+    if (sum) require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), sum, (size_t)h->nch, (size_t)h->nch, sizeof(double), 1);
+    in[na] = {(uintptr_t)in_dev[i], (uintptr_t)in_dev[i] + n[i] * h->in_elem()};
+    out[na] = {(uintptr_t)sum, (uintptr_t)sum + (sum ? (size_t)h->nch * sizeof(double) : 0)};
+    c[na++] = {i, n[i], no, 0};
+  }
+  cg_require_disjoint(c, na, in, out);
+  if (!na) return;
+  g->ctx->use();
+  CpGroupArgs t;
+  CpGroupFinishArgs ft;
+  int gx = 1, fx = 1, nf = 0;
+  for (int k = 0; k < na; k++) {
+    sdrhip_chanpower *h = static_cast<sdrhip_chanpower *>(g->member[c[k].i]);
+    double *sum = sum_dev ? sum_dev[c[k].i] : nullptr;
+    t.m[k].a = h->args(in_dev[c[k].i], c[k].n, nullptr, 0, c[k].no);
+    t.m[k].partial = h->partial.p;
+    t.m[k].W = std::min(t.m[k].a.tiles, h->G);
+    gx = std::max(gx, t.m[k].W);
+    if (c[k].no == 0 && !sum) continue;
+    ft.m[nf++] = h->finish_args(sum, t.m[k].W, c[k].no);
+    fx = std::max(fx, (int)ceil_div((size_t)h->nch, (size_t)CH_THREADS));
+  }
+  for (int k = na; k < CG_MAX; k++) t.m[k] = t.m[0];   // (never read: grid.y is na)
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(g->member[0]->pick(CPG_KERNELS), dim3((unsigned)gx, (unsigned)na), dim3(CH_THREADS), g->lds, g->ctx->stream, t);
+  SDRHIP_CHECK_HIP(hipGetLastError());
+  for (int k = 0; k < na; k++) {
+    g->member[c[k].i]->advance(c[k].n);
+    if (n_out) n_out[c[k].i] = c[k].no;
+  }
+  if (!nf) return;
+  for (int k = nf; k < CG_MAX; k++) ft.m[k] = ft.m[0];
+  hipLaunchKernelGGL(group_chanpower_finish_kernel, dim3((unsigned)fx, (unsigned)nf), dim3(CH_THREADS), 0, g->ctx->stream, ft);
+  SDRHIP_CHECK_HIP(hipGetLastError());
+  for (int k = 0; k < na; k++)
+    if (c[k].no) static_cast<sdrhip_chanpower *>(g->member[c[k].i])->calls++;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sdrhip_changroup_power_create(sdrhip_chanpower *const *members, int count, sdrhip_changroup **out) {
+  return cg_create(members, count, out, [](sdrhip_changroup *g) {
+    allow_lds_max(g->member[0]->pick(CPG_KERNELS), g->lds);
+    for (int i = 0; i < g->count; i++) g->grid_x = std::max(g->grid_x, static_cast<sdrhip_chanpower *>(g->member[i])->G);
+    g->names = g->member[0]->pick(CPG_NAMES);
+    g->sums = group_sums;
+  });
+}
+
+int sdrhip_changroup_power_process_dev(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, double *const *sum_dev,
+                                       size_t *n_out) {
+  return guarded([&] {
+    Range roctx_range("sdrhip_changroup_power_process_dev");
+    SDRHIP_REQUIRE(g, SDRHIP_E_INVALID, "handle is NULL");
+    SDRHIP_REQUIRE(g->sums, SDRHIP_E_INVALID, "not a power group: its call is sdrhip_changroup_process_dev");
+    g->sums(g, in_dev, n, sum_dev, n_out);
+  });
+}
 
 int sdrhip_chanpower_create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_taps, size_t max_in, double alpha,
                             sdrhip_chanpower **out) {
