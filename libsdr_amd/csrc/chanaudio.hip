@@ -10,7 +10,8 @@
 // channel's angle there — selected or not, its image has all M bins — and block 0 copies every other entry.
 // A handle of sdrhip_chanreal_audio_create (sdrhip_chanreal.h) runs chanaudio_real_s16_kernel / chanaudio_real_f32_kernel: the body's
 // real form in front of the same epilogue; the per-channel arrays then have nch = M / 2 + 1 entries.
-// A group of handles (sdrhip_changroup.h) runs group_chanaudio_*_kernel: member blockIdx.y's body on its own arguments.
+// A group of handles (sdrhip_changroup.h) runs group_chanaudio_*_kernel: member blockIdx.y's body (ch_body, as alone) on its own
+// arguments; the row call is channelizer_body.hpp's cg_process_rows, as the plain channelizer's.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanaudio.h"
 #include "sdrhip_chanreal.h"
@@ -199,7 +200,7 @@ int get_rows(sdrhip_chanaudio *h, const std::vector<X> sdrhip_chanaudio::*per_ch
 // the row call of an audio group
 void group_rows(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, void *const *out_dev, const size_t *out_stride,
                 size_t *n_out) {
-  cg_process_rows<sdrhip_chanaudio>(g, g->member[0]->pick(CAG_KERNELS), sizeof(short), in_dev, n, out_dev, out_stride, n_out,
+  cg_process_rows<sdrhip_chanaudio>(g, CAG_KERNELS, sizeof(short), in_dev, n, out_dev, out_stride, n_out,
                                     [](sdrhip_chanaudio *h, const void *in, void *out, const CgCall &c) {
                                       return h->audio_args(in, c.n, out, c.stride, c.no);
                                     });

@@ -9,7 +9,8 @@
 // A handle of sdrhip_chanreal_channelizer_create (sdrhip_chanreal.h) runs channelizer_real_s16_kernel / channelizer_real_f32_kernel: the
 // body's real form in front of the same epilogue, rows 0 ... M / 2.
 // A group of handles (sdrhip_changroup.h) runs group_channelizer_*_kernel: the member table in the arguments, member blockIdx.y's
-// body; the entry points every group has are at the end of this file.
+// body (ch_body: a workgroup per tile, as alone). Its row call is channelizer_body.hpp's cg_process_rows, a user of the one group
+// call skeleton cg_call; the entry points every group has are at the end of this file.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
 #include "sdrhip_chanreal.h"
@@ -84,7 +85,7 @@ int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_t
 // the row call of a channelizer group
 void group_rows(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, void *const *out_dev, const size_t *out_stride,
                 size_t *n_out) {
-  cg_process_rows<sdrhip_channelizer>(g, g->member[0]->pick(CG_KERNELS), sizeof(float2), in_dev, n, out_dev, out_stride, n_out,
+  cg_process_rows<sdrhip_channelizer>(g, CG_KERNELS, sizeof(float2), in_dev, n, out_dev, out_stride, n_out,
                                       [](sdrhip_channelizer *h, const void *in, void *out, const CgCall &c) {
                                         return h->args(in, c.n, out, c.stride, c.no);
                                       });

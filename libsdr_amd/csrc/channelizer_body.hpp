@@ -15,21 +15,20 @@
 //        void store(const ChArgs &, const float2 *img, int j0, int Tc, int halo, int tid)   the tile's outputs; image halo + tt
 //                                                                    holds output time j0 + tt
 //        void roll<I>(const ChArgs &, int tid)                       every block, behind its tiles (ch_roll_tail at least)
-// ch_body gives a workgroup one tile; ch_body_strided walks a launch of fewer workgroups than tiles over them (chanpower.hip),
-// ch_body_stride does so with the stride as an argument, inside a group launch (sdrhip_changroup.h: ChGroupArgs, and at the end of
-// this file the group's host layer).
+// The three phases are ONE function, ch_tile. ch_body gives a workgroup one tile; ch_body_walk(W) walks the first W workgroups of
+// a launch over the tiles with stride W — chanpower.hip's launch of fewer workgroups than tiles (W = gridDim.x), and a member's
+// row of a group launch (sdrhip_changroup.h: ChGroupArgs, and at the end of this file the group's host layer).
 // An output time is computed with the same operations in the same order whichever policy asks and wherever it lies in a tile
 // (the library is built with -ffp-contract=off, and the one fused operation is written as such), so the kernel families
 // agree bit for bit on the spectra.
 // The input is read at [0, n) and the tail at [0, n_taps - 1) only: the first output time of a call is not before its first
 // sample, the last not behind its last, and terms at l >= n_taps are skipped.
 //
-// The real-input form (sdrhip_chanreal.h; I = short or float, ChIn<I>::real) is ch_tile_real: the same three phases with a real
-// branch sum (one fma per term, a float tail), the sum packed as component jw & 1 of element jw >> 1 of an M / 2-point image,
-// the M / 2-point plan's passes, and between phases 2 and 3 the untangling pass ch_untangle that leaves the M / 2 + 1 distinct
-// channels at img[tt ld + k], natural order — what the epilogue policies read. A policy is handed the arguments with M replaced
-// by the channels an image holds, M / 2 + 1 (ch_epi_args), so its per-channel loops and strides need no second form. The complex
-// instances see none of this: ChArgs is what it was, and they take the `else` of every `if constexpr`.
+// The real-input form (sdrhip_chanreal.h; I = short or float, ChIn<I>::real) is the same function, apart at three `if constexpr`:
+// a real branch sum (one fma per term, a float tail) packed as component jw & 1 of element jw >> 1 of an M / 2-point image; behind
+// the M / 2-point plan's passes the untangling pass ch_untangle, which leaves the M / 2 + 1 distinct channels at img[tt ld + k],
+// natural order — what the epilogue policies read; and a policy is handed the arguments with M replaced by the channels an image
+// holds, M / 2 + 1 (ch_epi_args), so its per-channel loops and strides need no second form. ChArgs is one struct for both.
 #pragma once
 #include "sdrhip_internal.hpp"
 #include "sdrhip_channelizer.h"
@@ -69,7 +68,7 @@ __device__ __forceinline__ float2 ch_sample(const float2 *p, int i) { return p[i
 __device__ __forceinline__ float ch_sample(const short *p, int i) { return (float)p[i]; }
 __device__ __forceinline__ float ch_sample(const float *p, int i) { return p[i]; }
 
-// the input element decides the form: which tile body runs, and whether the tail is complex or real floats
+// the input element decides the form: which side of ch_tile's `if constexpr` runs, and whether the tail is complex or real floats
 template <class I> struct ChIn { static constexpr bool real = false; };
 template <> struct ChIn<short> { static constexpr bool real = true; };
 template <> struct ChIn<float> { static constexpr bool real = true; };
@@ -104,53 +103,6 @@ __device__ __forceinline__ void ch_roll_tail(const ChArgs &a, int tid) {
   }
 }
 
-// one tile: phases 1 to 3 for the output times [tile T, tile T + Tc). tmod_s, rel_s: the tile's time table, CH_TMAX + 1 entries
-// each. A workgroup that walks several tiles calls this in a loop with nothing in between: the barrier behind a tile's time table
-// also ends the store of the tile before (the images are written behind it), and the table itself is read in phase 1 only, which
-// two barriers separate from the next tile's.
-template <class I, class E>
-__device__ __forceinline__ void ch_tile(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
-  const int M = a.M;
-  const I *in = static_cast<const I *>(a.in);
-  const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
-  for (int tt = tid; tt < Ti; tt += CH_THREADS) {
-    const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
-    tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
-    rel_s[tt] = a.lead + (int)jd;
-  }
-  __syncthreads();
-  // phase 1
-  for (int e = tid; e < Ti * M; e += CH_THREADS) {
-    const int tt = e / M, r = e - tt * M;
-    int rel = rel_s[tt] - r;
-    float re = 0.f, im = 0.f;
-#pragma unroll 4
-    for (int l = r; l < a.n_taps; l += M, rel -= M) {
-      // (the clamps never bind — see the head of the file; they keep a wrong count from becoming a wild read)
-      const float2 v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : a.hist[max(a.HH + rel, 0)];
-      const float hv = a.taps[l];
-      re = __builtin_fmaf(hv, v.x, re);
-      im = __builtin_fmaf(hv, v.y, im);
-    }
-    int jw = r - tmod_s[tt];
-    jw += jw < 0 ? M : 0;
-    img[tt * a.ld + a.invperm[jw]] = make_float2(re, im);
-  }
-  __syncthreads();
-  // phase 2
-  int s = 1;
-  for (int pass = a.fft.npass - 1; pass >= 0; pass--) {
-    const int r = a.fft.radix[pass];
-#define SDRHIP_CH_CALL(R_) ch_pass<R_>(img, a.fft, s, Ti, a.ld, tid)
-    SDRHIP_GEN_RADIX_SWITCH(r, SDRHIP_CH_CALL)
-#undef SDRHIP_CH_CALL
-    __syncthreads();
-    s *= r;
-  }
-  // phase 3
-  epi.store(a, img, j0, Tc, halo, tid);
-}
-
 // the untangling pass over Ti images of the H-point transforms Z of z[j] = w[2 j] + i w[2 j + 1], H = M / 2: lane (tt, k),
 // k in [0, H / 2], takes the pair (k, kp = (H - k) mod H) in place, with a = Z[k], b = Z[kp], (c, s) = untw[k], in float32 and in
 // this order (sdrhip_chanreal.h states it):
@@ -182,35 +134,54 @@ __device__ __forceinline__ ChArgs ch_epi_args(const ChArgs &a) {
   return e;
 }
 
-// ch_tile for a row of real samples: a.M is the definition's M, a.fft and a.invperm are the M / 2-point plan's, an image has
-// M / 2 + 1 elements of a.ld
+// the LDS of a workgroup: the images (dynamic, the launch's) and a tile's time table, CH_TMAX + 1 entries each
+struct ChLds { float2 *img; int *tmod, *rel; };
+__device__ __forceinline__ ChLds ch_lds() {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+  return {reinterpret_cast<float2 *>(smem_raw), tmod_s, rel_s};
+}
+
+// one tile: phases 1 to 3 for the output times [tile T, tile T + Tc). A workgroup that walks several tiles calls this in a loop
+// with nothing in between: the barrier behind a tile's time table also ends the store of the tile before (the images are written
+// behind it), and the table itself is read in phase 1 only, which two barriers separate from the next tile's.
+// A row of real samples (ChIn<I>::real): a.M is the definition's M, a.fft and a.invperm are the M / 2-point plan's, an image has
+// M / 2 + 1 elements of a.ld.
 template <class I, class E>
-__device__ __forceinline__ void ch_tile_real(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
+__device__ __forceinline__ void ch_tile(const ChArgs &a, const E &epi, int tile, const ChLds &lds, int tid) {
+  constexpr bool real = ChIn<I>::real;
   const int M = a.M;
   const I *in = static_cast<const I *>(a.in);
-  const float *hist = reinterpret_cast<const float *>(a.hist);
-  float *imgf = reinterpret_cast<float *>(img);
+  float2 *img = lds.img;
   const int j0 = tile * a.T, Tc = min(a.T, a.n_out - j0), halo = epi.halo(a, j0), Ti = Tc + halo;
   for (int tt = tid; tt < Ti; tt += CH_THREADS) {
     const long long jd = (long long)(j0 - halo + tt) * a.D;   // below n <= 2^30
-    tmod_s[tt] = (int)(((long long)a.tmod0 + jd) % M);
-    rel_s[tt] = a.lead + (int)jd;
+    lds.tmod[tt] = (int)(((long long)a.tmod0 + jd) % M);
+    lds.rel[tt] = a.lead + (int)jd;
   }
   __syncthreads();
   // phase 1
   for (int e = tid; e < Ti * M; e += CH_THREADS) {
     const int tt = e / M, r = e - tt * M;
-    int rel = rel_s[tt] - r;
-    float u = 0.f;
+    int rel = lds.rel[tt] - r;
+    float re = 0.f, im = 0.f;   // (a real row: re alone)
 #pragma unroll 4
     for (int l = r; l < a.n_taps; l += M, rel -= M) {
-      // (the clamps never bind, as in ch_tile)
-      const float v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : hist[max(a.HH + rel, 0)];
-      u = __builtin_fmaf(a.taps[l], v, u);
+      // (the clamps never bind — see the head of the file; they keep a wrong count from becoming a wild read)
+      if constexpr (real) {   // (the tail: the floats at the head of the same buffer)
+        const float v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : reinterpret_cast<const float *>(a.hist)[max(a.HH + rel, 0)];
+        re = __builtin_fmaf(a.taps[l], v, re);
+      } else {
+        const float2 v = rel >= 0 ? ch_sample(in, min(rel, a.n - 1)) : a.hist[max(a.HH + rel, 0)];
+        const float hv = a.taps[l];
+        re = __builtin_fmaf(hv, v.x, re);
+        im = __builtin_fmaf(hv, v.y, im);
+      }
     }
-    int jw = r - tmod_s[tt];
+    int jw = r - lds.tmod[tt];
     jw += jw < 0 ? M : 0;
-    imgf[2 * (tt * a.ld + a.invperm[jw >> 1]) + (jw & 1)] = u;
+    if constexpr (real) reinterpret_cast<float *>(img)[2 * (tt * a.ld + a.invperm[jw >> 1]) + (jw & 1)] = re;
+    else img[tt * a.ld + a.invperm[jw]] = make_float2(re, im);
   }
   __syncthreads();
   // phase 2
@@ -223,56 +194,41 @@ __device__ __forceinline__ void ch_tile_real(const ChArgs &a, const E &epi, int 
     __syncthreads();
     s *= r;
   }
-  ch_untangle(a, img, Ti, tid);
-  __syncthreads();
   // phase 3
-  epi.store(ch_epi_args(a), img, j0, Tc, halo, tid);
+  if constexpr (real) {
+    ch_untangle(a, img, Ti, tid);
+    __syncthreads();
+    epi.store(ch_epi_args(a), img, j0, Tc, halo, tid);
+  } else epi.store(a, img, j0, Tc, halo, tid);
 }
 
-// the tile body of the input type
+// every block, behind its tiles: the policy's roll on the arguments it sees
 template <class I, class E>
-__device__ __forceinline__ void ch_tile_any(const ChArgs &a, const E &epi, int tile, float2 *img, int *tmod_s, int *rel_s, int tid) {
-  if constexpr (ChIn<I>::real) ch_tile_real<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  else ch_tile<I>(a, epi, tile, img, tmod_s, rel_s, tid);
+__device__ __forceinline__ void ch_roll(const ChArgs &a, const E &epi, int tid) {
+  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
+  else epi.template roll<I>(a, tid);
 }
 
-// one tile per workgroup: tile blockIdx.x
+// one tile per workgroup: tile blockIdx.x (not written as the walk at W = gridDim.x: compiled that way the row kernels took 190 to
+// 203 VGPRs for their 79 to 81 — profiles/chan_body_refactor.md)
 template <class I, class E>
 __device__ __forceinline__ void ch_body(const ChArgs &a, const E &epi) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *img = reinterpret_cast<float2 *>(smem_raw);
-  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+  const ChLds lds = ch_lds();
   const int tid = (int)threadIdx.x, tile = (int)blockIdx.x;
-  if (tile < a.tiles) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
-  else epi.template roll<I>(a, tid);
+  if (tile < a.tiles) ch_tile<I>(a, epi, tile, lds, tid);
+  ch_roll<I>(a, epi, tid);
 }
 
-// a bounded grid: workgroup b takes the tiles b, b + gridDim.x, ... in that order
+// a bounded walk of stride W: the first W workgroups of the launch's row take the tiles b, b + W, ... in that order and the others
+// none; every workgroup rolls its share of the tail. W = gridDim.x is a launch of its own with fewer workgroups than tiles
+// (chanpower.hip); a member of a group launch (sdrhip_changroup.h) passes the W of its own launch, whatever gridDim.x is.
 template <class I, class E>
-__device__ __forceinline__ void ch_body_strided(const ChArgs &a, const E &epi) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *img = reinterpret_cast<float2 *>(smem_raw);
-  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
-  const int tid = (int)threadIdx.x;
-  for (int tile = (int)blockIdx.x; tile < a.tiles; tile += (int)gridDim.x) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
-  else epi.template roll<I>(a, tid);
-}
-
-// the same inside a launch whose gridDim.x is not the walk's own (a member of a group launch, sdrhip_changroup.h): the first W
-// workgroups take the tiles b, b + W, ... in that order — what a launch of W workgroups gives them — and the others take none;
-// every workgroup of the launch rolls its share of the tail
-template <class I, class E>
-__device__ __forceinline__ void ch_body_stride(const ChArgs &a, const E &epi, int W) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float2 *img = reinterpret_cast<float2 *>(smem_raw);
-  __shared__ int tmod_s[CH_TMAX + 1], rel_s[CH_TMAX + 1];
+__device__ __forceinline__ void ch_body_walk(const ChArgs &a, const E &epi, int W) {
+  const ChLds lds = ch_lds();
   const int tid = (int)threadIdx.x;
   if ((int)blockIdx.x < W)
-    for (int tile = (int)blockIdx.x; tile < a.tiles; tile += W) ch_tile_any<I>(a, epi, tile, img, tmod_s, rel_s, tid);
-  if constexpr (ChIn<I>::real) epi.template roll<I>(ch_epi_args(a), tid);
-  else epi.template roll<I>(a, tid);
+    for (int tile = (int)blockIdx.x; tile < a.tiles; tile += W) ch_tile<I>(a, epi, tile, lds, tid);
+  ch_roll<I>(a, epi, tid);
 }
 
 // the member table of a group launch, by value in the kernel arguments: workgroup (x, y) runs member y's body on m[y]. The
@@ -608,44 +564,75 @@ static inline int cg_grid_tiles(const sdrhip_changroup *g) {
   return (int)gx;
 }
 
-// The row call of a group of H with rows of `ob` bytes per element: every member's own rules (ch_process_dev's, in its order),
-// then the rules between members, then ONE launch — table(h, call) is the member's entry of the kernel's table A — and only
-// behind it the members' states move on.
-template <class H, class A, class Table>
-static inline void cg_process_rows(sdrhip_changroup *g, void (*kernel)(const ChGroupArgs<A>), size_t ob, const void *const *in_dev,
-                                   const size_t *n, void *const *out_dev, const size_t *out_stride, size_t *n_out, Table &&table) {
-  SDRHIP_REQUIRE(in_dev && n && out_dev && out_stride, SDRHIP_E_INVALID, "NULL argument");
+// A group call of a family of H, whose kernel takes the member table ChGroupArgs<A>: every member's own rules, then the rules
+// between members, then ONE launch of dim3(grid.x, members in the call), and only behind it the members' states move on and n_out
+// is set. `kernels`: the family's [real][dtype] table, picked at the launch. `pointers`: whether the family's further array
+// arguments are all non-NULL — it joins in_dev and n in the one "NULL argument" rule, the first of the call, so that rule stands
+// here once (a family without further arrays passes true). The family supplies
+//   bool own(i, h, CgOwn &)     member i's own rules in its own call's order, first of them call_begin — false: n = 0, the member
+//                               sits the call out — and what they leave: its outputs, its row stride, the bytes it writes
+//   A    entry(h, call)         its entry of the table, from its state before the call (called once per accepted member)
+//   int  grid(h, call, entry)   the workgroups its row of the grid needs
+// -> the accepted calls, for what a family does behind the launch.
+struct CgOwn { size_t no, stride; CgExtent out; };
+struct CgCalls { CgCall c[CG_MAX]; int na = 0; };
+template <class H, class A, class Own, class Entry, class Grid>
+static inline CgCalls cg_call(sdrhip_changroup *g, void (*const (&kernels)[2][2])(const ChGroupArgs<A>), bool pointers,
+                              const void *const *in_dev, const size_t *n, size_t *n_out, Own &&own, Entry &&entry, Grid &&grid) {
+  SDRHIP_REQUIRE(in_dev && n && pointers, SDRHIP_E_INVALID, "NULL argument");
   for (int i = 0; n_out && i < g->count; i++) n_out[i] = 0;
-  CgCall c[CG_MAX];
+  CgCalls r;
+  CgCall *c = r.c;
   CgExtent in[CG_MAX], out[CG_MAX];
   int na = 0;
   for (int i = 0; i < g->count; i++) {
     H *h = static_cast<H *>(g->member[i]);
-    if (!call_begin(h, "n", n[i], in_dev[i], out_dev[i])) continue;
-    const size_t no = h->out_count(n[i]), rows = (size_t)h->n_sel;
-    const Strides s = call_strides("n", n[i], 0, no, out_stride[i], STRIDE_OUT);
-    require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), out_dev[i], s.out, no, ob, 1, rows);
+    CgOwn o;
+    if (!own(i, h, o)) continue;
     in[na] = {(uintptr_t)in_dev[i], (uintptr_t)in_dev[i] + n[i] * h->in_elem()};
-    out[na] = {(uintptr_t)out_dev[i], (uintptr_t)out_dev[i] + (no ? ((rows - 1) * s.out + no) * ob : 0)};
-    c[na++] = {i, n[i], no, s.out};
+    out[na] = o.out;
+    c[na++] = {i, n[i], o.no, o.stride};
   }
   cg_require_disjoint(c, na, in, out);
-  if (!na) return;
+  if (!na) return r;
   g->ctx->use();
   ChGroupArgs<A> t;
   int gx = 1;
   for (int k = 0; k < na; k++) {
-    t.m[k] = table(static_cast<H *>(g->member[c[k].i]), in_dev[c[k].i], out_dev[c[k].i], c[k]);
-    gx = std::max(gx, (int)ceil_div(c[k].no, (size_t)g->member[c[k].i]->T));
+    H *h = static_cast<H *>(g->member[c[k].i]);
+    t.m[k] = entry(h, c[k]);
+    gx = std::max(gx, grid(h, c[k], t.m[k]));
   }
   for (int k = na; k < CG_MAX; k++) t.m[k] = t.m[0];   // (never read: grid.y is na)
   (void)hipGetLastError();
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)na), dim3(CH_THREADS), g->lds, g->ctx->stream, t);
+  hipLaunchKernelGGL(g->member[0]->pick(kernels), dim3((unsigned)gx, (unsigned)na), dim3(CH_THREADS), g->lds, g->ctx->stream, t);
   SDRHIP_CHECK_HIP(hipGetLastError());
   for (int k = 0; k < na; k++) {
     g->member[c[k].i]->advance(c[k].n);
     if (n_out) n_out[c[k].i] = c[k].no;
   }
+  r.na = na;
+  return r;
+}
+
+// The row call of a group of H with rows of `ob` bytes per element: a member's own rules are ch_process_dev's, in its order;
+// table(h, in, out, call) is the member's entry of the kernel's table A; a workgroup per tile.
+template <class H, class A, class Table>
+static inline void cg_process_rows(sdrhip_changroup *g, void (*const (&kernels)[2][2])(const ChGroupArgs<A>), size_t ob,
+                                   const void *const *in_dev, const size_t *n, void *const *out_dev, const size_t *out_stride,
+                                   size_t *n_out, Table &&table) {
+  cg_call<H>(
+      g, kernels, out_dev && out_stride, in_dev, n, n_out,
+      [&](int i, H *h, CgOwn &o) {
+        if (!call_begin(h, "n", n[i], in_dev[i], out_dev[i])) return false;
+        const size_t no = h->out_count(n[i]), rows = (size_t)h->n_sel;
+        const Strides s = call_strides("n", n[i], 0, no, out_stride[i], STRIDE_OUT);
+        require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), out_dev[i], s.out, no, ob, 1, rows);
+        o = {no, s.out, {(uintptr_t)out_dev[i], (uintptr_t)out_dev[i] + (no ? ((rows - 1) * s.out + no) * ob : 0)}};
+        return true;
+      },
+      [&](H *h, const CgCall &c) { return table(h, in_dev[c.i], out_dev[c.i], c); },
+      [](H *h, const CgCall &c, const A &) { return (int)ceil_div(c.no, (size_t)h->T); });
 }
 
 }  // namespace sdrhip

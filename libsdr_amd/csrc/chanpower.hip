@@ -6,14 +6,15 @@
 //      lanes read consecutive LDS words) and adds e = (double)re (double)re + (double)im (double)im, in time order, onto the
 //      workgroup's row of the [grid][M] partial buffer — from +0 on the workgroup's first tile, a read-modify-write by the one
 //      owner of the element on the later ones. No atomics: the order is the header's, whatever the timing.
-// The grid is bounded (ch_body_strided: workgroup b takes the tiles b, b + W, ...), so the partial buffer is. The finish kernel
-// runs behind the launch on the same stream, one lane per channel: the rows of the workgroups that ran, added in row order, the
-// call's sum where asked for, and the level and flag update; calls, J and alpha come from the host as arguments.
+// The grid is bounded (ch_body_walk at W = gridDim.x: workgroup b takes the tiles b, b + W, ...), so the partial buffer is. The
+// finish step (cp_finish) runs behind the launch on the same stream, one lane per channel: the rows of the workgroups that ran,
+// added in row order, the call's sum where asked for, and the level and flag update; calls, J and alpha come from the host as
+// arguments.
 // A handle of sdrhip_chanreal_power_create (sdrhip_chanreal.h) runs chanpower_real_s16_kernel / chanpower_real_f32_kernel: the body's real
 // form in front of the same epilogue; the partial buffer, the finish launch and every per-channel array then take nch = M / 2 + 1
 // channels.
-// A group of handles (sdrhip_changroup.h) runs group_chanpower_*_kernel — the bounded walk with the member's own stride W, whatever
-// the launch's gridDim.x — and group_chanpower_finish_kernel, blockIdx.y the member.
+// A group of handles (sdrhip_changroup.h) runs group_chanpower_*_kernel — the same walk with the member's own stride W, whatever
+// the launch's gridDim.x — and group_chanpower_finish_kernel, the same finish step on member blockIdx.y's arguments.
 #include "sdrhip_internal.hpp"
 #include "sdrhip_chanpower.h"
 #include "sdrhip_chanreal.h"
@@ -55,16 +56,16 @@ struct ChStorePower {
 };
 
 __global__ __launch_bounds__(CH_THREADS) void chanpower_cs16_kernel(const ChArgs a, double *partial) {
-  ch_body_strided<short2>(a, ChStorePower{partial});
+  ch_body_walk<short2>(a, ChStorePower{partial}, (int)gridDim.x);
 }
 __global__ __launch_bounds__(CH_THREADS) void chanpower_cf32_kernel(const ChArgs a, double *partial) {
-  ch_body_strided<float2>(a, ChStorePower{partial});
+  ch_body_walk<float2>(a, ChStorePower{partial}, (int)gridDim.x);
 }
 __global__ __launch_bounds__(CH_THREADS) void chanpower_real_s16_kernel(const ChArgs a, double *partial) {
-  ch_body_strided<short>(a, ChStorePower{partial});
+  ch_body_walk<short>(a, ChStorePower{partial}, (int)gridDim.x);
 }
 __global__ __launch_bounds__(CH_THREADS) void chanpower_real_f32_kernel(const ChArgs a, double *partial) {
-  ch_body_strided<float>(a, ChStorePower{partial});
+  ch_body_walk<float>(a, ChStorePower{partial}, (int)gridDim.x);
 }
 
 using CpKernel = void (*)(const ChArgs, double *);
@@ -82,9 +83,8 @@ struct CpFinishArgs {
   int M, rows, J, first;            // M: the handle's channels (nch); rows: the workgroups that ran (0 where J = 0); first: calls == 0
 };
 
-// (group_chanpower_finish_kernel below holds these statements a second time: a change to one is a change to both — a member's
-// sums, levels and flags are bit for bit its own only while the two agree)
-__global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFinishArgs f) {
+// the finish step of one handle, one lane per channel (by value: the two kernels below hand it their own copy of the arguments)
+__device__ __forceinline__ void cp_finish(const CpFinishArgs f) {
   const int k = (int)blockIdx.x * CH_THREADS + (int)threadIdx.x;
   if (k >= f.M) return;
   // the rows in increasing order, CP_BATCH loads in flight at a time: the adds are a chain, the loads need not wait for it
@@ -107,6 +107,8 @@ __global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFi
   f.open[k] = f.open[k] ? !(level < f.close_thr[k]) : level >= f.open_thr[k];
 }
 
+__global__ __launch_bounds__(CH_THREADS) void chanpower_finish_kernel(const CpFinishArgs f) { cp_finish(f); }
+
 // A group launch (sdrhip_changroup.h): member blockIdx.y's body on its own arguments. W is the stride of the member's own launch,
 // min(tiles, G): the first W workgroups of the row walk the tiles as that launch's would, each on its own row of the member's
 // partial buffer, so the finish step adds the same rows in the same order.
@@ -121,46 +123,23 @@ static_assert(sizeof(CpGroupArgs) <= CG_ARG_BYTES && sizeof(CpGroupFinishArgs) <
 
 __global__ __launch_bounds__(CH_THREADS) void group_chanpower_cs16_kernel(const CpGroupArgs g) {
   const CpGroupMember &m = g.m[blockIdx.y];
-  ch_body_stride<short2>(m.a, ChStorePower{m.partial}, m.W);
+  ch_body_walk<short2>(m.a, ChStorePower{m.partial}, m.W);
 }
 __global__ __launch_bounds__(CH_THREADS) void group_chanpower_cf32_kernel(const CpGroupArgs g) {
   const CpGroupMember &m = g.m[blockIdx.y];
-  ch_body_stride<float2>(m.a, ChStorePower{m.partial}, m.W);
+  ch_body_walk<float2>(m.a, ChStorePower{m.partial}, m.W);
 }
 __global__ __launch_bounds__(CH_THREADS) void group_chanpower_real_s16_kernel(const CpGroupArgs g) {
   const CpGroupMember &m = g.m[blockIdx.y];
-  ch_body_stride<short>(m.a, ChStorePower{m.partial}, m.W);
+  ch_body_walk<short>(m.a, ChStorePower{m.partial}, m.W);
 }
 __global__ __launch_bounds__(CH_THREADS) void group_chanpower_real_f32_kernel(const CpGroupArgs g) {
   const CpGroupMember &m = g.m[blockIdx.y];
-  ch_body_stride<float>(m.a, ChStorePower{m.partial}, m.W);
+  ch_body_walk<float>(m.a, ChStorePower{m.partial}, m.W);
 }
 
-// chanpower_finish_kernel's statements on member blockIdx.y's arguments (that kernel's text stays what it is, so they stand
-// here a second time): the same adds in the same order, the same level and flag step. EDIT THE TWO TOGETHER; the parity test of
-// the group (tests/test_gpu_parity_changroup.py, levels and flags against a twin handle) fails when they drift apart.
-__global__ __launch_bounds__(CH_THREADS) void group_chanpower_finish_kernel(const CpGroupFinishArgs g) {
-  const CpFinishArgs &f = g.m[blockIdx.y];
-  const int k = (int)blockIdx.x * CH_THREADS + (int)threadIdx.x;
-  if (k >= f.M) return;
-  const double *col = f.partial + k;
-  double s = 0.0;
-  int b = 0;
-  for (; b + CP_BATCH <= f.rows; b += CP_BATCH) {
-    double v[CP_BATCH];
-#pragma unroll
-    for (int i = 0; i < CP_BATCH; i++) v[i] = col[(size_t)(b + i) * (size_t)f.M];
-#pragma unroll
-    for (int i = 0; i < CP_BATCH; i++) s += v[i];
-  }
-  for (; b < f.rows; b++) s += col[(size_t)b * (size_t)f.M];
-  if (f.sum) f.sum[k] = s;
-  if (f.J <= 0) return;
-  const double mean = s / (double)f.J, old = f.level[k];
-  const double level = f.first ? mean : old + f.alpha * (mean - old);
-  f.level[k] = level;
-  f.open[k] = f.open[k] ? !(level < f.close_thr[k]) : level >= f.open_thr[k];
-}
+// member blockIdx.y's finish step: the same adds in the same order, the same level and flag step
+__global__ __launch_bounds__(CH_THREADS) void group_chanpower_finish_kernel(const CpGroupFinishArgs g) { cp_finish(g.m[blockIdx.y]); }
 
 using CpGroupKernel = void (*)(const CpGroupArgs);
 constexpr CpGroupKernel CPG_KERNELS[2][2] = {{group_chanpower_cs16_kernel, group_chanpower_cf32_kernel},
@@ -235,55 +214,39 @@ int create(sdrhip_ctx *ctx, int dtype, int M, int D, const double *taps, int n_t
   });
 }
 
-// The call of a power group: every member's own rules (sdrhip_chanpower_process_dev's, in its order), the rules between members,
-// the main launch, the members' states, and the finish launch over the members whose own call would have one.
+// The call of a power group (cg_call): a member's own rules are sdrhip_chanpower_process_dev's, in its order; behind the main launch
+// and the members' states, the finish launch over the members whose own call would have one.
 void group_sums(sdrhip_changroup *g, const void *const *in_dev, const size_t *n, double *const *sum_dev, size_t *n_out) {
-  SDRHIP_REQUIRE(in_dev && n, SDRHIP_E_INVALID, "NULL argument");
-  for (int i = 0; n_out && i < g->count; i++) n_out[i] = 0;
-  CgCall c[CG_MAX];
-  CgExtent in[CG_MAX], out[CG_MAX];
-  int na = 0;
-  for (int i = 0; i < g->count; i++) {
-    sdrhip_chanpower *h = static_cast<sdrhip_chanpower *>(g->member[i]);
-    double *sum = sum_dev ? sum_dev[i] : nullptr;
-    if (!call_begin(h, "n", n[i], in_dev[i], sum ? (const void *)sum : in_dev[i])) continue;
-    const size_t no = h->out_count(n[i]);
-    if (sum) require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), sum, (size_t)h->nch, (size_t)h->nch, sizeof(double), 1);
-    in[na] = {(uintptr_t)in_dev[i], (uintptr_t)in_dev[i] + n[i] * h->in_elem()};
-    out[na] = {(uintptr_t)sum, (uintptr_t)sum + (sum ? (size_t)h->nch * sizeof(double) : 0)};
-    c[na++] = {i, n[i], no, 0};
-  }
-  cg_require_disjoint(c, na, in, out);
-  if (!na) return;
-  g->ctx->use();
-  CpGroupArgs t;
+  using H = sdrhip_chanpower;
+  const auto sum_of = [&](int i) { return sum_dev ? sum_dev[i] : nullptr; };
+  const auto walk_of = [](const H *h, size_t no) { return std::min((int)ceil_div(no, (size_t)h->T), h->G); };   // launch()'s `rows`
+  const CgCalls r = cg_call<H>(
+      g, CPG_KERNELS, true, in_dev, n, n_out,
+      [&](int i, H *h, CgOwn &o) {
+        double *sum = sum_of(i);
+        if (!call_begin(h, "n", n[i], in_dev[i], sum ? (const void *)sum : in_dev[i])) return false;
+        if (sum) require_disjoint(in_dev[i], n[i], n[i], h->in_elem(), sum, (size_t)h->nch, (size_t)h->nch, sizeof(double), 1);
+        o = {h->out_count(n[i]), 0, {(uintptr_t)sum, (uintptr_t)sum + (sum ? (size_t)h->nch * sizeof(double) : 0)}};
+        return true;
+      },
+      [&](H *h, const CgCall &c) { return CpGroupMember{h->args(in_dev[c.i], c.n, nullptr, 0, c.no), h->partial.p, walk_of(h, c.no)}; },
+      [](H *, const CgCall &, const CpGroupMember &m) { return m.W; });
+  // the finish table: the members whose own call would have that step (finish_args reads `calls`, which moves only below)
   CpGroupFinishArgs ft;
-  int gx = 1, fx = 1, nf = 0;
-  for (int k = 0; k < na; k++) {
-    sdrhip_chanpower *h = static_cast<sdrhip_chanpower *>(g->member[c[k].i]);
-    double *sum = sum_dev ? sum_dev[c[k].i] : nullptr;
-    t.m[k].a = h->args(in_dev[c[k].i], c[k].n, nullptr, 0, c[k].no);
-    t.m[k].partial = h->partial.p;
-    t.m[k].W = std::min(t.m[k].a.tiles, h->G);
-    gx = std::max(gx, t.m[k].W);
-    if (c[k].no == 0 && !sum) continue;
-    ft.m[nf++] = h->finish_args(sum, t.m[k].W, c[k].no);
+  int fx = 1, nf = 0;
+  for (int k = 0; k < r.na; k++) {
+    const CgCall &c = r.c[k];
+    H *h = static_cast<H *>(g->member[c.i]);
+    if (c.no == 0 && !sum_of(c.i)) continue;
+    ft.m[nf++] = h->finish_args(sum_of(c.i), walk_of(h, c.no), c.no);
     fx = std::max(fx, (int)ceil_div((size_t)h->nch, (size_t)CH_THREADS));
-  }
-  for (int k = na; k < CG_MAX; k++) t.m[k] = t.m[0];   // (never read: grid.y is na)
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(g->member[0]->pick(CPG_KERNELS), dim3((unsigned)gx, (unsigned)na), dim3(CH_THREADS), g->lds, g->ctx->stream, t);
-  SDRHIP_CHECK_HIP(hipGetLastError());
-  for (int k = 0; k < na; k++) {
-    g->member[c[k].i]->advance(c[k].n);
-    if (n_out) n_out[c[k].i] = c[k].no;
   }
   if (!nf) return;
   for (int k = nf; k < CG_MAX; k++) ft.m[k] = ft.m[0];
   hipLaunchKernelGGL(group_chanpower_finish_kernel, dim3((unsigned)fx, (unsigned)nf), dim3(CH_THREADS), 0, g->ctx->stream, ft);
   SDRHIP_CHECK_HIP(hipGetLastError());
-  for (int k = 0; k < na; k++)
-    if (c[k].no) static_cast<sdrhip_chanpower *>(g->member[c[k].i])->calls++;
+  for (int k = 0; k < r.na; k++)
+    if (r.c[k].no) static_cast<H *>(g->member[r.c[k].i])->calls++;
 }
 
 }  // namespace
