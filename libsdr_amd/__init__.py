@@ -18,6 +18,7 @@ from .channelizer import Channelizer  # noqa: F401
 from .chanaudio import AudioChannelizer  # noqa: F401
 from .chanpower import ChannelPower  # noqa: F401
 from .changroup import ChannelGroup  # noqa: F401
+from .synthesis import Synthesis  # noqa: F401
 from . import baudot  # noqa: F401
 from .baudot import Baudot, BaudotBank  # noqa: F401
 from . import ax25  # noqa: F401
